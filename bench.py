@@ -10,13 +10,16 @@ region).  --config selects which BASELINE.json configuration is the headline of 
     streams1024  configs[2]/[3]: 1024 concurrent streams / GPU, seq_len 40, last-row output (what RTRunnerMin.step consumes)
     scaled512    configs[4]: 12 layers, d=1024, ffn=4096, seq_len 80, batch 512 / GPU (4096 over 8 GPUs), full output
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--config streams1024]
 
-At N = 1 the default run also puts every other BASELINE configuration on the same clock (`extra.configs`: B=1 latency with
-and without the PCIe hops, 1024 closed-loop streams, B=1024 last-row, B=8192, the scaled model) and holds the headline step
-for >= 3 s (`extra.sustained`) so that the clock actually held is known.
+A plain run sets up, warms up, times the K steps and prints the headline line; --dump-outputs DIR also writes the last timed
+step's output to DIR/y.npy (float32).  Everything else is measured only with --full: the cross-rank self-checks (packed image
+and probe-window outputs identical on every rank), north_star's table on this run's N GPUs (`extra.scaling_table`), the CPU
+baseline and, at N = 1, every other BASELINE configuration on the same clock (`extra.configs`: B=1 latency with and without
+the PCIe hops, 1024 closed-loop streams, B=1024 last-row, B=8192, the scaled model) and the headline step held for >= 3 s
+(`extra.sustained`) so that the clock actually held is known.
 """
 import argparse
 import contextlib
@@ -133,6 +136,21 @@ def probe_outputs(model, cfg, dev, T, batch_xi, batch_xs, last):
     y_in = (model.forward_last(xi2, xs2) if last else model(xi2, xs2))[:n]
     torch.cuda.synchronize()
     return torch.cat([output_digest(y_alone), output_digest(y_in)])
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs: at most this much in all, over every rank
+
+
+def dump_outputs(out_dir, y, rank, world):
+    """--dump-outputs: the last timed step's output as float32 .npy — DIR/y.npy (one rank) or DIR/y_rank<r>.npy.  Above the
+    byte budget, a fixed sample of whole windows (seeded, sorted, the same for the same shape) stands in for the batch."""
+    y = y.detach().float().cpu().numpy()
+    budget = DUMP_BYTES // world
+    if y.nbytes > budget:
+        keep = max(1, budget // (y[0].nbytes or 1))
+        y = y[np.sort(np.random.default_rng(0).choice(y.shape[0], keep, replace=False))]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "y.npy" if world == 1 else f"y_rank{rank}.npy"), np.ascontiguousarray(y))
 
 
 def frac_of_peak(cfg, T, windows_per_s, n_gpus=1):
@@ -654,13 +672,22 @@ def main():
     ap.add_argument("--seq-len", type=int, default=0)
     ap.add_argument("--plan", default="auto", choices=["auto", "general", "fused", "latency", "fused2", "fusedh", "fused1s"])
     ap.add_argument("--rnn-cluster", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip extra.configs / extra.sustained / extra.scaling_table (headline line only)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the cross-rank self-checks, the CPU baseline and the extras (extra.configs / extra.sustained / "
+                         "extra.scaling_table); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output to DIR/y.npy (float32; a seeded sample of windows above 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip extra.configs / extra.sustained / extra.scaling_table")
     ap.add_argument("--no-scaled", action="store_true", help="scaling table without the scaled-model row (BASELINE configs[4])")
     ap.add_argument("--sustain-s", type=float, default=3.0)
     ap.add_argument("--prewarm-s", type=float, default=0.5, help="untimed seconds of the same step before the warm-up (clock ramp)")
     ap.add_argument("--profile-all", action="store_true", help="print a per-stage time table (separate pass)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    extras = args.full and not args.no_extra
+    cpu_leg = args.full and not args.no_cpu_baseline
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))   # `python bench.py --gpus N` starts its own N ranks (one per GPU)
@@ -712,11 +739,13 @@ def main():
     packed = tdist.broadcast_packed(model, src=0, device=dev)      # one-time RCCL broadcast (no-op collective at N=1)
     torch.cuda.synchronize()
     bcast_ms = (time.perf_counter() - t_b0) * 1e3
-    # every rank must hold rank 0's image, bit for bit
-    csum = packed.view(torch.int32).to(torch.int64).sum().reshape(1)
-    sums = gather_all(csum)
-    image_equal = all(int(s.item()) == int(sums[0].item()) for s in sums)
-    assert image_equal, "a rank's packed weight image differs from rank 0's after the broadcast"
+    image_equal = None
+    if args.full:
+        # every rank must hold rank 0's image, bit for bit
+        csum = packed.view(torch.int32).to(torch.int64).sum().reshape(1)
+        sums = gather_all(csum)
+        image_equal = all(int(s.item()) == int(sums[0].item()) for s in sums)
+        assert image_equal, "a rank's packed weight image differs from rank 0's after the broadcast"
     model.set_plan(args.plan, rnn_cluster=args.rnn_cluster, profile=0)
 
     x_imu, x_s = synth.make_inputs(cfg, min(B, 256), T, seed=1234 + rank)
@@ -756,12 +785,16 @@ def main():
         model.set_plan(args.plan, rnn_cluster=args.rnn_cluster, profile=0)
     assert torch.isfinite(y).all()
     model.check_handoffs()                 # a lost inter-workgroup hand-off is an error, not a number
-    # every rank's outputs for the same probe windows must be rank 0's, bit for bit
-    with torch.no_grad():
-        dig = probe_outputs(model, cfg, dev, T, xi, xs, last)
-    digs = gather_all(dig)
-    outputs_equal = all(torch.equal(d_, digs[0]) for d_ in digs)
-    assert outputs_equal, f"rank outputs differ for identical probe windows: {[d_.tolist() for d_ in digs]}"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, y, rank, world)
+    outputs_equal, digs = None, None
+    if args.full:
+        # every rank's outputs for the same probe windows must be rank 0's, bit for bit
+        with torch.no_grad():
+            dig = probe_outputs(model, cfg, dev, T, xi, xs, last)
+        digs = gather_all(dig)
+        outputs_equal = all(torch.equal(d_, digs[0]) for d_ in digs)
+        assert outputs_equal, f"rank outputs differ for identical probe windows: {[d_.tolist() for d_ in digs]}"
     my_ms = elapsed / args.steps * 1e3
     rank_ms = [my_ms]
     if use_pg:
@@ -800,7 +833,7 @@ def main():
                         "sampling": "HIP event pair around every 4th launch of the kernel inside the timed region"}
 
     extra = {}
-    if args.config == "paper256" and not args.no_extra:
+    if args.config == "paper256" and extras:
         # north_star's table on this run's N GPUs, every row with the headline's barrier + max-over-ranks timing:
         #   batch1_per_gpu      one stream per GPU (the latency case; frames/s = N / step time)
         #   batch256_total      256 windows in total, 256 / N per GPU, full output: the headline workload STRONG-scaled (the headline
@@ -888,7 +921,7 @@ def main():
         model.check_handoffs()
         extra["scaling_table"] = table
     with torch.no_grad():
-        if rank == 0 and world == 1 and not args.no_extra:
+        if rank == 0 and world == 1 and extras:
             extra["sustained"] = sustained_pass(step, my_ms, args.sustain_s)
             sus = extra["sustained"]
             if sus.get("sclk_ghz_s_memtime"):
@@ -912,7 +945,7 @@ def main():
     model.check_handoffs()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:     # N = 1 only (the N > 1 lines carry the GPU table; the host cores are the same box's)
+    if rank == 0 and world == 1 and cpu_leg:                      # N = 1 only (the N > 1 lines carry the GPU table; the host cores are the same box's)
         if pin.get("pinned"):                                       # the CPU leg may use every core the process was given
             os.sched_setaffinity(0, range(os.cpu_count()))
         cpu = cpu_baseline(synth.PAPER, 256, 40, budget_s=10.0)
@@ -934,7 +967,7 @@ def main():
             "world_size": world, "backend": ("nccl (RCCL)" if backend == "nccl" else backend) if use_pg else "single process",
             "per_rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms), "all": rank_ms},
             "packed_image_identical_on_all_ranks": image_equal,
-            "ranks_output_identical": outputs_equal, "probe_output_digest": [int(v) for v in digs[0].tolist()],
+            "ranks_output_identical": outputs_equal, "probe_output_digest": [int(v) for v in digs[0].tolist()] if digs else None,
             "weight_broadcast_ms": bcast_ms, "prewarm_s": args.prewarm_s,
             "host_pinning": pins, "wall_s": time.perf_counter() - t_main0,
             "extra": extra,

@@ -30,7 +30,7 @@ def test_bench_under_torchrun_with_rccl(config):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
-           "--config", config, "--no-extra", "--no-cpu-baseline"]
+           "--config", config, "--full", "--no-extra", "--no-cpu-baseline"]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -55,7 +55,7 @@ def test_bench_world_size_2_on_one_gpu():
     dependent line of it runs with world_size 2 — broadcast of the packed image, image checksums, probe-window output digests
     (`ranks_output_identical`), max-over-ranks timing, the scaling table."""
     res = _torchrun(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--plan", "fusedh",
-                        "--rnn-cluster", "1", "--no-cpu-baseline", "--prewarm-s", "0.05"],
+                        "--rnn-cluster", "1", "--full", "--no-cpu-baseline", "--prewarm-s", "0.05"],
                     {"TIP_BENCH_SHARE_GPU": "1", "TIP_BENCH_BACKEND": "gloo"})
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -104,7 +104,7 @@ def test_plain_bench_command_spawns_its_own_ranks():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--plan", "fusedh",
-           "--rnn-cluster", "1", "--no-cpu-baseline", "--no-extra", "--prewarm-s", "0.05"]
+           "--rnn-cluster", "1", "--full", "--no-cpu-baseline", "--no-extra", "--prewarm-s", "0.05"]
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -115,18 +115,18 @@ def test_plain_bench_command_spawns_its_own_ranks():
 
 
 def test_plain_bench_command_gpus_8_carries_the_whole_north_star_table():
-    """The driver's 8-GPU invocation, `python bench.py --gpus 8` (no launcher, default steps), rehearsed with eight ranks on the one GPU
-    this box has (TIP_BENCH_SHARE_GPU=1, gloo, a plan without cooperating kernels): the line says n_gpus == world_size == 8 and its
-    scaling table has every row of north_star's table — batch 1 per GPU, 256 windows in total (strong), 8192 streams in total (BASELINE
-    configs[3]) and the scaled model at 4096 windows in total (configs[4], with its own 609-MB broadcast) — finite, and every rank's
-    outputs for the probe windows identical; the whole run inside the wall-time bound (5 minutes; eight ranks SHARING one GPU are
-    slower than eight GPUs)."""
+    """The driver's 8-GPU invocation, `python bench.py --gpus 8 --full` (no launcher, default steps), rehearsed with eight ranks on
+    the one GPU this box has (TIP_BENCH_SHARE_GPU=1, gloo, a plan without cooperating kernels): the line says n_gpus == world_size
+    == 8 and its scaling table has every row of north_star's table — batch 1 per GPU, 256 windows in total (strong), 8192 streams
+    in total (BASELINE configs[3]) and the scaled model at 4096 windows in total (configs[4], with its own 609-MB broadcast) —
+    finite, and every rank's outputs for the probe windows identical; the whole run inside the wall-time bound (5 minutes; eight
+    ranks SHARING one GPU are slower than eight GPUs)."""
     import math
     import time
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", TIP_BENCH_SHARE_GPU="1", TIP_BENCH_BACKEND="gloo")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--plan", "fusedh", "--rnn-cluster", "1"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--plan", "fusedh", "--rnn-cluster", "1", "--full"]
     t0 = time.time()
     res = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900, env=env, cwd=ROOT)
     wall = time.time() - t0

@@ -14,7 +14,7 @@ export TMPDIR=/tmp
 BENCH="python $PWD/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-extra"
 
 # 1. the default bench line (with cpu_baseline) and the same command under rocprofv3 --kernel-trace --stats
-timeout 600 python bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+timeout 600 python bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 for cfg in "256:" "1:--batch 1" "1024:--batch 1024"; do
     tag=${cfg%%:*}; extra=${cfg#*:}
     d=/tmp/prof_$tag; rm -rf $d

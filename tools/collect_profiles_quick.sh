@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp
 [ -f transformer-inertial-poser_amd/csrc/libtip_hip_measure.so ] || make -C transformer-inertial-poser_amd/csrc -j8 measure > /dev/null
 BENCH="python $PWD/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-extra"
-timeout 900 python bench.py > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
+timeout 900 python bench.py --full > "$OUT/bench_n1.json" 2> "$OUT/bench_n1.err"
 for cfg in "256:" "1:--batch 1"; do
     tag=${cfg%%:*}; extra=${cfg#*:}
     d=/tmp/prof_$tag; rm -rf $d
