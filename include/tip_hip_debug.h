@@ -28,7 +28,8 @@ extern "C" {
 TIP_API int tip_debug_read_fh_wg(unsigned long long* out, int n);      /* hybrid encoder: per-workgroup start / end stamps (tools/fh_trace.py) */
 TIP_API int tip_debug_read_fh_trace(unsigned long long* out, int n);   /* hybrid encoder: phase stamps of workgroup 0 */
 TIP_API int tip_debug_read_bwd_trace(unsigned long long* out, int n);  /* fused backward kernels: phase stamps (tools/bwd_trace.py) */
-TIP_API int tip_debug_pgemm_launches(unsigned long long* out);         /* panel-GEMM launches since load (tests: the scaled widths take it) */
+TIP_API int tip_debug_pgemm_launches(unsigned long long* out);         /* panel-GEMM launches since load, inference (pgemm_kernel) and
+                                                                          training step (pgemm_tg_kernel) alike (tests: the scaled widths take it) */
 TIP_API int tip_debug_read_f2s_cross_xcd(unsigned* out);               /* pair-split plan: pairs whose halves sat on different XCDs */
 TIP_API int tip_debug_read_f2_trace(unsigned long long* out, int n);   /* two-window encoder phase stamps (tools/f2_trace.py) */
 TIP_API int tip_debug_read_flow_trace(unsigned long long* out, int n);  /* few-stream dataflow kernel: (entry, inputs ready, stored, published) stamps per stage (tools/flow_trace.py) */

@@ -32,13 +32,16 @@ def drop_key(seed: int, site: int) -> np.uint32:
     return np.uint32(z >> np.uint64(32))
 
 
-def drop_scale(seed: int, site: int, n: int, p: float) -> np.ndarray:
+def drop_scale(seed: int, site: int, n: int, p: float, idx=None) -> np.ndarray:
     """keep/(1-p) factor of the n elements of dropout site `site` (include/tip_hip.h, tip_train_forward):
-    keep(idx) = lowbias32((idx mod 2^32) * 0x9E3779B1 + key(seed, site)) >= floor(p * 2^32)."""
+    keep(idx) = lowbias32((idx mod 2^32) * 0x9E3779B1 + key(seed, site)) >= floor(p * 2^32).
+    idx: optional element indices (int64 array of n); default 0 .. n-1."""
     if p <= 0.0:
         return np.ones(n, dtype=np.float32)
+    idx = np.arange(n, dtype=np.uint64) if idx is None else np.asarray(idx, dtype=np.int64).astype(np.uint64)
+    assert idx.size == n
     with np.errstate(over="ignore"):
-        z = np.arange(n, dtype=np.uint64).astype(np.uint32) * np.uint32(0x9E3779B1) + drop_key(seed, site)
+        z = idx.astype(np.uint32) * np.uint32(0x9E3779B1) + drop_key(seed, site)
         z ^= z >> np.uint32(16)
         z *= np.uint32(0x7FEB352D)
         z ^= z >> np.uint32(15)
@@ -51,19 +54,33 @@ def drop_scale(seed: int, site: int, n: int, p: float) -> np.ndarray:
 
 
 def forward(cfg: dict, params: "dict[str, torch.Tensor]", x_imu, x_s, keep_mask=None, keep_scale=1.0, p_drop=0.0, seed=0,
-            dtype=torch.float64, relu_gates=None):
-    """y [B,T,size_s] with autograd attached to `params` (fp64 leaf tensors).  x_imu/x_s: numpy fp32.
+            dtype=torch.float64, relu_gates=None, window_ids=None):
+    """y [B,T,size_s] with autograd attached to `params` (fp64 leaf tensors).  x_imu/x_s: numpy fp32, or torch tensors of `dtype`
+    (leaves that may require grad: gradients w.r.t. the inputs; d x_s is zero where x_s is NaN, as nan_to_num's derivative).
 
     relu_gates: optional list of L boolean arrays [B,T,F].  ReLU makes the model piecewise linear; a hidden unit whose
     pre-activation is within fp32 rounding of zero may be open in one implementation and closed in another, and either
     choice is a valid (sub)gradient.  When the gates of the implementation under test are passed, the oracle
-    differentiates the SAME linear piece, so the comparison is not polluted by such flips."""
+    differentiates the SAME linear piece, so the comparison is not polluted by such flips.
+
+    window_ids: optional positions (int array of B) of the given windows in a larger batch.  The encoder dropout masks are then
+    those the kernels draw for these windows in that batch: the hash of the FULL-batch element index, per site
+    ((b * per-window count) + offset inside the window); only these windows' indices are hashed."""
     D, H, L = cfg["tf_in_dim"], cfg["n_heads"], cfg["tf_layers"]
     F_, R = cfg["tf_hid_size"], cfg["rnn_hid_size"]
     dh = D // H
-    xi = torch.tensor(np.asarray(x_imu), dtype=dtype)
-    s = torch.tensor(np.nan_to_num(np.asarray(x_s), nan=0.0), dtype=dtype)           # :65
+    if isinstance(x_imu, torch.Tensor):
+        xi = x_imu
+    else:
+        xi = torch.tensor(np.asarray(x_imu), dtype=dtype)
+    if isinstance(x_s, torch.Tensor):
+        s = torch.nan_to_num(x_s, nan=0.0)                                             # :65
+    else:
+        s = torch.tensor(np.nan_to_num(np.asarray(x_s), nan=0.0), dtype=dtype)       # :65
     B, T = xi.shape[0], xi.shape[1]
+    if window_ids is not None:
+        window_ids = np.asarray(window_ids, dtype=np.int64)
+        assert window_ids.shape == (B,)
     M = B * T
     s[..., 18 * 6:18 * 6 + 3] = 0.0                                                    # :75
     if keep_mask is not None:
@@ -74,7 +91,11 @@ def forward(cfg: dict, params: "dict[str, torch.Tensor]", x_imu, x_s, keep_mask=
 
     def site(l, k, shape):
         n = int(np.prod(shape))
-        return torch.tensor(drop_scale(seed, 4 * l + k, n, p_drop).reshape(shape), dtype=dtype)
+        idx = None
+        if window_ids is not None and p_drop > 0.0:
+            per = n // B                                                               # elements of one window (window-major layout)
+            idx = (window_ids[:, None] * per + np.arange(per, dtype=np.int64)[None, :]).reshape(-1)
+        return torch.tensor(drop_scale(seed, 4 * l + k, n, p_drop, idx).reshape(shape), dtype=dtype)
 
     for l in range(L):
         p = f"tf_encode.layers.{l}."
@@ -103,12 +124,22 @@ def forward(cfg: dict, params: "dict[str, torch.Tensor]", x_imu, x_s, keep_mask=
 
 
 def step(cfg, weights: "dict[str, np.ndarray]", x_imu, x_s, cot, keep_mask=None, keep_scale=1.0, p_drop=0.0, seed=0,
-         relu_gates=None):
-    """(y, grads) of loss = sum(y * cot): what `loss.backward()` leaves in .grad for that loss."""
-    params = {k: torch.tensor(np.asarray(v), dtype=torch.float64, requires_grad=True) for k, v in weights.items()}
-    y = forward(cfg, params, x_imu, x_s, keep_mask, keep_scale, p_drop, seed, relu_gates=relu_gates)
-    (y * torch.tensor(np.asarray(cot), dtype=torch.float64)).sum().backward()
-    return y.detach().numpy(), {k: v.grad.numpy() for k, v in params.items()}
+         relu_gates=None, window_ids=None, input_grads=False, dtype=torch.float64):
+    """(y, grads) of loss = sum(y * cot): what `loss.backward()` leaves in .grad for that loss.
+    input_grads: also return (d x_imu, d x_s) as a third element.  window_ids: see forward.  dtype: float32 gives the
+    reference's own fp32 rounding noise at a shape (what a tolerance above the fp64 default has to be justified by)."""
+    params = {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=True) for k, v in weights.items()}
+    xi, xs = x_imu, x_s
+    if input_grads:
+        xi = torch.tensor(np.asarray(x_imu), dtype=dtype, requires_grad=True)
+        xs = torch.tensor(np.asarray(x_s), dtype=dtype, requires_grad=True)
+    y = forward(cfg, params, xi, xs, keep_mask, keep_scale, p_drop, seed, dtype=dtype, relu_gates=relu_gates,
+                window_ids=window_ids)
+    (y * torch.tensor(np.asarray(cot), dtype=dtype)).sum().backward()
+    grads = {k: v.grad.numpy() for k, v in params.items()}
+    if input_grads:
+        return y.detach().numpy(), grads, (xi.grad.numpy(), xs.grad.numpy())
+    return y.detach().numpy(), grads
 
 
 def digest(name: str, g: np.ndarray) -> np.ndarray:

@@ -25,19 +25,19 @@ LOOP = """
     from simple_transformer_with_state import TF_RNN_Past_State
     from training_data_loader import TrainSubDataset
     from learning_utils import set_seed, loss_q_only_2axis, loss_constr_multi, loss_jerk
-    # ---- argparse defaults of :22-75 that the body reads, with --cuda --with_acc_sum --optim AdamW ------------------
+    # ---- argparse defaults of :22-75 that the body reads, with --cuda --optim AdamW (--with_acc_sum, --n_heads: per test) -
     class args: cuda = True; double = %(double)s; clip = 5.0; optim = "AdamW"; weight_decay = 1e-5; lr = 4e-4; seed = 1111
-    batch_size, seq_length, n_sbps, with_acc_sum, d_tag, noise_input_hist = 16, 40, 5, True, "t", 0.1
+    batch_size, seq_length, n_sbps, with_acc_sum, d_tag, noise_input_hist = 16, 40, 5, %(with_acc_sum)s, "t", 0.1
     if args.double:
         torch.set_default_dtype(torch.float64)                              # :84-85
     set_seed(args.seed)                                                      # :87
     input_channels = 6 * (9 + 3)
     output_channels = 18 * 6 + 3 + (n_sbps * 4)
-    model = TF_RNN_Past_State(                                               # :97-106 (paper widths; --n_heads 16 as the released models)
+    model = TF_RNN_Past_State(                                               # :97-106 (paper widths; --n_heads 16 as the released models, or 8)
         input_channels, output_channels,
         rnn_hid_size=512,
         tf_hid_size=1024, tf_in_dim=256,
-        n_heads=16, tf_layers=4,
+        n_heads=%(n_heads)d, tf_layers=4,
         dropout=0.0, in_dropout=0.0,
         past_state_dropout=0.8,
         with_rnn=True,
@@ -110,9 +110,9 @@ LOOP = """
     """
 
 
-def _run(tmp, double):
+def _run(tmp, double, n_heads=16, with_acc_sum=True):
     write_combined_files(tmp)
-    out = run_dropin(LOOP % dict(double=double), tmp)
+    out = run_dropin(LOOP % dict(double=double, n_heads=n_heads, with_acc_sum=with_acc_sum), tmp)
     assert out.returncode == 0, out.stderr[-4000:]
     import json
     line = [l for l in out.stdout.splitlines() if l.startswith("RESULT ")][-1]
@@ -158,3 +158,20 @@ def test_train_loop_body_through_the_dropin_under_double(tmp_path):
     assert res["moved"] == res["n_params"] == 56
     assert "torch-op training composite" not in out.stderr
     _check_losses(tmp, res, 1e-9)
+
+
+@pytest.mark.parametrize("double", [False, True])
+def test_train_loop_body_at_train_model_defaults(tmp_path, double):
+    """The same loop with the model train_model.py builds at its argparse defaults (:50 --n_heads 8, :66 no --with_acc_sum: 72 IMU
+    columns from the loader) — the layer-by-layer training path, not the fused one (16 heads only)."""
+    tmp = str(tmp_path)
+    res, out = _run(tmp, double, n_heads=8, with_acc_sum=False)
+    assert res["dtype"] == ("torch.float64" if double else "torch.float32") and len(res["log"]) == 3
+    for rec in res["log"]:
+        assert rec["model_fn"].startswith("_HipTrainFunction"), rec
+        assert rec["loss_fn"].startswith("_Loss"), rec
+        assert np.isfinite(rec["norm"]) and rec["norm"] > 0
+    assert [rec["n"] for rec in res["log"]] == [16, 16, 5]
+    assert res["moved"] == res["n_params"] == 56
+    assert "torch-op training composite" not in out.stderr
+    _check_losses(tmp, res, 1e-9 if double else 2e-5)

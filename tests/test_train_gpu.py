@@ -22,9 +22,9 @@ REL = 1e-5   # per-tensor relative L2 error of fp32 MFMA gradients (reductions o
              # differentiating the same linear piece (ReLU gates taken from the run under test)
 
 
-def _train_model(cfg, seed, p_enc):
+def _train_model(cfg, seed, p_enc, p_state=0.0):
     assert torch.cuda.is_available()
-    m = make_model(cfg)
+    m = make_model(cfg, p_state=p_state)
     w = load_synth(m, cfg, seed)
     m = m.cuda().train()
     m.ENCODER_DROPOUT = p_enc
@@ -37,19 +37,26 @@ def _gates(m, cfg, B, T):
             for l in range(cfg["tf_layers"])]
 
 
-def _hip_step(m, x_imu, x_s, cot, seed=None):
-    """One model call + backward through the HIP path; returns (y, grads, seed used)."""
+def _hip_step(m, x_imu, x_s, cot, seed=None, input_grads=False):
+    """One model call + backward through the HIP path; returns (y, grads, extras) — extras["dx_imu"] / ["dx_s"]: the gradients
+    w.r.t. the inputs (tip_train_input_grads) when input_grads."""
     used = {}
     if seed is not None:
         m._draw_seeds = lambda: [seed, seed]          # (the module's seed source: two draws from torch's CPU generator)
     try:
         n0 = m.hip_forward_count()
         m.zero_grad(set_to_none=True)
-        y = m(torch.tensor(x_imu).cuda(), torch.tensor(x_s).cuda())
+        xi, xs = torch.tensor(x_imu).cuda(), torch.tensor(x_s).cuda()
+        if input_grads:
+            xi.requires_grad_(True)
+            xs.requires_grad_(True)
+        y = m(xi, xs)
         assert m.hip_forward_count() == n0 + 1, "the HIP training forward did not run"
         assert type(y.grad_fn).__name__.startswith("_HipTrainFunction"), type(y.grad_fn).__name__
         (y * torch.tensor(cot).cuda()).sum().backward()
         torch.cuda.synchronize()
+        if input_grads:
+            used["dx_imu"], used["dx_s"] = xi.grad.cpu().numpy(), xs.grad.cpu().numpy()
     finally:
         if seed is not None:
             del m._draw_seeds

@@ -327,6 +327,9 @@ bool pgemm_shape_ok(int M, int N, int K);   // N % 512 == 0, K % 128 == 0, M >= 
 // wfrag: W [N][K] in 16x16x4 B-fragment order [N/16][K/16][64][4], followed by >= 2 KiB of readable padding
 hipError_t launch_pgemm(const float* A, int lda, const float* wfrag, size_t wfrag_floats, const float* bias, const float* res, int ldres,
                         float* C, int ldc, int M, int N, int K, int flags, hipStream_t s);
+// one more panel-GEMM launch for tip_debug_pgemm_launches: launch_pgemm counts its own; the training step's pgemm_tg_kernel
+// launches (tip_train.hip lin_launch) call this
+void count_pgemm_launch();
 
 // ---- on-device packing (tip_pack.hip) ----
 hipError_t run_pack_ops(const std::vector<PackOp>& ops, float* img, hipStream_t s);

@@ -452,6 +452,7 @@ static hipError_t lin_launch(const TG& g, const float* wfrag, hipStream_t s) {
         if (e != hipSuccess) return e;
         attr_set = true;
     }
+    count_pgemm_launch();
     hipLaunchKernelGGL(pgemm_tg_kernel, dim3(g.nn / pg::COLS, (g.mm + pg::ROWS - 1) / pg::ROWS), dim3(pg::THREADS), pg::LDS_BYTES, s, g,
                        wfrag, (int)((long long)g.nn * g.kva * 4));
     return hipGetLastError();

@@ -82,6 +82,9 @@ PAPER = dict(input_size_imu=72, size_s=131, rnn_hid_size=512, tf_hid_size=1024, 
 # BASELINE.json configs[4]; H / R are not stated there, SURVEY.md section 8d assumes H=16, R=512.
 SCALED = dict(input_size_imu=72, size_s=131, rnn_hid_size=512, tf_hid_size=4096, tf_in_dim=1024,
               n_heads=16, tf_layers=12, with_rnn=True, with_acc_sum=True)
+# what the reference's training script builds at its argparse defaults (train_model.py:44-66, model at :95-107): --n_heads 8
+# (head width 32), --with_acc_sum off (72 + 131 input columns); its past-state dropout 0.8 and batch 128 are run-time settings
+TRAIN_DEFAULT = dict(PAPER, n_heads=8, with_acc_sum=False)
 # small config used by fast parity tests (exercises T=80, dh=32, non-paper widths)
 TINY = dict(input_size_imu=72, size_s=131, rnn_hid_size=192, tf_hid_size=320, tf_in_dim=128,
             n_heads=4, tf_layers=2, with_rnn=True, with_acc_sum=True)
