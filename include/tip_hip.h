@@ -29,7 +29,8 @@ extern "C" {
                              removed; TIP_OPT_FUSE_HEAD reserved
                              4: plans 5 / 7 / 8 (pair-split, split-fp16) and TIP_OPT_PACK_SPLIT16 retired (and the split-fp16 trace hook of tip_hip_debug.h with them)
                              5: exact streaming reuse — tip_reuse_cache_bytes, tip_reuse_reset, tip_forward_reuse, tip_stream_frame_counter_offset,
-                                tip_stream_ingest_newest */
+                                tip_stream_ingest_newest; later, backward compatible: tip_forward_rows and the staggered streaming entry points
+                                (tip_stream_attach, tip_stream_detach, tip_stream_ingest_staggered, tip_stream_consume_staggered) */
 
 /* The library is built with -fvisibility=hidden: the functions declared here (and the measurement hooks of
  * tip_hip_debug.h) are its whole dynamic symbol table (tests/test_host_cpu.py compares `nm -D` with the two headers). */
@@ -183,6 +184,17 @@ TIP_API int tip_max_batch(const tip_handle* h, int T, int fp64, int* max_batch);
 TIP_API int tip_forward(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, int flags,
                 const float* keep_mask, float keep_scale, void* workspace, size_t workspace_bytes,
                 tip_stream_t stream);
+/* One output row per window, chosen per window: y [B,size_s], y[b] = row rows[b] of window b, rows a DEVICE int [B] read once per
+ * window.  Bit-identical to tip_forward(...)[b, rows[b]] on the same plan (and with rows[b] == T-1 everywhere to
+ * TIP_FWD_LAST_ROW_ONLY): plan choice, chunking limit (tip_max_batch), keep mask, CU-masked streams, a demoted handle and HIP-graph
+ * capture behave as in tip_forward; only the output projection's row addressing differs (flags as tip_forward's; the last-row flag
+ * is implied).  rows[b] outside [0, T) gives an all-NaN row ("no value"); nothing outside the window is read for it.
+ * Finite padding: attention is causal and the recurrence runs forward, so row r of a window depends on rows 0 .. r only — but only
+ * while the later rows are FINITE.  The diagonal attention tile multiplies masked probabilities (exact 0) with the V rows of later
+ * keys, and 0 * NaN = NaN: a NaN or Inf in a later row spreads into earlier ones.  Pad a short window with zeros (the staggered ingest
+ * below does). */
+TIP_API int tip_forward_rows(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, const int* rows, int flags,
+                     const float* keep_mask, float keep_scale, void* workspace, size_t workspace_bytes, tip_stream_t stream);
 
 /* The forward WITH the training step's encoder dropout and WITHOUT its activation stash: what a `.train()`-mode module computes when
  * nobody differentiates it — the unedited reference runner (offline_testing_simple.py:98 never calls .eval();
@@ -272,6 +284,34 @@ TIP_API int tip_stream_consume(void* state, const float* y_last, int n_streams, 
  * takes every older row from its ring, and at >= 1024 streams gathering the 35-KB windows is most of the ingest's time. */
 TIP_API int tip_stream_ingest_newest(void* state, const float* raw_imu, int n_streams, int frame_idx, float* x_imu, float* x_s,
                              tip_stream_t stream);
+
+/* ---- staggered streams: every slot of `state` starts, warms up and stops on its own (a server's connect / disconnect / restart),
+ *      without touching the other slots.  Each slot keeps its own frame counter f_i (in `state`; no host frame index anywhere) and a
+ *      flag, attached or detached; detached is the flag's zero value, so after tip_stream_reset every slot is detached.  A NEW state
+ *      buffer goes through tip_stream_reset once before its first staggered call: freshly allocated memory holds garbage flags.
+ *      Windows sit in fixed 40-row slots, x_imu [n,40,90] / x_s [n,40,131]; per frame, on one stream:
+ *          tip_stream_ingest_staggered(state, raw_imu[n,72], n, x_imu, x_s, rows[n], stream);
+ *              attached slot i: f_i advances, T_i = tip_stream_window_len(f_i); rows 0 .. T_i-1 of its window are what
+ *              tip_stream_ingest writes for frame f_i (bit for bit), rows T_i .. 39 are zero, rows[i] = T_i - 1 (-1 while priming);
+ *              detached slot: zero window, rows[i] = -1, state untouched
+ *          tip_forward_rows(h, x_imu, x_s, y_last[n,131], n, 40, rows, ...);      (NaN rows where rows[i] = -1)
+ *          tip_stream_consume_staggered(state, y_last, rows, n, s_rest[n,111], c_t[n,20], stream);
+ *              slot i with rows[i] >= 0 consumes y_last[i] as call f_i - 5; the others are skipped (state and output rows untouched)
+ *      The three calls take no frame index, so they can be captured once (HIP graph) and replayed from the first frame on;
+ *      tip_stream_attach / tip_stream_detach run between replays on the same stream.  slots / s_init are DEVICE arrays; slot indices
+ *      outside [0, n) are ignored (the host rejects them, and duplicates, before the call).
+ *      tip_stream_attach: the listed slots are reset as tip_stream_reset does (history row 0 from s_init row j for slots[j]) and
+ *      marked attached: their next staggered ingest is their frame 0.  tip_stream_detach marks slots detached.
+ *      Cost: every slot, warming up, priming or detached, occupies a T = 40 window in the forward — a freshly started staggered
+ *      engine pays the steady-state price from its first frame on, where the lock-step entry points run shorter windows.  The
+ *      lock-step entry points ignore the flag. */
+TIP_API int tip_stream_attach(void* state, int n_streams, const int* slots, const float* s_init /* [count,114] */, int count,
+                      tip_stream_t stream);
+TIP_API int tip_stream_detach(void* state, int n_streams, const int* slots, int count, tip_stream_t stream);
+TIP_API int tip_stream_ingest_staggered(void* state, const float* raw_imu, int n_streams, float* x_imu, float* x_s, int* rows,
+                                tip_stream_t stream);
+TIP_API int tip_stream_consume_staggered(void* state, const float* y_last, const int* rows, int n_streams, float* s_rest, float* c_t,
+                                 tip_stream_t stream);
 
 /* ---- exact streaming reuse: tip_forward for lock-stepped streams whose windows slide by one frame per call.
  *      In the runner a frame's model inputs never change once recorded (real_time_runner_minimal.py:74,85,137: raw_imu_buffer,

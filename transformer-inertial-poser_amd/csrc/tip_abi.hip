@@ -689,14 +689,23 @@ struct ReuseCtx {
     const int* frame_ctr;
     int frame_idx;
 };
+// rows (tip_forward_rows; null: tip_forward): one output row per window, row rows[b] of window b — only the output projection's row
+// addressing differs (TIP_FWD_LAST_ROW_ONLY is set with it, so everything that depends on the output's shape takes the last-row form)
 static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, int flags,
                         const float* keep_mask, float keep_scale, void* workspace, size_t workspace_bytes,
-                        tip_stream_t stream, const ReuseCtx* reuse);
+                        tip_stream_t stream, const ReuseCtx* reuse, const int* rows = nullptr);
 
 int tip_forward(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, int flags,
                 const float* keep_mask, float keep_scale, void* workspace, size_t workspace_bytes,
                 tip_stream_t stream) {
     return forward_impl(h, x_imu, x_s, y, B, T, flags, keep_mask, keep_scale, workspace, workspace_bytes, stream, nullptr);
+}
+
+int tip_forward_rows(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, const int* rows, int flags,
+                     const float* keep_mask, float keep_scale, void* workspace, size_t workspace_bytes, tip_stream_t stream) {
+    if (!rows && B > 0) return TIP_ERR_INVALID_ARG;
+    return forward_impl(h, x_imu, x_s, y, B, T, flags | TIP_FWD_LAST_ROW_ONLY, keep_mask, keep_scale, workspace, workspace_bytes, stream,
+                        nullptr, rows);
 }
 
 int tip_reuse_cache_bytes(const tip_handle* h, int n_streams, size_t* bytes) {
@@ -727,7 +736,7 @@ int tip_forward_reuse(tip_handle* h, const float* x_imu, const float* x_s, float
 
 static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, int flags,
                         const float* keep_mask, float keep_scale, void* workspace, size_t workspace_bytes,
-                        tip_stream_t stream, const ReuseCtx* reuse) {
+                        tip_stream_t stream, const ReuseCtx* reuse, const int* rows) {
     if (!h || !x_imu || !x_s || !y || B < 0 || T < 1) return TIP_ERR_INVALID_ARG;
     // (cfg.t_max is a sizing hint, not a limit: the reference builds its causal mask for any window length, :56-58,85; what
     // bounds B * T here are the 32-bit byte offsets of the buffer descriptors)
@@ -825,15 +834,16 @@ static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, flo
                 {
                     StageScope sc(h, s, "out_linear");
                     const bool last_only = (flags & TIP_FWD_LAST_ROW_ONLY) != 0;
-                    const float* hA = last_only ? hall + (size_t)(T - 1) * d.R : hall;
-                    const long long hlda = last_only ? (long long)T * d.R : d.R;
+                    const float* hA = last_only && !rows ? hall + (size_t)(T - 1) * d.R : hall;
+                    const long long hlda = last_only && !rows ? (long long)T * d.R : d.R;
                     const int hM = last_only ? B : B * T;
                     static const bool ksplit = !(tip_env("TIP_HEAD") && tip_env("TIP_HEAD")[0] == 'o');   // TIP_HEAD=old: measurement
                     e = hipErrorInvalidValue;
                     if (ksplit && T % 40 == 0)
-                        e = launch_head_ksplit(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, d.R, last_only, cus, s);
+                        e = launch_head_ksplit(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, d.R, last_only, cus, s,
+                                               rows, T);
                     if (e == hipErrorInvalidValue)
-                        e = launch_head_gemm(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, d.R, s);
+                        e = launch_head_gemm(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, d.R, s, rows, T);
                     if (e != hipSuccess) return fail_hip(h, e, "out_linear");
                 }
                 h->forward_count++;
@@ -844,10 +854,10 @@ static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, flo
                 const size_t row_i = (size_t)T * d.n_imu_total, row_s = (size_t)T * d.S;
                 const size_t row_y = (flags & TIP_FWD_LAST_ROW_ONLY) ? (size_t)d.S : row_s;
                 const uint64_t count0 = h->forward_count;
-                int st = tip_forward(h, x_imu, x_s, y, bm, T, flags, keep_mask, keep_scale, workspace, workspace_bytes, stream);
+                int st = forward_impl(h, x_imu, x_s, y, bm, T, flags, keep_mask, keep_scale, workspace, workspace_bytes, stream, nullptr, rows);
                 if (st != TIP_OK) return st;
-                st = tip_forward(h, x_imu + bm * row_i, x_s + bm * row_s, y + bm * row_y, r, T, flags, keep_mask ? keep_mask + bm * row_s : nullptr,
-                                 keep_scale, workspace, workspace_bytes, stream);
+                st = forward_impl(h, x_imu + bm * row_i, x_s + bm * row_s, y + bm * row_y, r, T, flags, keep_mask ? keep_mask + bm * row_s : nullptr,
+                                  keep_scale, workspace, workspace_bytes, stream, nullptr, rows ? rows + bm : nullptr);
                 if (st != TIP_OK) return st;
                 h->forward_count = count0 + 1;   // one forward, two launch sequences
                 return TIP_OK;
@@ -930,8 +940,9 @@ static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, flo
     auto arm_hall = [&]() { return rnn_uses_sentinel(d, B, T, rnn_cluster); };
     if (plan == TIP_PLAN_LATENCY) {
         StageScope sc(h, s, "latency_chain");
-        const LatencyHead lh{P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, d.S, (flags & TIP_FWD_LAST_ROW_ONLY) != 0, h->flow_epoch, &head_done,
-                             reinterpret_cast<unsigned long long*>(W0 + ws.flow)};
+        LatencyHead lh{P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, d.S, (flags & TIP_FWD_LAST_ROW_ONLY) != 0, h->flow_epoch, &head_done,
+                       reinterpret_cast<unsigned long long*>(W0 + ws.flow)};
+        lh.rows = rows;
         TIP_TRY(launch_latency_plan(d, P + L.fused_off, P + L.whh_frag_off, x_imu, x_s, mask, keep_scale, W0 + ws.lat, hall,
                                     B, T, cus, gd, s, nullptr, cus == h->num_cus && !h->no_flow ? &lh : nullptr), "latency_chain");
         rnn_done = true;
@@ -1027,21 +1038,22 @@ static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, flo
     if (!head_done) {
         StageScope sc(h, s, "out_linear");
         const int Kh = d.with_rnn ? d.R : d.D;
-        // rows the projection runs on: all M, or row T-1 of every window (real_time_runner_minimal.py:150)
-        const float* hA = last_only ? head_in + (size_t)(T - 1) * head_ld : head_in;
-        const long long hlda = last_only ? (long long)T * head_ld : head_ld;
+        // rows the projection runs on: all M, or row T-1 of every window (real_time_runner_minimal.py:150), or row rows[b] of window b
+        // (tip_forward_rows: A is then the first row, lda the row stride)
+        const float* hA = last_only && !rows ? head_in + (size_t)(T - 1) * head_ld : head_in;
+        const long long hlda = last_only && !rows ? (long long)T * head_ld : head_ld;
         const int hM = last_only ? B : M;
         if (plan == TIP_PLAN_LATENCY) {
-            TIP_TRY(launch_latency_head(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, s), "out_linear");
+            TIP_TRY(launch_latency_head(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, s, rows, T), "out_linear");
         } else {
             // window lengths that are multiples of 40 (the paper's and the scaled configuration's): the register-resident
             // kernel for both forms of the output (bit-identical last rows); everything else: head_gemm_kernel for both
             static const bool ksplit = !(tip_env("TIP_HEAD") && tip_env("TIP_HEAD")[0] == 'o');   // TIP_HEAD=old: measurement
             hipError_t he = hipErrorInvalidValue;
             if (ksplit && T % 40 == 0)
-                he = launch_head_ksplit(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, Kh, last_only, cus, s);
+                he = launch_head_ksplit(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, Kh, last_only, cus, s, rows, T);
             if (he == hipErrorInvalidValue)
-                he = launch_head_gemm(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, Kh, s);
+                he = launch_head_gemm(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, Kh, s, rows, T);
             TIP_TRY(he, "out_linear");
         }
     }

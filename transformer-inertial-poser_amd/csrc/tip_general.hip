@@ -203,7 +203,8 @@ hipError_t launch_gemm(const float* A, int lda, const float* W, int Kpad, const 
 template <int NBO>   // 16-column blocks per workgroup (9 = all of N = 131; 1 when M is small and grid.y walks the blocks)
 __global__ __launch_bounds__(256) void head_gemm_kernel(const float* __restrict__ A, long long lda,
                                                         const float* __restrict__ wfrag, const float* __restrict__ bias,
-                                                        float* __restrict__ Y, int ldy, int M, int N, int K) {
+                                                        float* __restrict__ Y, int ldy, int M, int N, int K,
+                                                        const int* __restrict__ rows, int rows_T) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l15 = lane & 15, lg = lane >> 4;
@@ -217,7 +218,12 @@ __global__ __launch_bounds__(256) void head_gemm_kernel(const float* __restrict_
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, lane * 16, ((nbase + n) * KB + kb) * 1024, 0));
     };
     const int arow = row0 + l15 < M ? row0 + l15 : M - 1;   // clamp: padded rows are computed but never stored
-    const float* ap = A + (size_t)arow * lda + lg * 4;
+    size_t arow_a = (size_t)arow;
+    if (rows) {   // tip_forward_rows: row rows[m] of window m (an index outside [0, T) reads the window's row 0 and stores NaN)
+        const int r = rows[arow];
+        arow_a = (size_t)arow * rows_T + ((unsigned)r < (unsigned)rows_T ? r : 0);
+    }
+    const float* ap = A + arow_a * lda + lg * 4;
     f32x4 acc[NBO];
 #pragma unroll
     for (int n = 0; n < NBO; ++n) acc[n] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -300,30 +306,34 @@ __global__ __launch_bounds__(256) void head_gemm_kernel(const float* __restrict_
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = row0 + lg * 4 + e;
-                if (row < M) Y[(size_t)row * ldy + col] = acc[n][e] + bv;
+                if (row < M) {
+                    float v = acc[n][e] + bv;
+                    if (rows && (unsigned)rows[row] >= (unsigned)rows_T) v = __builtin_nanf("");
+                    Y[(size_t)row * ldy + col] = v;
+                }
             }
         }
     }
 }
 
 hipError_t launch_head_gemm(const float* A, long long lda, const float* wfrag, const float* bias, float* Y, int ldy,
-                            int M, int N, int K, hipStream_t s) {
+                            int M, int N, int K, hipStream_t s, const int* rows, int rows_T) {
     if (M <= 0) return hipSuccess;
     const int nbo = (N + 15) / 16;
     const dim3 block(256);
     if ((M + 63) / 64 * 4 < 256) {
         // few rows: one column block per workgroup so the (rows x column blocks) grid still covers many CUs
-        hipLaunchKernelGGL(head_gemm_kernel<1>, dim3((M + 63) / 64, nbo), block, 0, s, A, lda, wfrag, bias, Y, ldy, M, N, K);
+        hipLaunchKernelGGL(head_gemm_kernel<1>, dim3((M + 63) / 64, nbo), block, 0, s, A, lda, wfrag, bias, Y, ldy, M, N, K, rows, rows_T);
         return hipGetLastError();
     }
     if (nbo % 3 == 0) {
         // 3 column blocks per wave: three times the waves (every SIMD gets work, 2+ waves each hide the fragment latency)
-        hipLaunchKernelGGL(head_gemm_kernel<3>, dim3((M + 63) / 64, nbo / 3), block, 0, s, A, lda, wfrag, bias, Y, ldy, M, N, K);
+        hipLaunchKernelGGL(head_gemm_kernel<3>, dim3((M + 63) / 64, nbo / 3), block, 0, s, A, lda, wfrag, bias, Y, ldy, M, N, K, rows, rows_T);
         return hipGetLastError();
     }
     const dim3 grid((M + 63) / 64);
 #define TIP_HEAD_CASE(NB) \
-    case NB: hipLaunchKernelGGL(head_gemm_kernel<NB>, grid, block, 0, s, A, lda, wfrag, bias, Y, ldy, M, N, K); break;
+    case NB: hipLaunchKernelGGL(head_gemm_kernel<NB>, grid, block, 0, s, A, lda, wfrag, bias, Y, ldy, M, N, K, rows, rows_T); break;
     switch (nbo) {
         TIP_HEAD_CASE(1) TIP_HEAD_CASE(2) TIP_HEAD_CASE(3) TIP_HEAD_CASE(4) TIP_HEAD_CASE(5) TIP_HEAD_CASE(6)
         TIP_HEAD_CASE(7) TIP_HEAD_CASE(8) TIP_HEAD_CASE(9) TIP_HEAD_CASE(10) TIP_HEAD_CASE(11) TIP_HEAD_CASE(12)

@@ -51,14 +51,45 @@ struct HdGridStride {
     __device__ __forceinline__ int stride() const { return gridDim.x; }
     __device__ __forceinline__ void after_weights() const {}
 };
-template <int MODE, bool TRACE, int AUX, class Ctl>
+// Row addressing.  HdDense: output row m is row m of A (every existing caller; the arithmetic is the original one).  HdGather
+// (tip_forward_rows): output row m is row rows[m] of window m, i.e. row m * T + rows[m] of A; a launch stores only the rows of its
+// tile kind (tkind 0: B-tile rows, t mod 40 < 32; 1: T-tile rows) — the kind MODE 0 gives that row, so the bits are the full
+// output's — and the T-kind launch stores NaN for an index outside [0, T) (its A loads fall outside the descriptor: zeros).
+struct HdDense {
+    static constexpr bool gather = false;
+};
+struct HdGather {
+    static constexpr bool gather = true;
+    const int* rows;
+    int T, M, tkind;
+    unsigned ld_b;   // bytes between two rows of A
+    __device__ __forceinline__ int row_of(int m) const { return m < M ? rows[m] : -1; }
+    __device__ __forceinline__ unsigned a_off(int m) const {
+        const int r = row_of(m);
+        return (unsigned)r < (unsigned)T ? (unsigned)(m * T + r) * ld_b : 0x80000000u;
+    }
+    // 0: not this launch's row, 1: store the value, 2: store NaN
+    __device__ __forceinline__ int code(int m) const {
+        const int r = row_of(m);
+        if ((unsigned)r >= (unsigned)T) return tkind ? 2 : 0;
+        return ((r % 40 >= 32) == (tkind != 0)) ? 1 : 0;
+    }
+    __device__ __forceinline__ void fix(int m, unsigned& off, float& v) const {
+        const int c = code(m);
+        if (c == 0) off = 0x80000000u;
+        if (c == 2) v = __builtin_nanf("");
+    }
+};
+
+// MODE 0: 40-row groups B(0) B(16) T(32) T(36); MODE 1: 16-row groups, one B tile; MODE 2: 4-row groups, one T tile
+template <int MODE, bool TRACE, int AUX, class Ctl, class Rows = HdDense>
 __device__ __forceinline__ void head_ksplit_body(const float* __restrict__ A, unsigned lda_b, unsigned a_bytes,
                                                  const float* __restrict__ wfrag, const float* __restrict__ bias, float* __restrict__ Y,
-                                                 int ldy, int M, int N, int ngroups, Ctl ctl) {
+                                                 int ldy, int M, int N, int ngroups, Ctl ctl, Rows rsel = Rows{}) {
     using namespace hd;
     extern __shared__ float part[];   // hd::LDS_BYTES of dynamic LDS (the caller's dynamic region, from its start)
     constexpr int NPH = MODE == 0 ? 4 : 1;
-    constexpr int RG = MODE == 0 ? 40 : 4;
+    constexpr int RG = MODE == 0 ? 40 : MODE == 1 ? 16 : 4;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int l15 = lane & 15, lg = lane >> 4;
@@ -70,12 +101,16 @@ __device__ __forceinline__ void head_ksplit_body(const float* __restrict__ A, un
     const unsigned aoff_b = (unsigned)l15 * lda_b + (unsigned)(wave * KBW * 64 + lg * 16);          // 16-row tile: row l15
     const unsigned aoff_t = (unsigned)(lane & 3) * lda_b + (unsigned)(wave * KBW * 64 + lg * 16);   // 4-row tile: row lane & 3
 
-    auto tile_is_tail = [](int p) { return MODE != 0 || p >= 2; };
+    auto tile_is_tail = [](int p) { return MODE == 2 || (MODE == 0 && p >= 2); };
     auto tile_row = [](int p) { return MODE == 0 ? (p < 2 ? 16 * p : 32 + 4 * (p - 2)) : 0; };
 
     hf4 acur[KBW], anext[KBW];
     auto load_a = [&](hf4 (&a)[KBW], int g, int p) {
-        const unsigned base = (unsigned)(g * RG + tile_row(p)) * lda_b + (tile_is_tail(p) ? aoff_t : aoff_b);
+        unsigned base;
+        if constexpr (Rows::gather)
+            base = rsel.a_off(g * RG + tile_row(p) + (tile_is_tail(p) ? (lane & 3) : l15)) + (unsigned)(wave * KBW * 64 + lg * 16);
+        else
+            base = (unsigned)(g * RG + tile_row(p)) * lda_b + (tile_is_tail(p) ? aoff_t : aoff_b);
 #pragma unroll
         for (int j = 0; j < KBW; ++j) a[j] = __builtin_bit_cast(hf4, __builtin_amdgcn_raw_buffer_load_b128(ars, (int)(base + j * 64), 0, AUX));
     };
@@ -127,12 +162,19 @@ __device__ __forceinline__ void head_ksplit_body(const float* __restrict__ A, un
     };
     auto red_store = [&](bool tail, const hf4& v, int row0, int n, float bv) {
         if (tail) {
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v[0] + bv), yrs, (int)red_addr(row0 + lg, n), 0, 0);
+            unsigned off = red_addr(row0 + lg, n);
+            float val = v[0] + bv;
+            if constexpr (Rows::gather) rsel.fix(row0 + lg, off, val);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, val), yrs, (int)off, 0, 0);
         } else {
             const unsigned off = red_addr(row0 + lg * 4, n);
 #pragma unroll
-            for (int e = 0; e < 4; ++e)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v[e] + bv), yrs, (int)(off + (unsigned)(e * ldy) * 4u), 0, 0);
+            for (int e = 0; e < 4; ++e) {
+                unsigned oe = off + (unsigned)(e * ldy) * 4u;
+                float val = v[e] + bv;
+                if constexpr (Rows::gather) rsel.fix(row0 + lg * 4 + e, oe, val);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, val), yrs, (int)oe, 0, 0);
+            }
         }
     };
 
@@ -144,8 +186,10 @@ __device__ __forceinline__ void head_ksplit_body(const float* __restrict__ A, un
             const hf4 a = src[0], b = src[1];
             const float v = ((a[0] + a[1]) + (a[2] + a[3])) + ((b[0] + b[1]) + (b[2] + b[3]));
             const int col = 128 + lane % 3;
-            const unsigned off = (unsigned)(row0 + lane / 3) * (unsigned)ldy * 4u + (col < N ? (unsigned)col * 4u : 0x80000000u);
-            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v + bias_c8), yrs, (int)off, 0, 0);
+            unsigned off = (unsigned)(row0 + lane / 3) * (unsigned)ldy * 4u + (col < N ? (unsigned)col * 4u : 0x80000000u);
+            float val = v + bias_c8;
+            if constexpr (Rows::gather) rsel.fix(row0 + lane / 3, off, val);
+            __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, val), yrs, (int)off, 0, 0);
         }
     };
     int buf = 0;
@@ -153,8 +197,8 @@ __device__ __forceinline__ void head_ksplit_body(const float* __restrict__ A, un
     // one tile: p = its index in the group (compile time), has_prev = a finished tile waits in part[buf ^ 1]
     auto phase = [&](auto PC, int gg, bool has_prev) {
         constexpr int p = decltype(PC)::value;
-        constexpr bool tail = MODE != 0 || p >= 2;
-        constexpr bool prev_tail = MODE != 0 || ((p + NPH - 1) % NPH) >= 2;
+        constexpr bool tail = MODE == 2 || (MODE == 0 && p >= 2);
+        constexpr bool prev_tail = MODE == 2 || (MODE == 0 && ((p + NPH - 1) % NPH) >= 2);
         const int row0 = gg * RG + tile_row(p);
         // the buffer index is kept opaque: with its parity known per unrolled tile the compiler hoists one LDS address register
         // per (buffer, access kind) out of the loop — a dozen VGPRs the kernel does not have (it spilled them)
@@ -239,7 +283,7 @@ __device__ __forceinline__ void head_ksplit_body(const float* __restrict__ A, un
     }
     // the last tile
     {
-        constexpr bool lt = MODE != 0 || NPH - 1 >= 2;
+        constexpr bool lt = MODE == 2 || (MODE == 0 && NPH - 1 >= 2);
         hf4 sv[4];
         half_load(lt, sv, buf ^ 1, wave, 0);
         hf4 q = half_sum(lt, sv);

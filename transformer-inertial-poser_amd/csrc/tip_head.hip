@@ -38,6 +38,21 @@ __global__ __launch_bounds__(hd::THREADS) void head_ksplit_kernel(const float* _
     head_ksplit_body<MODE, TRACE, 0>(A, lda_b, a_bytes, wfrag, bias, Y, ldy, M, N, ngroups, HdGridStride{});
 }
 
+// tip_forward_rows: one output row per window, row rows[m] of window m (HdGather).  MODE 1 (B-tile rows) first looks whether any
+// window of its groups wants a B-tile row and leaves at once when none does — a stream past its warm-up asks for row 39 only.
+template <int MODE>
+__global__ __launch_bounds__(hd::THREADS) void head_rows_kernel(const float* __restrict__ A, unsigned a_bytes,
+                                                                const float* __restrict__ wfrag, const float* __restrict__ bias,
+                                                                float* __restrict__ Y, int ldy, int M, int N, int ngroups, HdGather rsel) {
+    if (MODE == 1) {
+        int any = 0;
+        if (threadIdx.x < 16)
+            for (int g = blockIdx.x; g < ngroups; g += gridDim.x) any |= rsel.code(g * 16 + (int)threadIdx.x) == 1;
+        if (!__syncthreads_or(any)) return;
+    }
+    head_ksplit_body<MODE, false, 0>(A, rsel.ld_b, a_bytes, wfrag, bias, Y, ldy, M, N, ngroups, HdGridStride{}, rsel);
+}
+
 extern "C" int tip_debug_read_head_wg(unsigned long long* out, int n) {
     if (!out || n < 0 || n > 2048) return -1;
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(g_hd_wg), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -5;
@@ -52,9 +67,35 @@ extern "C" int tip_debug_read_head_trace(unsigned long long* out, int n) {
 // ignored for last_only (M = one row per window).  Returns hipErrorInvalidValue for shapes it does not serve (the caller then
 // keeps head_gemm_kernel).
 hipError_t launch_head_ksplit(const float* A, long long lda, const float* wfrag, const float* bias, float* Y, int ldy, int M, int N,
-                              int K, bool last_only, int num_cus, hipStream_t s) {
+                              int K, bool last_only, int num_cus, hipStream_t s, const int* rows, int rows_T) {
     if (M <= 0) return hipSuccess;
     if (K != 512 || N <= 128 || N > 144) return hipErrorInvalidValue;
+    if (rows) {
+        // A = the first row of window 0, lda = the row stride, M = windows: both tile kinds, each storing its own rows
+        if (rows_T < 1 || rows_T % 40 || lda * 4 > 0x7fffffffLL || ((long long)M * rows_T - 1) * lda + K > 0x1fffffffLL ||
+            (long long)M * ldy * 4 > 0x7fffffffLL)
+            return hipErrorInvalidValue;
+        static PerDeviceFlag rows_flag[2];
+        const unsigned a_bytes = (unsigned)((((long long)M * rows_T - 1) * lda + K) * 4);
+        const void* fns[2] = {reinterpret_cast<const void*>(head_rows_kernel<1>), reinterpret_cast<const void*>(head_rows_kernel<2>)};
+        for (int i = 0; i < 2; ++i) {
+            bool& done = rows_flag[i].cur();
+            if (!done) {
+                const hipError_t e2 = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, hd::LDS_BYTES);
+                if (e2 != hipSuccess) return e2;
+                done = true;
+            }
+        }
+        const HdGather g1{rows, rows_T, M, 0, (unsigned)(lda * 4)}, g2{rows, rows_T, M, 1, (unsigned)(lda * 4)};
+        const int ng1 = (M + 15) / 16, ng2 = (M + 3) / 4;
+        hipLaunchKernelGGL(head_rows_kernel<1>, dim3(std::min(ng1, num_cus)), dim3(hd::THREADS), hd::LDS_BYTES, s, A, a_bytes, wfrag,
+                           bias, Y, ldy, M, N, ng1, g1);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(head_rows_kernel<2>, dim3(std::min(ng2, num_cus)), dim3(hd::THREADS), hd::LDS_BYTES, s, A, a_bytes, wfrag,
+                           bias, Y, ldy, M, N, ng2, g2);
+        return hipGetLastError();
+    }
     if (lda * 4 > 0x7fffffffLL || ((long long)(M - 1) * lda + K) * 4 > 0xffffffffLL || (long long)M * ldy * 4 > 0x7fffffffLL)
         return hipErrorInvalidValue;
     const unsigned a_bytes = (unsigned)(((long long)(M - 1) * lda + K) * 4);

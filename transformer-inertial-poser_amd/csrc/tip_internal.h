@@ -421,14 +421,17 @@ hipError_t launch_fused_train_h(const Dims& d, const float* fused_w, const float
 // the fused encoder can do that for its own rows, otherwise launch_rnn memsets)
 bool rnn_uses_sentinel(const Dims& d, int B, int T, int cluster);
 // Y[M,N] = A[M,K(lda)] * Wfrag^T + bias with Wfrag in 16x16x4 B-fragment order [ceil(N/16)][K/16][64][4]
+// rows (tip_forward_rows; null: every row of A): output row m is row m * rows_T + rows[m] of A (lda = the row stride), NaN for an
+// index outside [0, rows_T); M = windows
 hipError_t launch_head_gemm(const float* A, long long lda, const float* wfrag, const float* bias, float* Y, int ldy,
-                            int M, int N, int K, hipStream_t s);
+                            int M, int N, int K, hipStream_t s, const int* rows = nullptr, int rows_T = 0);
 
 // the same product with the weight resident in registers (tip_head.hip): K = 512, 128 < N <= 144, window length a multiple of 40
 // (full output: M a multiple of 40; last_only: M = one row per window, bit-identical to row T-1 of the full output).
 // hipErrorInvalidValue = shape not served (nothing launched).
+// rows: as launch_head_gemm's (two launches, one per tile kind: every row keeps the bits the full output gives it; rows_T a multiple of 40)
 hipError_t launch_head_ksplit(const float* A, long long lda, const float* wfrag, const float* bias, float* Y, int ldy, int M, int N,
-                              int K, bool last_only, int num_cus, hipStream_t s);
+                              int K, bool last_only, int num_cus, hipStream_t s, const int* rows = nullptr, int rows_T = 0);
 
 // ---- latency plan (tip_latency.hip): one window spread over many CUs, for few concurrent streams ----
 bool latency_supported(const Dims& d, int B, int T);
@@ -453,6 +456,7 @@ struct LatencyHead {
     unsigned long long nonce;   // the handle's stamp base (tip_handle::flow_epoch)
     bool* done;
     unsigned long long* flags;  // the workspace's flag / launch-counter area (Workspace::flow; latency_flow_flag_floats() floats)
+    const int* rows = nullptr;  // tip_forward_rows: row rows[b] of window b (last_only set too: one output row per window)
 };
 size_t latency_flow_flag_floats();
 hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float* whh_frag, const float* x_imu,
@@ -461,7 +465,7 @@ hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float*
                                const LatencyHead* head = nullptr);
 
 hipError_t launch_latency_head(const float* A, long long lda, const float* wfrag, const float* bias, float* Y, int ldy,
-                               int M, int N, hipStream_t s);
+                               int M, int N, hipStream_t s, const int* rows = nullptr, int rows_T = 0);
 
 hipError_t read_spin_timeouts_general(unsigned* out);
 hipError_t read_spin_timeouts_latency(unsigned* out);

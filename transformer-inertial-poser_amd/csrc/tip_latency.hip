@@ -617,7 +617,8 @@ __global__ __launch_bounds__(NW * 64) void lat_res_gemm_kernel(LatResArgs a) {
 template <bool FLOW, typename WAIT>
 __device__ __forceinline__ void lat_head_body(const float* __restrict__ A, long long lda, const float* __restrict__ wfrag,
                                               const float* __restrict__ bias, float* __restrict__ Y, int ldy, int M, int N, int nb, int m0,
-                                              float* red, const Act& act, FlowCtx& fc, WAIT&& wait) {
+                                              float* red, const Act& act, FlowCtx& fc, WAIT&& wait, const int* rows = nullptr,
+                                              int rows_T = 0) {
     using namespace lz;
     constexpr int KBT = R / 16, KBW = KBT / 4;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -636,7 +637,12 @@ __device__ __forceinline__ void lat_head_body(const float* __restrict__ A, long 
 #pragma unroll
     for (int r = 0; r < RB; ++r) {
         const int row = m0 + r * 16 + l15;
-        const float* ap = A + (size_t)(row < M ? row : 0) * lda + kb0 * 16 + lg * 4;
+        size_t ra = (size_t)(row < M ? row : 0);
+        if (rows && row < M) {   // tip_forward_rows: row rows[m] of window m (outside [0, T): the window's row 0, stored as NaN)
+            const int rr = rows[row];
+            ra = ra * rows_T + ((unsigned)rr < (unsigned)rows_T ? rr : 0);
+        }
+        const float* ap = A + ra * lda + kb0 * 16 + lg * 4;
 #pragma unroll
         for (int k = 0; k < KBW; ++k)
             a[r][k] = row < M ? ld_act4<FLOW>(act, ap + k * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -659,24 +665,28 @@ __device__ __forceinline__ void lat_head_body(const float* __restrict__ A, long 
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const int row = m0 + wave * 16 + lg * 4 + e;
-                if (row < M) Y[(size_t)row * ldy + col] = FLOW ? poison_if(fc.poisoned, sres[e] + bv) : sres[e] + bv;
+                if (row < M) {
+                    float v = FLOW ? poison_if(fc.poisoned, sres[e] + bv) : sres[e] + bv;
+                    if (rows && (unsigned)rows[row] >= (unsigned)rows_T) v = __builtin_nanf("");
+                    Y[(size_t)row * ldy + col] = v;
+                }
             }
         }
     }
 }
 __global__ __launch_bounds__(256) void lat_head_kernel(const float* __restrict__ A, long long lda, const float* __restrict__ wfrag,
                                                        const float* __restrict__ bias, float* __restrict__ Y, int ldy, int M,
-                                                       int N) {
+                                                       int N, const int* __restrict__ rows, int rows_T) {
     __shared__ __attribute__((aligned(16))) float red[4 * 3 * 256];
     FlowCtx fc;
-    lat_head_body<false>(A, lda, wfrag, bias, Y, ldy, M, N, blockIdx.x, blockIdx.y * lz::RP, red, null_act(), fc, [] {});
+    lat_head_body<false>(A, lda, wfrag, bias, Y, ldy, M, N, blockIdx.x, blockIdx.y * lz::RP, red, null_act(), fc, [] {}, rows, rows_T);
 }
 
 hipError_t launch_latency_head(const float* A, long long lda, const float* wfrag, const float* bias, float* Y, int ldy,
-                               int M, int N, hipStream_t s) {
+                               int M, int N, hipStream_t s, const int* rows, int rows_T) {
     if (M <= 0) return hipSuccess;
     hipLaunchKernelGGL(lat_head_kernel, dim3((N + 15) / 16, (M + lz::RP - 1) / lz::RP), dim3(256), 0, s, A, lda, wfrag, bias, Y,
-                       ldy, M, N);
+                       ldy, M, N, rows, rows_T);
     return hipGetLastError();
 }
 
@@ -958,6 +968,7 @@ struct LatFlowArgs {
     u64 nonce;                             // per-handle constant mixed into the stamps
     const float* whh_frag; float* hall;    // recurrence role
     const float* out_frag; const float* out_bias; float* y; int ldy, N, last_only;   // output projection role
+    const int* rows;                       // tip_forward_rows (null: last_only decides): row rows[win] of each window
     int B, T, NI, S, L;
     unsigned mkey, mthresh;
     LatDrop dr;
@@ -1035,10 +1046,10 @@ __global__ __launch_bounds__(256) void lat_flow_kernel(LatFlowArgs a) {
     if (stage == nenc + 1) {                              // output projection: every row of the window, or row T - 1 (real_time_runner_minimal.py:150)
         const float* hwin = a.hall + (size_t)win * T * R;
         const Act hact{__builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hwin), 0, T * R * 4, 0x00020000), hwin};
-        const float* hA = a.last_only ? hwin + (size_t)(T - 1) * R : hwin;
+        const float* hA = a.last_only && !a.rows ? hwin + (size_t)(T - 1) * R : hwin;
         float* yw = a.last_only ? a.y + (size_t)win * a.ldy : a.y + (size_t)win * T * a.ldy;
         lat_head_body<true>(hA, R, a.out_frag, a.out_bias, yw, a.ldy, a.last_only ? 1 : T, a.N, nb, 0, smem, hact, fc,
-                            [&] { flow_wait(fc, nenc, kFlowRnnMembers, &s_ok); FLOW_STAMP(1); });
+                            [&] { flow_wait(fc, nenc, kFlowRnnMembers, &s_ok); FLOW_STAMP(1); }, a.rows ? a.rows + win : nullptr, T);
         FLOW_STAMP(2);
         // (the outputs leave the launch: no flag; the designated workgroup advances the launch counter for the next launch)
         if (nb == nhead - 1 && threadIdx.x == 0) __hip_atomic_store(counter, launch + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1152,6 +1163,7 @@ hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float*
         fa.nonce = head->nonce;
         fa.whh_frag = whh_frag; fa.hall = hall;
         fa.out_frag = head->wfrag; fa.out_bias = head->bias; fa.y = head->y; fa.ldy = head->ldy; fa.N = head->N; fa.last_only = head->last_only ? 1 : 0;
+        fa.rows = head->rows;
         fa.B = B; fa.T = T; fa.NI = d.n_imu_total; fa.S = d.S; fa.L = d.L;
         fa.mkey = td ? td->mkey : 0u; fa.mthresh = td && !keep_mask ? td->mthresh : 0u;
         fa.dr = LatDrop{};

@@ -15,7 +15,7 @@
 // root translation, which is not a model input.
 //
 // State per stream (floats, caller-owned device buffer): raw[11][72] | loc[40][72] | accs[40][18] | hist[40][131] |
-// outs[6][131] | last[54] | frame counter (int).  Frame / call counters live on the host (all streams advance in lock step); the
+// outs[6][131] | last[54] | frame counter (int) | attached flag (int; the staggered entry points only, 0 = detached).  Frame / call counters live on the host (all streams advance in lock step); the
 // ingest kernel also leaves the frame index in the state, so that a call with TIP_STREAM_FRAME_AUTO continues from it — kernel
 // arguments are frozen in a captured HIP graph, a counter in HBM is not.
 #include "tip_internal.h"
@@ -31,7 +31,8 @@ constexpr int HIST = ACCS + WIN * 18;         // 4392
 constexpr int OUTS = HIST + WIN * NS;         // 9632
 constexpr int LAST = OUTS + OUTN * NS;        // 10418
 constexpr int CTR = LAST + 54;                // 10472: frame index of the last ingest (int)
-constexpr int STRIDE = 10496;                 // CTR + 1 = 10473, padded to a multiple of 64
+constexpr int ATT = CTR + 1;                  // 10473: staggered slots: 1 = attached (int); the lock-step entry points ignore it
+constexpr int STRIDE = 10496;                 // ATT + 1 = 10474, padded to a multiple of 64
 }  // namespace sz
 
 // ---- scipy.spatial.transform.Rotation restated (fp32) -------------------------------------------------------
@@ -160,14 +161,29 @@ __device__ __forceinline__ void rotvec_to_6d(const float rv[3], float out[6]) {
     out[5] = 2.f * (yz + xw);     // m21
 }
 
+__host__ __device__ __forceinline__ int window_len(int frame_idx) {   // T of the model call issued for frame `frame_idx`; 0 while priming
+    if (frame_idx < 5) return 0;
+    const int t = frame_idx - 4;
+    return t < sz::WIN ? t : sz::WIN;
+}
+
 // ---- reset: history row 0 from s_init (:45, :78-85) ----------------------------------------------------------
-__global__ __launch_bounds__(64) void stream_reset_kernel(float* __restrict__ state, const float* __restrict__ s_init, int B) {
+// slots == nullptr: every stream b = blockIdx.x (tip_stream_reset: all detached).  Otherwise (tip_stream_attach) the block rebuilds
+// stream slots[blockIdx.x] from s_init row blockIdx.x and marks it attached, its next staggered ingest being its frame 0.
+__global__ __launch_bounds__(64) void stream_reset_kernel(float* __restrict__ state, const float* __restrict__ s_init, int B,
+                                                          const int* __restrict__ slots) {
     using namespace sz;
-    const int b = blockIdx.x, tid = threadIdx.x;
+    const int tid = threadIdx.x;
+    const int b = slots ? slots[blockIdx.x] : (int)blockIdx.x;
+    if (b < 0 || b >= B) return;
     float* S = state + (size_t)b * STRIDE;
     for (int i = tid; i < STRIDE; i += 64) S[i] = 0.f;
     __syncthreads();
-    const float* si = s_init + (size_t)b * 114;
+    if (slots && tid == 0) {
+        reinterpret_cast<int*>(S + CTR)[0] = -1;   // "last ingested frame": the next one is frame 0
+        reinterpret_cast<int*>(S + ATT)[0] = 1;
+    }
+    const float* si = s_init + (size_t)blockIdx.x * 114;
     if (tid < 18) {
         float rv[3] = {si[3 + tid * 3], si[4 + tid * 3], si[5 + tid * 3]}, o[6];
         rotvec_to_6d(rv, o);
@@ -176,18 +192,44 @@ __global__ __launch_bounds__(64) void stream_reset_kernel(float* __restrict__ st
     if (tid < 3) S[HIST + 108 + tid] = si[57 + tid];
 }
 
+// ---- detach: the listed slots stop taking part in the staggered calls (their state is kept until the next attach) -----------
+__global__ __launch_bounds__(64) void stream_detach_kernel(float* __restrict__ state, int B, const int* __restrict__ slots, int count) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= count) return;
+    const int b = slots[i];
+    if (b < 0 || b >= B) return;
+    reinterpret_cast<int*>(state + (size_t)b * sz::STRIDE + sz::ATT)[0] = 0;
+}
+
 // ---- ingest one raw frame per stream and emit the model inputs -----------------------------------------------
 // newest != 0 (tip_stream_ingest_newest): only row T - 1 of every window is written — what the exact-reuse forward reads
 // (tip_forward_reuse takes every older row from its ring).  At >= 1024 streams the window gather IS this kernel: 35 KB read and 35 KB
 // written per stream, 18 us at 1024 streams and 53 us at 4096 against 8-9 us for the smoothing chain.
+// rows_out != nullptr (tip_stream_ingest_staggered): every stream keeps its own frame counter and window length T_i, and its window
+// sits in a 40-row slot: rows 0 .. T_i - 1 as the lock-step ingest writes them for frame f_i, rows T_i .. 39 zero, rows_out[b] = T_i - 1
+// (-1 while priming).  A detached stream gets a zero window and -1, and its state is not touched.
 __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ state, const float* __restrict__ raw_in, int B,
-                                                            int f, float* __restrict__ x_imu, float* __restrict__ x_s, int T, int newest) {
+                                                            int f, float* __restrict__ x_imu, float* __restrict__ x_s, int T, int newest,
+                                                            int* __restrict__ rows_out) {
     using namespace sz;
     __shared__ float sm[NIMU], loc[NIMU];
     const int b = blockIdx.x, tid = threadIdx.x;
     float* S = state + (size_t)b * STRIDE;
     int* ctr = reinterpret_cast<int*>(S + CTR);
-    if (f < 0) {   // TIP_STREAM_FRAME_AUTO: the frame after the last one ingested (every thread reads before thread 0 writes)
+    int ldw = T;   // rows between two windows of x_imu / x_s
+    if (rows_out) {
+        const bool attached = reinterpret_cast<const int*>(S + ATT)[0] != 0;
+        f = attached ? *ctr + 1 : 0;
+        __syncthreads();   // every thread reads before thread 0 writes
+        T = attached ? window_len(f) : 0;
+        ldw = WIN;
+        float* xs0 = x_s + (size_t)b * WIN * NS;
+        float* xi0 = x_imu + (size_t)b * WIN * NX;
+        for (int i = T * NS + tid; i < WIN * NS; i += 256) xs0[i] = 0.f;
+        for (int i = T * NX + tid; i < WIN * NX; i += 256) xi0[i] = 0.f;
+        if (tid == 0) rows_out[b] = T - 1;
+        if (!attached) return;
+    } else if (f < 0) {   // TIP_STREAM_FRAME_AUTO: the frame after the last one ingested (every thread reads before thread 0 writes)
         f = *ctr + 1;
         __syncthreads();
     }
@@ -201,8 +243,8 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
     if (f >= 5) {
         // (compile-time trip counts, every load of a loop requested before its first store: 36 round trips in flight together)
         constexpr int XS_IT = (WIN * NS + 255) / 256, XI_IT = (WIN * NX + 255) / 256;
-        float* xs = x_s + (size_t)b * T * NS;
-        float* xi = x_imu + (size_t)b * T * NX;
+        float* xs = x_s + (size_t)b * ldw * NS;
+        float* xi = x_imu + (size_t)b * ldw * NX;
         if (newest) {
             if (tid < NS) xs[(T - 1) * NS + tid] = S[HIST + (k % WIN) * NS + tid];     // history entry k (:144)
         } else {
@@ -294,7 +336,7 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
     }
     __syncthreads();
     // this frame's row: to the state (next frames read it) and straight to the newest row of x_imu, both from LDS
-    float* xin = x_imu + (size_t)b * T * NX + (size_t)(T - 1) * NX;
+    float* xin = x_imu + (size_t)b * ldw * NX + (size_t)(T - 1) * NX;
     if (tid < NIMU) {
         S[LOC + (k % WIN) * NIMU + tid] = loc[tid];
         xin[tid] = loc[tid];
@@ -307,11 +349,15 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
 }
 
 // ---- consume the model's last row: filter, decode, pose assembly, history feedback ----------------------------
+// rows != nullptr (tip_stream_consume_staggered): a stream with rows[b] < 0 is skipped (state and output rows untouched); the others
+// consume their row as call f_b - 5 of their own counter
 __global__ __launch_bounds__(192) void stream_consume_kernel(float* __restrict__ state, const float* __restrict__ y_last, int B,
-                                                             int k, float* __restrict__ s_rest, float* __restrict__ c_out) {
+                                                             int k, float* __restrict__ s_rest, float* __restrict__ c_out,
+                                                             const int* __restrict__ rows) {
     using namespace sz;
     __shared__ float s[NS], aa[54], rootv[3];
     const int b = blockIdx.x, tid = threadIdx.x;
+    if (rows && rows[b] < 0) return;
     float* S = state + (size_t)b * STRIDE;
     const float coeff[OUTN] = {0.07776f, 0.1296f, 0.216f, 0.36f, 0.6f, 1.0f};   // 0.6^(5..0) (:57)
     const float csum = 0.07776f + 0.1296f + 0.216f + 0.36f + 0.6f + 1.0f;
@@ -408,7 +454,7 @@ int tip_stream_reset(void* state, const float* s_init, int n_streams, tip_stream
     if (!state || !s_init || n_streams < 0) return TIP_ERR_INVALID_ARG;
     if (n_streams == 0) return TIP_OK;
     hipLaunchKernelGGL(stream_reset_kernel, dim3(n_streams), dim3(64), 0, static_cast<hipStream_t>(stream),
-                       static_cast<float*>(state), s_init, n_streams);
+                       static_cast<float*>(state), s_init, n_streams, nullptr);
     return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 
@@ -419,9 +465,7 @@ int tip_stream_frame_counter_offset(size_t* bytes) {   // where stream 0's block
 }
 
 int tip_stream_window_len(int frame_idx) {   // T of the model call issued for frame `frame_idx`; 0 while priming
-    if (frame_idx < 5) return 0;
-    const int t = frame_idx - 4;
-    return t < sz::WIN ? t : sz::WIN;
+    return window_len(frame_idx);
 }
 
 static int stream_ingest(void* state, const float* raw_imu, int n_streams, int frame_idx, float* x_imu, float* x_s, tip_stream_t stream,
@@ -431,7 +475,7 @@ static int stream_ingest(void* state, const float* raw_imu, int n_streams, int f
     if (T > 0 && (!x_imu || !x_s)) return TIP_ERR_INVALID_ARG;
     if (n_streams == 0) return TIP_OK;
     hipLaunchKernelGGL(stream_ingest_kernel, dim3(n_streams), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<float*>(state), raw_imu, n_streams, frame_idx, x_imu, x_s, T, newest);
+                       static_cast<float*>(state), raw_imu, n_streams, frame_idx, x_imu, x_s, T, newest, nullptr);
     return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 
@@ -450,7 +494,41 @@ int tip_stream_consume(void* state, const float* y_last, int n_streams, int call
     if (!state || !y_last || !s_rest || !c_t || n_streams < 0 || call_idx < TIP_STREAM_FRAME_AUTO) return TIP_ERR_INVALID_ARG;
     if (n_streams == 0) return TIP_OK;
     hipLaunchKernelGGL(stream_consume_kernel, dim3(n_streams), dim3(192), 0, static_cast<hipStream_t>(stream),
-                       static_cast<float*>(state), y_last, n_streams, call_idx, s_rest, c_t);
+                       static_cast<float*>(state), y_last, n_streams, call_idx, s_rest, c_t, nullptr);
+    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+}
+
+int tip_stream_attach(void* state, int n_streams, const int* slots, const float* s_init, int count, tip_stream_t stream) {
+    if (!state || n_streams < 0 || count < 0 || (count > 0 && (!slots || !s_init))) return TIP_ERR_INVALID_ARG;
+    if (count == 0) return TIP_OK;
+    hipLaunchKernelGGL(stream_reset_kernel, dim3(count), dim3(64), 0, static_cast<hipStream_t>(stream), static_cast<float*>(state),
+                       s_init, n_streams, slots);
+    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+}
+
+int tip_stream_detach(void* state, int n_streams, const int* slots, int count, tip_stream_t stream) {
+    if (!state || n_streams < 0 || count < 0 || (count > 0 && !slots)) return TIP_ERR_INVALID_ARG;
+    if (count == 0) return TIP_OK;
+    hipLaunchKernelGGL(stream_detach_kernel, dim3((count + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       static_cast<float*>(state), n_streams, slots, count);
+    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+}
+
+int tip_stream_ingest_staggered(void* state, const float* raw_imu, int n_streams, float* x_imu, float* x_s, int* rows,
+                                tip_stream_t stream) {
+    if (!state || !raw_imu || !x_imu || !x_s || !rows || n_streams < 0) return TIP_ERR_INVALID_ARG;
+    if (n_streams == 0) return TIP_OK;
+    hipLaunchKernelGGL(stream_ingest_kernel, dim3(n_streams), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<float*>(state), raw_imu, n_streams, 0, x_imu, x_s, sz::WIN, 0, rows);
+    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+}
+
+int tip_stream_consume_staggered(void* state, const float* y_last, const int* rows, int n_streams, float* s_rest, float* c_t,
+                                 tip_stream_t stream) {
+    if (!state || !y_last || !rows || !s_rest || !c_t || n_streams < 0) return TIP_ERR_INVALID_ARG;
+    if (n_streams == 0) return TIP_OK;
+    hipLaunchKernelGGL(stream_consume_kernel, dim3(n_streams), dim3(192), 0, static_cast<hipStream_t>(stream),
+                       static_cast<float*>(state), y_last, n_streams, TIP_STREAM_FRAME_AUTO, s_rest, c_t, rows);
     return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 

@@ -38,6 +38,7 @@ EXPORTS = (
     "tip_pack_weights_device", "tip_attach_packed", "tip_workspace_bytes", "tip_max_batch", "tip_forward", "tip_forward_dropout", "tip_draw_keep_mask", "tip_forward_f64_bytes", "tip_forward_f64", "tip_forward_count", "tip_profile_read",
     "tip_spin_timeouts", "tip_check", "tip_stream_state_bytes", "tip_stream_reset", "tip_stream_window_len", "tip_stream_ingest", "tip_stream_consume",
     "tip_reuse_cache_bytes", "tip_reuse_reset", "tip_forward_reuse", "tip_stream_frame_counter_offset", "tip_stream_ingest_newest",
+    "tip_forward_rows", "tip_stream_attach", "tip_stream_detach", "tip_stream_ingest_staggered", "tip_stream_consume_staggered",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
     "tip_train_bytes_f64", "tip_train_forward_f64", "tip_train_backward_f64",
     "tip_combine_frames", "tip_combine_scratch_bytes", "tip_combine_sequence", "tip_gather_windows",
@@ -149,6 +150,11 @@ def load() -> ctypes.CDLL:
     lib.tip_reuse_reset.argtypes = [vp, sz, vp]
     lib.tip_forward_reuse.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, sz, i32, vp, vp, sz, vp]
     lib.tip_stream_frame_counter_offset.argtypes = [ctypes.POINTER(sz)]
+    lib.tip_forward_rows.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, ctypes.c_float, vp, sz, vp]
+    lib.tip_stream_attach.argtypes = [vp, i32, vp, vp, i32, vp]
+    lib.tip_stream_detach.argtypes = [vp, i32, vp, i32, vp]
+    lib.tip_stream_ingest_staggered.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    lib.tip_stream_consume_staggered.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     u64 = ctypes.c_ulonglong
     f32 = ctypes.c_float
     lib.tip_train_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz)]
@@ -251,6 +257,12 @@ class Handle:
                 keep_scale: float, workspace: int, workspace_bytes: int, stream: int):
         self._check(self.lib.tip_forward(self._h, x_imu, x_s, y, B, T, flags, keep_mask, keep_scale, workspace,
                                          workspace_bytes, stream))
+
+    def forward_rows(self, x_imu: int, x_s: int, y: int, B: int, T: int, rows: int, flags: int, keep_mask: Optional[int],
+                     keep_scale: float, workspace: int, workspace_bytes: int, stream: int):
+        """tip_forward_rows: y[b] = row rows[b] (device int [B]) of window b's output; NaN rows for indices outside [0, T)."""
+        self._check(self.lib.tip_forward_rows(self._h, x_imu, x_s, y, B, T, rows, flags, keep_mask, keep_scale, workspace,
+                                              workspace_bytes, stream))
 
     def reuse_cache_bytes(self, n_streams: int) -> int:
         n = ctypes.c_size_t()

@@ -198,6 +198,21 @@ class TF_RNN_Past_State(nn.Module):
             return self._forward_hip(x_imu, x_s, True, workspace=workspace, out=out)
         return self._dispatch(x_imu, x_s, last_row_only=True)
 
+    def forward_rows(self, x_imu, x_s, rows, *, workspace=None, out=None):
+        """One output row per window, chosen per window ([B, size_s]): y[b] = forward(x_imu, x_s)[b, rows[b]], bit for bit on the
+        same plan (include/tip_hip.h: tip_forward_rows); rows is an int32 CUDA tensor [B], and an index outside [0, T) gives an all-NaN
+        row.  Row r depends on rows 0 .. r of its window only while the later rows are finite (pad short windows with zeros).  fp32,
+        .eval() under torch.no_grad() only; the past-state keep mask and in_dropout are drawn per call as in forward_last.  workspace
+        / out as forward_last's."""
+        if self.training or torch.is_grad_enabled():
+            raise RuntimeError("tip_amd: forward_rows runs the inference kernels only (.eval() under torch.no_grad())")
+        if self.in_linear.weight.dtype != torch.float32:
+            raise RuntimeError("tip_amd: forward_rows computes in fp32 only")
+        if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_cuda or
+                rows.shape[0] != x_imu.shape[0] or rows.device != x_imu.device):
+            raise RuntimeError("tip_amd: rows must be an int32 CUDA tensor [B] on the inputs' device")
+        return self._forward_hip(x_imu, x_s, True, workspace=workspace, out=out, rows=rows.contiguous())
+
     def reuse_cache(self, n_streams: int) -> torch.Tensor:
         """A cleared ring for forward_last_reuse: 40 slots x 4 KiB per stream (in_linear row + layer-0 q | k | v row of each of the
         last 40 frames) behind a 256-byte header of frame tags."""
@@ -728,7 +743,7 @@ class TF_RNN_Past_State(nn.Module):
         self._workspace.clear()
         self._train_scratch.clear()
 
-    def _forward_hip(self, x_imu, x_s, last_row_only: bool, keep_mask="draw", apply_in_dropout=True, workspace=None, out=None):
+    def _forward_hip(self, x_imu, x_s, last_row_only: bool, keep_mask="draw", apply_in_dropout=True, workspace=None, out=None, rows=None):
         if not (x_imu.is_cuda and x_s.is_cuda):
             raise RuntimeError("tip_amd.TF_RNN_Past_State: the inference forward runs on an MI355X through "
                                "libtip_hip.so only — move the module and its inputs to the GPU (.cuda()); "
@@ -762,7 +777,8 @@ class TF_RNN_Past_State(nn.Module):
             for lo in range(0, B, max_b):
                 hi = min(B, lo + max_b)
                 parts.append(self._forward_hip(x_imu[lo:hi], x_s[lo:hi], last_row_only,
-                                               keep_mask if km is None else km[lo:hi], apply_in_dropout))
+                                               keep_mask if km is None else km[lo:hi], apply_in_dropout,
+                                               rows=None if rows is None else rows[lo:hi]))
             return torch.cat(parts, dim=0)
         # (the library launches on the CURRENT device: switch only when it is another one — the context manager costs ~3 us)
         with (torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _NO_CTX):
@@ -797,6 +813,8 @@ class TF_RNN_Past_State(nn.Module):
             else:
                 y = torch.empty(shape, dtype=pdt, device=dev)
             stream = torch.cuda.current_stream(dev).cuda_stream
+            if rows is not None and f64:
+                raise RuntimeError("tip_amd: forward_rows computes in fp32 only")
             if f64:
                 params = [p.detach() for p in self.state_dict().values()]
                 if any(p.dtype != torch.float64 or p.device != dev for p in params):
@@ -815,9 +833,16 @@ class TF_RNN_Past_State(nn.Module):
                 ws = workspace
             else:
                 ws = self._stream_buffer(self._workspace, dev, stream, need)
+            if rows is not None:     # tip_forward_rows: the same launch sequence, one chosen row per window out of the projection
+                def launch():
+                    h.forward_rows(x_imu_c.data_ptr(), x_s_c.data_ptr(), y.data_ptr(), B, T, rows.data_ptr(), flags, mask_ptr, scale,
+                                   ws.data_ptr(), ws.numel(), stream)
+            else:
+                def launch():
+                    h.forward(x_imu_c.data_ptr(), x_s_c.data_ptr(), y.data_ptr(), B, T, flags, mask_ptr, scale,
+                              ws.data_ptr(), ws.numel(), stream)
             try:
-                h.forward(x_imu_c.data_ptr(), x_s_c.data_ptr(), y.data_ptr(), B, T, flags, mask_ptr, scale,
-                          ws.data_ptr(), ws.numel(), stream)
+                launch()
             except _lib.TipHandoffError:
                 # An EARLIER launch of this handle lost an inter-workgroup hand-off (a co-tenant held CUs): its outputs were
                 # NaN-poisoned and flagged.  First time: demote the handle to the plans that need no co-residency (hybrid
@@ -825,16 +850,14 @@ class TF_RNN_Past_State(nn.Module):
                 # throughput, not every following frame.  TIP_OPT_AUTO_DEMOTE = 0 (or a second loss) reports the error.
                 if self._answer_handoff(h) is None:
                     raise
-                h.forward(x_imu_c.data_ptr(), x_s_c.data_ptr(), y.data_ptr(), B, T, flags, mask_ptr, scale,
-                          ws.data_ptr(), ws.numel(), stream)
+                launch()
             if not self._frozen and B <= self.LAZY_STASH_MAX_BATCH:
                 plist = self._plist()
                 ptrs, vsum = list(map(_data_ptr, plist)), sum(map(_version, plist))
                 if trusted and (ptrs != est[1] or vsum != est[2]):
                     self.refresh_packed(dev)                 # the parameters moved or changed under the trusted image: once more, behind it
                     self._relaunches += 1
-                    h.forward(x_imu_c.data_ptr(), x_s_c.data_ptr(), y.data_ptr(), B, T, flags, mask_ptr, scale,
-                              ws.data_ptr(), ws.numel(), stream)
+                    launch()
                 self._eval_state = (dev, ptrs, vsum)
         return y
 

@@ -33,6 +33,12 @@ host word, no synchronisation): a lost hand-off of an earlier replay — its y_l
 re-primes the engine (reset()), demotes the handle to the non-cooperating plans when TIP_OPT_AUTO_DEMOTE allows, and raises
 TipHandoffError.  The launch-by-launch engine does the same: when the model's forward reports that it demoted itself because
 of an earlier frame's loss, step() resets the engine and raises instead of consuming on top of a NaN history row.
+
+StaggeredStreamingEngine (below): the same loop for streams that start, warm up and stop ON THEIR OWN — n fixed slots, each with its
+own frame counter, attached / detached between frames (attach(slots, s_init_rows), detach(slots)) without re-priming the others.
+Windows sit in 40-row slots (rows past a slot's T_i are zero) and the forward is forward_rows (row T_i - 1 of each window;
+include/tip_hip.h: tip_forward_rows): every slot costs a T = 40 window whatever its state, so a fresh staggered engine pays the
+steady-state price from its first frame on.  No frame index anywhere: use_graph=True captures at the first step.
 """
 from __future__ import annotations
 
@@ -125,6 +131,29 @@ class StreamingEngine:
             self.reset()          # the NaN row of the lost frame is in the history ring: re-prime (and re-capture on the new plan)
             raise
 
+    def _replay_graph(self, warm, body):
+        """One replay of the captured frame `body` (capturing it first); `warm` runs the frame's forward once outside the capture."""
+        if self._graph is None:
+            # buffers the captured kernels will point at: allocated OUTSIDE the capture and held by the engine
+            if self._graph_ws is None:
+                self._graph_ws = torch.empty(self.model.workspace_bytes(self.n, 40), dtype=torch.uint8, device=self.device)
+                self._graph_y = torch.empty((self.n, self.model.size_s), dtype=torch.float32, device=self.device)
+            # packs / attaches outside the capture.  The device RNG is put back afterwards: with past_state_dropout or
+            # in_dropout live this warm-up would otherwise draw once more than the launch-by-launch loop does
+            rng = torch.cuda.get_rng_state(self.device)
+            warm()
+            torch.cuda.set_rng_state(rng, self.device)
+            torch.cuda.current_stream(self.device).synchronize()
+            self._poll_handoff()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._y_last = body()
+            self._graph = g
+            self._graph_refs = (self._graph_ws, self.model._packed_dev, self._graph_y)
+        else:
+            self._poll_handoff()
+        self._graph.replay()
+
     def _frame_auto(self):
         """ingest -> forward_last -> consume with the frame index taken from the state buffer (capturable)."""
         st = self._stream()
@@ -147,26 +176,8 @@ class StreamingEngine:
             # steady state (T = 40): one copy + one graph launch per frame
             self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
             with torch.cuda.device(self.device):
-                if self._graph is None:
-                    # buffers the captured kernels will point at: allocated OUTSIDE the capture and held by the engine
-                    if self._graph_ws is None:
-                        self._graph_ws = torch.empty(self.model.workspace_bytes(self.n, 40), dtype=torch.uint8, device=self.device)
-                        self._graph_y = torch.empty((self.n, self.model.size_s), dtype=torch.float32, device=self.device)
-                    # packs / attaches outside the capture.  The device RNG is put back afterwards: with past_state_dropout or
-                    # in_dropout live this warm-up would otherwise draw once more than the launch-by-launch loop does
-                    rng = torch.cuda.get_rng_state(self.device)
-                    self.model.forward_last(self.x_imu, self.x_s, workspace=self._graph_ws, out=self._graph_y)   # (never touches the ring)
-                    torch.cuda.set_rng_state(rng, self.device)
-                    torch.cuda.current_stream(self.device).synchronize()
-                    self._poll_handoff()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        self._y_last = self._frame_auto()
-                    self._graph = g
-                    self._graph_refs = (self._graph_ws, self.model._packed_dev, self._graph_y)
-                else:
-                    self._poll_handoff()
-                self._graph.replay()
+                self._replay_graph(lambda: self.model.forward_last(self.x_imu, self.x_s, workspace=self._graph_ws, out=self._graph_y),
+                                   self._frame_auto)   # (the warm-up never touches the ring)
             self.frame += 1
             return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": self._y_last, "T": 40}
         raw = torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72).to(self.device, non_blocking=True).contiguous()
@@ -205,3 +216,138 @@ class StreamingEngine:
             self._check(self.lib.tip_stream_consume(self.state.data_ptr(), y_last.data_ptr(), self.n, f - 5,
                                                     self.s_rest.data_ptr(), self.c_t.data_ptr(), self._stream()))
         return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": y_last, "T": T}
+
+
+class StaggeredStreamingEngine(StreamingEngine):
+    """Streams that start, warm up and stop on their own (include/tip_hip.h, "staggered streams"): n fixed slots, each with its
+    own frame counter, attached or detached.
+
+        eng = StaggeredStreamingEngine(model, s_init)      # s_init [n,114]: every slot attached, at its frame 0
+        out = eng.step(raw)                                # raw [n,72]; always a dict (below)
+        eng.detach([3])                                    # slot 3 stops (its state is kept, its rows are skipped)
+        eng.attach([3], s_init_rows)                       # slot 3 restarts at its frame 0 from s_init_rows [1,114]
+
+    step() returns s_rest [n,111], c_t [n,20], y_last [n,131], T (int32 [n]: the slot's window length this frame, 0 while priming
+    or detached) and valid (bool [n]: the slot produced a row this frame).  Rows of slots that are not valid are NaN in y_last and
+    unchanged in s_rest / c_t.  A frame is ingest_staggered -> forward_rows -> consume_staggered with no frame index, so with
+    use_graph=True it is captured once, at the first step, and replayed from then on; attach / detach run between replays.
+    Every slot occupies a T = 40 window in the forward whatever its state (a fixed slot -> window map keeps the graph static): a
+    fresh engine pays the steady-state price from its first frame on, where StreamingEngine runs shorter windows while it warms up.
+    .eval() only (fp32); reuse= is refused (the reuse ring assumes lock-step frames).  A lost hand-off (StreamingEngine's
+    contract) re-attaches every attached slot with the s_init it was last attached with and raises TipHandoffError."""
+
+    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False):
+        if reuse:
+            raise RuntimeError("tip_amd.StaggeredStreamingEngine: reuse= is not supported (the reuse ring assumes lock-step frames)")
+        if model.training:
+            raise RuntimeError("tip_amd.StaggeredStreamingEngine needs model.eval() (the inference kernels: forward_rows)")
+        self._attached = None
+        super().__init__(model, s_init, use_graph=use_graph, reuse=False)
+        self.s_rest.zero_()          # (rows of slots that have not produced a row yet: defined, and unchanged until they do)
+        self.c_t.zero_()
+
+    def _slots(self, slots, what):
+        try:
+            idx = [int(i) for i in slots]
+        except TypeError:
+            raise ValueError(f"tip_amd.StaggeredStreamingEngine.{what}: slots must be a list of slot indices") from None
+        if any(i < 0 or i >= self.n for i in idx):
+            raise ValueError(f"tip_amd.StaggeredStreamingEngine.{what}: slot index outside [0, {self.n})")
+        if len(set(idx)) != len(idx):
+            raise ValueError(f"tip_amd.StaggeredStreamingEngine.{what}: duplicate slot index")
+        return idx
+
+    def _to_dev(self, t):
+        """Host -> device without a synchronising copy from pageable memory (an attach between two frames must not drain the queue)."""
+        return t.to(self.device, non_blocking=True) if t.is_cuda else t.pin_memory().to(self.device, non_blocking=True)
+
+    def _attach_dev(self, idx):
+        if not idx:
+            return
+        with torch.cuda.device(self.device):
+            slots = self._to_dev(torch.tensor(idx, dtype=torch.int32))
+            rows = self.s_cur.index_select(0, slots.long()).contiguous()
+            self._check(self.lib.tip_stream_attach(self.state.data_ptr(), self.n, slots.data_ptr(), rows.data_ptr(), len(idx),
+                                                   self._stream()))
+
+    def reset(self):
+        """Re-prime: every attached slot restarts at its frame 0 from the s_init it was last attached with; detached slots stay
+        detached.  Drops the captured graph."""
+        if self._attached is None:
+            self._attached = [True] * self.n
+            self.s_cur = self.s_init.clone()
+            self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        self.frame = 0
+        self._graph = None
+        self._graph_refs = None
+        self._y_last = None
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tip_stream_reset(self.state.data_ptr(), self.s_cur.data_ptr(), self.n, self._stream()))
+        self._attach_dev([i for i in range(self.n) if self._attached[i]])
+
+    def attach(self, slots, s_init_rows):
+        """(Re)start the listed slots at their frame 0 from s_init_rows [len(slots),114]."""
+        idx = self._slots(slots, "attach")
+        rows = torch.as_tensor(s_init_rows, dtype=torch.float32).reshape(-1, 114) if len(idx) else None
+        if rows is not None and rows.shape[0] != len(idx):
+            raise ValueError("tip_amd.StaggeredStreamingEngine.attach: one s_init row [114] per slot")
+        if not idx:
+            return
+        with torch.cuda.device(self.device):
+            self.s_cur.index_copy_(0, self._to_dev(torch.tensor(idx, dtype=torch.long)), self._to_dev(rows))
+        for i in idx:
+            self._attached[i] = True
+        self._attach_dev(idx)
+
+    def detach(self, slots):
+        """Stop the listed slots: from the next frame on they are skipped (NaN y_last row, s_rest / c_t rows unchanged)."""
+        idx = self._slots(slots, "detach")
+        if not idx:
+            return
+        for i in idx:
+            self._attached[i] = False
+        with torch.cuda.device(self.device):
+            sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
+            self._check(self.lib.tip_stream_detach(self.state.data_ptr(), self.n, sl.data_ptr(), len(idx), self._stream()))
+
+    @property
+    def attached(self):
+        return list(self._attached)
+
+    def _frame_staggered(self):
+        """ingest_staggered -> forward_rows -> consume_staggered: no frame index anywhere (capturable from the first frame on)."""
+        st = self._stream()
+        self._check(self.lib.tip_stream_ingest_staggered(self.state.data_ptr(), self.raw.data_ptr(), self.n, self.x_imu.data_ptr(),
+                                                         self.x_s.data_ptr(), self.rows.data_ptr(), st))
+        y_last = self.model.forward_rows(self.x_imu, self.x_s, self.rows, workspace=self._graph_ws, out=self._graph_y)
+        self._check(self.lib.tip_stream_consume_staggered(self.state.data_ptr(), y_last.data_ptr(), self.rows.data_ptr(), self.n,
+                                                          self.s_rest.data_ptr(), self.c_t.data_ptr(), st))
+        return y_last
+
+    @torch.no_grad()
+    def step(self, raw_imu: torch.Tensor) -> dict:
+        if self.model.training:
+            raise RuntimeError("tip_amd.StaggeredStreamingEngine needs model.eval() (the inference kernels: forward_rows)")
+        self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
+        with torch.cuda.device(self.device):
+            if self.use_graph:
+                self._replay_graph(lambda: self.model.forward_rows(self.x_imu, self.x_s, self.rows, workspace=self._graph_ws,
+                                                                   out=self._graph_y),
+                                   self._frame_staggered)
+                y_last = self._y_last
+            else:
+                demotions = self.model.demotions + self.model.flow_demotions
+                st = self._stream()
+                self._check(self.lib.tip_stream_ingest_staggered(self.state.data_ptr(), self.raw.data_ptr(), self.n,
+                                                                 self.x_imu.data_ptr(), self.x_s.data_ptr(), self.rows.data_ptr(), st))
+                y_last = self.model.forward_rows(self.x_imu, self.x_s, self.rows)
+                if self.model.demotions + self.model.flow_demotions != demotions:
+                    # an EARLIER frame lost a hand-off (StreamingEngine.step): its NaN row went into the history rings — re-prime, raise
+                    self.reset()
+                    raise _lib.TipHandoffError(_lib.TIP_ERR_HANDOFF, "an earlier frame of this engine lost an inter-workgroup hand-off; "
+                                               "the model now runs the non-cooperating plans and every attached slot was re-attached")
+                self._check(self.lib.tip_stream_consume_staggered(self.state.data_ptr(), y_last.data_ptr(), self.rows.data_ptr(),
+                                                                  self.n, self.s_rest.data_ptr(), self.c_t.data_ptr(), st))
+            T = self.rows + 1
+        self.frame += 1
+        return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": y_last, "T": T, "valid": T > 0}
