@@ -30,7 +30,8 @@ extern "C" {
                              4: plans 5 / 7 / 8 (pair-split, split-fp16) and TIP_OPT_PACK_SPLIT16 retired (and the split-fp16 trace hook of tip_hip_debug.h with them)
                              5: exact streaming reuse — tip_reuse_cache_bytes, tip_reuse_reset, tip_forward_reuse, tip_stream_frame_counter_offset,
                                 tip_stream_ingest_newest; later, backward compatible: tip_forward_rows and the staggered streaming entry points
-                                (tip_stream_attach, tip_stream_detach, tip_stream_ingest_staggered, tip_stream_consume_staggered) */
+                                (tip_stream_attach, tip_stream_detach, tip_stream_ingest_staggered, tip_stream_consume_staggered,
+                                tip_stream_ingest_mapped, tip_stream_consume_mapped) */
 
 /* The library is built with -fvisibility=hidden: the functions declared here (and the measurement hooks of
  * tip_hip_debug.h) are its whole dynamic symbol table (tests/test_host_cpu.py compares `nm -D` with the two headers). */
@@ -303,8 +304,8 @@ TIP_API int tip_stream_ingest_newest(void* state, const float* raw_imu, int n_st
  *      tip_stream_attach: the listed slots are reset as tip_stream_reset does (history row 0 from s_init row j for slots[j]) and
  *      marked attached: their next staggered ingest is their frame 0.  tip_stream_detach marks slots detached.
  *      Cost: every slot, warming up, priming or detached, occupies a T = 40 window in the forward — a freshly started staggered
- *      engine pays the steady-state price from its first frame on, where the lock-step entry points run shorter windows.  The
- *      lock-step entry points ignore the flag. */
+ *      engine pays the steady-state price from its first frame on, where the lock-step entry points run shorter windows (the
+ *      position-mapped entry points below run the forward on the attached slots only).  The lock-step entry points ignore the flag. */
 TIP_API int tip_stream_attach(void* state, int n_streams, const int* slots, const float* s_init /* [count,114] */, int count,
                       tip_stream_t stream);
 TIP_API int tip_stream_detach(void* state, int n_streams, const int* slots, int count, tip_stream_t stream);
@@ -312,6 +313,31 @@ TIP_API int tip_stream_ingest_staggered(void* state, const float* raw_imu, int n
                                 tip_stream_t stream);
 TIP_API int tip_stream_consume_staggered(void* state, const float* y_last, const int* rows, int n_streams, float* s_rest, float* c_t,
                                  tip_stream_t stream);
+
+/* ---- staggered streams through a position map (compact pools): the forward runs on B <= n windows, not n.  slot_at is a DEVICE
+ *      int [B]: window position p (0 <= p < B) carries slot slot_at[p], and -1 (any value outside [0, n)) marks an empty position.
+ *      Each slot appears AT MOST ONCE in slot_at: that is the host's duty, it is not checked on the device (a slot listed twice would
+ *      advance twice in one frame).  Indexing: raw_imu, state, s_rest, c_t, y_slot and rows_slot are by SLOT ([n, *]); x_imu, x_s,
+ *      rows and y are by POSITION ([B, *]).  Per frame, on one stream:
+ *          tip_stream_ingest_mapped(state, raw_imu[n,72], n, slot_at, B, x_imu[B,40,90], x_s[B,40,131], rows[B], stream);
+ *              position p with slot s = slot_at[p]: window p and rows[p] are bit for bit what tip_stream_ingest_staggered writes for
+ *              slot s (s's state, frame counter and attached flag); an empty position, or a detached slot: zero window, rows[p] = -1.
+ *              Slots not listed are not touched (their frame counter does not advance).
+ *          tip_forward_rows(h, x_imu, x_s, y[B,131], B, 40, rows, ...);
+ *          tip_stream_consume_mapped(state, y, rows, slot_at, B, n, s_rest[n,111], c_t[n,20], y_slot[n,131], rows_slot[n], stream);
+ *              tip_stream_consume_staggered's work for slot slot_at[p] on y[p]; y_slot[s] = y[p] (the NaN row included) and
+ *              rows_slot[s] = rows[p] when those are given (both nullable); rows of slots not listed are not touched.
+ *      One workgroup per position: both calls cost in proportion to B.  Position -> slot is free to change between frames (the ingest
+ *      rebuilds every window from the slot's own state), so a host keeps the attached slots at positions 0 .. k-1 and runs the
+ *      forward on the smallest cheap B >= k (tip_amd.streaming.StaggeredStreamingEngine(compact=True)).  Bits: tip_forward's plan
+ *      under TIP_PLAN_AUTO depends on B, and AUTO splits a batch into whole rounds plus a remainder, so a window's output bits may
+ *      change with B or with its position (within the parity bound of the fp64 reference); on a pinned plan whose per-window results
+ *      do not depend on the batch (TIP_PLAN_FUSED) they do not.  B > n and null pointers (other than y_slot / rows_slot) give
+ *      TIP_ERR_INVALID_ARG. */
+TIP_API int tip_stream_ingest_mapped(void* state, const float* raw_imu, int n_streams, const int* slot_at, int B, float* x_imu,
+                             float* x_s, int* rows, tip_stream_t stream);
+TIP_API int tip_stream_consume_mapped(void* state, const float* y, const int* rows, const int* slot_at, int B, int n_streams,
+                              float* s_rest, float* c_t, float* y_slot, int* rows_slot, tip_stream_t stream);
 
 /* ---- exact streaming reuse: tip_forward for lock-stepped streams whose windows slide by one frame per call.
  *      In the runner a frame's model inputs never change once recorded (real_time_runner_minimal.py:74,85,137: raw_imu_buffer,

@@ -208,26 +208,30 @@ __global__ __launch_bounds__(64) void stream_detach_kernel(float* __restrict__ s
 // rows_out != nullptr (tip_stream_ingest_staggered): every stream keeps its own frame counter and window length T_i, and its window
 // sits in a 40-row slot: rows 0 .. T_i - 1 as the lock-step ingest writes them for frame f_i, rows T_i .. 39 zero, rows_out[b] = T_i - 1
 // (-1 while priming).  A detached stream gets a zero window and -1, and its state is not touched.
-__global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ state, const float* __restrict__ raw_in, int B,
+// slot_at != nullptr (tip_stream_ingest_mapped, staggered only): block p builds window p (x_imu, x_s, rows_out by POSITION) for slot
+// slot_at[p] (state, raw_in by SLOT); a position whose entry is outside [0, n) is empty: zero window, -1.  nullptr: slot = position.
+__global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ state, const float* __restrict__ raw_in, int n,
                                                             int f, float* __restrict__ x_imu, float* __restrict__ x_s, int T, int newest,
-                                                            int* __restrict__ rows_out) {
+                                                            int* __restrict__ rows_out, const int* __restrict__ slot_at) {
     using namespace sz;
     __shared__ float sm[NIMU], loc[NIMU];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    float* S = state + (size_t)b * STRIDE;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int b = slot_at ? slot_at[p] : p;
+    const bool listed = b >= 0 && b < n;
+    float* S = state + (size_t)(listed ? b : 0) * STRIDE;
     int* ctr = reinterpret_cast<int*>(S + CTR);
     int ldw = T;   // rows between two windows of x_imu / x_s
     if (rows_out) {
-        const bool attached = reinterpret_cast<const int*>(S + ATT)[0] != 0;
+        const bool attached = listed && reinterpret_cast<const int*>(S + ATT)[0] != 0;
         f = attached ? *ctr + 1 : 0;
         __syncthreads();   // every thread reads before thread 0 writes
         T = attached ? window_len(f) : 0;
         ldw = WIN;
-        float* xs0 = x_s + (size_t)b * WIN * NS;
-        float* xi0 = x_imu + (size_t)b * WIN * NX;
+        float* xs0 = x_s + (size_t)p * WIN * NS;
+        float* xi0 = x_imu + (size_t)p * WIN * NX;
         for (int i = T * NS + tid; i < WIN * NS; i += 256) xs0[i] = 0.f;
         for (int i = T * NX + tid; i < WIN * NX; i += 256) xi0[i] = 0.f;
-        if (tid == 0) rows_out[b] = T - 1;
+        if (tid == 0) rows_out[p] = T - 1;
         if (!attached) return;
     } else if (f < 0) {   // TIP_STREAM_FRAME_AUTO: the frame after the last one ingested (every thread reads before thread 0 writes)
         f = *ctr + 1;
@@ -243,8 +247,8 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
     if (f >= 5) {
         // (compile-time trip counts, every load of a loop requested before its first store: 36 round trips in flight together)
         constexpr int XS_IT = (WIN * NS + 255) / 256, XI_IT = (WIN * NX + 255) / 256;
-        float* xs = x_s + (size_t)b * ldw * NS;
-        float* xi = x_imu + (size_t)b * ldw * NX;
+        float* xs = x_s + (size_t)p * ldw * NS;
+        float* xi = x_imu + (size_t)p * ldw * NX;
         if (newest) {
             if (tid < NS) xs[(T - 1) * NS + tid] = S[HIST + (k % WIN) * NS + tid];     // history entry k (:144)
         } else {
@@ -336,7 +340,7 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
     }
     __syncthreads();
     // this frame's row: to the state (next frames read it) and straight to the newest row of x_imu, both from LDS
-    float* xin = x_imu + (size_t)b * ldw * NX + (size_t)(T - 1) * NX;
+    float* xin = x_imu + (size_t)p * ldw * NX + (size_t)(T - 1) * NX;
     if (tid < NIMU) {
         S[LOC + (k % WIN) * NIMU + tid] = loc[tid];
         xin[tid] = loc[tid];
@@ -351,13 +355,23 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
 // ---- consume the model's last row: filter, decode, pose assembly, history feedback ----------------------------
 // rows != nullptr (tip_stream_consume_staggered): a stream with rows[b] < 0 is skipped (state and output rows untouched); the others
 // consume their row as call f_b - 5 of their own counter
-__global__ __launch_bounds__(192) void stream_consume_kernel(float* __restrict__ state, const float* __restrict__ y_last, int B,
+// slot_at != nullptr (tip_stream_consume_mapped): block p consumes y_last[p] / rows[p] (by POSITION) for slot slot_at[p] (state,
+// s_rest, c_out by SLOT), after copying them to y_slot[slot] / rows_slot[slot] when given; an empty position (entry outside
+// [0, n_slots)) does nothing.  nullptr: slot = position.
+__global__ __launch_bounds__(192) void stream_consume_kernel(float* __restrict__ state, const float* __restrict__ y_last, int n_slots,
                                                              int k, float* __restrict__ s_rest, float* __restrict__ c_out,
-                                                             const int* __restrict__ rows) {
+                                                             const int* __restrict__ rows, const int* __restrict__ slot_at,
+                                                             float* __restrict__ y_slot, int* __restrict__ rows_slot) {
     using namespace sz;
     __shared__ float s[NS], aa[54], rootv[3];
-    const int b = blockIdx.x, tid = threadIdx.x;
-    if (rows && rows[b] < 0) return;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int b = slot_at ? slot_at[p] : p;
+    if (slot_at) {
+        if (b < 0 || b >= n_slots) return;
+        if (y_slot && tid < NS) y_slot[(size_t)b * NS + tid] = y_last[(size_t)p * NS + tid];
+        if (rows_slot && tid == 0) rows_slot[b] = rows[p];
+    }
+    if (rows && rows[p] < 0) return;
     float* S = state + (size_t)b * STRIDE;
     const float coeff[OUTN] = {0.07776f, 0.1296f, 0.216f, 0.36f, 0.6f, 1.0f};   // 0.6^(5..0) (:57)
     const float csum = 0.07776f + 0.1296f + 0.216f + 0.36f + 0.6f + 1.0f;
@@ -372,7 +386,7 @@ __global__ __launch_bounds__(192) void stream_consume_kernel(float* __restrict__
     if (tid == 0)
         for (int e = 0; e < 9; ++e) rr[e] = S[LOC + (k % WIN) * NIMU + e];
     if (tid < NS) {
-        const float y = y_last[(size_t)b * NS + tid];
+        const float y = y_last[(size_t)p * NS + tid];
         S[OUTS + (k % OUTN) * NS + tid] = y;
         float v;
         if (n >= OUTN) {
@@ -475,7 +489,7 @@ static int stream_ingest(void* state, const float* raw_imu, int n_streams, int f
     if (T > 0 && (!x_imu || !x_s)) return TIP_ERR_INVALID_ARG;
     if (n_streams == 0) return TIP_OK;
     hipLaunchKernelGGL(stream_ingest_kernel, dim3(n_streams), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<float*>(state), raw_imu, n_streams, frame_idx, x_imu, x_s, T, newest, nullptr);
+                       static_cast<float*>(state), raw_imu, n_streams, frame_idx, x_imu, x_s, T, newest, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 
@@ -494,7 +508,7 @@ int tip_stream_consume(void* state, const float* y_last, int n_streams, int call
     if (!state || !y_last || !s_rest || !c_t || n_streams < 0 || call_idx < TIP_STREAM_FRAME_AUTO) return TIP_ERR_INVALID_ARG;
     if (n_streams == 0) return TIP_OK;
     hipLaunchKernelGGL(stream_consume_kernel, dim3(n_streams), dim3(192), 0, static_cast<hipStream_t>(stream),
-                       static_cast<float*>(state), y_last, n_streams, call_idx, s_rest, c_t, nullptr);
+                       static_cast<float*>(state), y_last, n_streams, call_idx, s_rest, c_t, nullptr, nullptr, nullptr, nullptr);
     return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 
@@ -519,7 +533,7 @@ int tip_stream_ingest_staggered(void* state, const float* raw_imu, int n_streams
     if (!state || !raw_imu || !x_imu || !x_s || !rows || n_streams < 0) return TIP_ERR_INVALID_ARG;
     if (n_streams == 0) return TIP_OK;
     hipLaunchKernelGGL(stream_ingest_kernel, dim3(n_streams), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<float*>(state), raw_imu, n_streams, 0, x_imu, x_s, sz::WIN, 0, rows);
+                       static_cast<float*>(state), raw_imu, n_streams, 0, x_imu, x_s, sz::WIN, 0, rows, nullptr);
     return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 
@@ -528,7 +542,25 @@ int tip_stream_consume_staggered(void* state, const float* y_last, const int* ro
     if (!state || !y_last || !rows || !s_rest || !c_t || n_streams < 0) return TIP_ERR_INVALID_ARG;
     if (n_streams == 0) return TIP_OK;
     hipLaunchKernelGGL(stream_consume_kernel, dim3(n_streams), dim3(192), 0, static_cast<hipStream_t>(stream),
-                       static_cast<float*>(state), y_last, n_streams, TIP_STREAM_FRAME_AUTO, s_rest, c_t, rows);
+                       static_cast<float*>(state), y_last, n_streams, TIP_STREAM_FRAME_AUTO, s_rest, c_t, rows, nullptr, nullptr, nullptr);
+    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+}
+
+int tip_stream_ingest_mapped(void* state, const float* raw_imu, int n_streams, const int* slot_at, int B, float* x_imu, float* x_s,
+                             int* rows, tip_stream_t stream) {
+    if (!state || !raw_imu || !slot_at || !x_imu || !x_s || !rows || n_streams < 0 || B < 0 || B > n_streams) return TIP_ERR_INVALID_ARG;
+    if (B == 0) return TIP_OK;
+    hipLaunchKernelGGL(stream_ingest_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<float*>(state), raw_imu, n_streams, 0, x_imu, x_s, sz::WIN, 0, rows, slot_at);
+    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+}
+
+int tip_stream_consume_mapped(void* state, const float* y, const int* rows, const int* slot_at, int B, int n_streams, float* s_rest,
+                              float* c_t, float* y_slot, int* rows_slot, tip_stream_t stream) {
+    if (!state || !y || !rows || !slot_at || !s_rest || !c_t || n_streams < 0 || B < 0 || B > n_streams) return TIP_ERR_INVALID_ARG;
+    if (B == 0) return TIP_OK;
+    hipLaunchKernelGGL(stream_consume_kernel, dim3(B), dim3(192), 0, static_cast<hipStream_t>(stream),
+                       static_cast<float*>(state), y, n_streams, TIP_STREAM_FRAME_AUTO, s_rest, c_t, rows, slot_at, y_slot, rows_slot);
     return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 

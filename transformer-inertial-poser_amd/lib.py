@@ -39,6 +39,7 @@ EXPORTS = (
     "tip_spin_timeouts", "tip_check", "tip_stream_state_bytes", "tip_stream_reset", "tip_stream_window_len", "tip_stream_ingest", "tip_stream_consume",
     "tip_reuse_cache_bytes", "tip_reuse_reset", "tip_forward_reuse", "tip_stream_frame_counter_offset", "tip_stream_ingest_newest",
     "tip_forward_rows", "tip_stream_attach", "tip_stream_detach", "tip_stream_ingest_staggered", "tip_stream_consume_staggered",
+    "tip_stream_ingest_mapped", "tip_stream_consume_mapped",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
     "tip_train_bytes_f64", "tip_train_forward_f64", "tip_train_backward_f64",
     "tip_combine_frames", "tip_combine_scratch_bytes", "tip_combine_sequence", "tip_gather_windows",
@@ -155,6 +156,8 @@ def load() -> ctypes.CDLL:
     lib.tip_stream_detach.argtypes = [vp, i32, vp, i32, vp]
     lib.tip_stream_ingest_staggered.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     lib.tip_stream_consume_staggered.argtypes = [vp, vp, vp, i32, vp, vp, vp]
+    lib.tip_stream_ingest_mapped.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
+    lib.tip_stream_consume_mapped.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
     u64 = ctypes.c_ulonglong
     f32 = ctypes.c_float
     lib.tip_train_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz)]

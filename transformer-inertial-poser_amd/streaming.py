@@ -39,15 +39,89 @@ own frame counter, attached / detached between frames (attach(slots, s_init_rows
 Windows sit in 40-row slots (rows past a slot's T_i are zero) and the forward is forward_rows (row T_i - 1 of each window;
 include/tip_hip.h: tip_forward_rows): every slot costs a T = 40 window whatever its state, so a fresh staggered engine pays the
 steady-state price from its first frame on.  No frame index anywhere: use_graph=True captures at the first step.
+StaggeredStreamingEngine(..., compact=True) makes that cost follow the load instead: the attached slots are packed into window
+positions 0 .. k-1 (include/tip_hip.h: tip_stream_ingest_mapped) and the forward runs on the top of the step of AUTO's cost staircase
+that holds them (POOL_LADDER below).
 """
 from __future__ import annotations
 
+import bisect
 import ctypes
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import lib as _lib
+
+# Compact pools: the batch a frame's forward runs on is the top of the step of AUTO's cost staircase over B that holds the k attached
+# slots (one MI355X, 256 CUs, T = 40; tools/auto_sweep.py, profiles/pool/auto_sweep.txt, us per forward):
+#   B <= 8: 151-153 | 9-16: 185-186 | 17-24: 248-250 | 25-32: 283-296 | 33-64: 312-316 | 65-128: 459-467 | 129-256: 620-624
+# (the one-launch few-stream form steps once per window an XCD takes on, the launch chain grows to 32, the window-split encoder
+# serves 64 and 128, one window per CU 256; 1, 2 and 4 cost what 8 does and keep a tiny pool's ingest small).  Beyond 256: whole
+# rounds of POOL_ROUND windows plus a remainder served like a small batch, so the tops recur above every round — e.g. 264: 785,
+# 272: 815, 280: 878, 320: 915, 384: 1066, 512: 1202, 520: 1367, 576: 1523, 640: 1676, 768: 1852, 832: 2096, 896: 2249, 1024: 2384 —
+# except a 25-32 window remainder (288: 925 against 320: 915; 800: 2151 against 832: 2096), which the launch chain serves beside the
+# whole rounds no cheaper than 64 windows.
+POOL_LADDER = (1, 2, 4, 8, 16, 24, 32, 64, 128, 256)
+POOL_REMAINDER = (8, 16, 24, 64, 128, 256)
+POOL_ROUND = 256
+
+
+def pool_ladder(n: int) -> list:
+    """The batch sizes a compact pool of n slots runs its forward on: ascending, the last one n itself."""
+    n = int(n)
+    if n <= 0:
+        return []
+    out = [b for b in POOL_LADDER if b < n]
+    for r in range(POOL_ROUND, n, POOL_ROUND):
+        out += [r + b for b in POOL_REMAINDER if r + b < n]
+    return out + [n]
+
+
+def pool_bucket(k: int, ladder) -> int:
+    """Smallest entry of `ladder` (ascending) that holds k windows; 0 for k = 0."""
+    if k <= 0:
+        return 0
+    return ladder[bisect.bisect_left(ladder, k)]
+
+
+class SlotPositions:
+    """Window positions of a compact pool (host only): the k attached slots hold positions 0 .. k-1, each exactly once.  A slot that
+    attaches takes position k; one that detaches leaves its hole to the slot at the last position; re-attaching an attached slot
+    keeps its position; reset() lays the attached slots out in slot order."""
+
+    def __init__(self, n: int, attached=()):
+        self.n = int(n)
+        self.reset(attached)
+
+    def reset(self, attached):
+        self.slot_at = sorted({int(s) for s in attached})
+        self.pos = [-1] * self.n
+        for p, s in enumerate(self.slot_at):
+            self.pos[s] = p
+
+    def __len__(self):
+        return len(self.slot_at)
+
+    def attach(self, s: int) -> bool:
+        """True if the map changed."""
+        if self.pos[s] >= 0:
+            return False
+        self.pos[s] = len(self.slot_at)
+        self.slot_at.append(s)
+        return True
+
+    def detach(self, s: int) -> bool:
+        p = self.pos[s]
+        if p < 0:
+            return False
+        last = self.slot_at.pop()
+        if last != s:
+            self.slot_at[p] = last
+            self.pos[last] = p
+        self.pos[s] = -1
+        return True
 
 
 class StreamingEngine:
@@ -128,8 +202,12 @@ class StreamingEngine:
             h = self.model._ensure_handle()
             if self.model._answer_handoff(h) is None:     # (launch chain instead of the one-launch form, or the plans without hand-offs)
                 h.check_clear()
-            self.reset()          # the NaN row of the lost frame is in the history ring: re-prime (and re-capture on the new plan)
+            self._handoff_reset()   # the NaN row of the lost frame is in the history ring: re-prime (and re-capture on the new plan)
             raise
+
+    def _handoff_reset(self):
+        """What a lost hand-off does to the engine before TipHandoffError is raised."""
+        self.reset()
 
     def _replay_graph(self, warm, body):
         """One replay of the captured frame `body` (capturing it first); `warm` runs the frame's forward once outside the capture."""
@@ -234,13 +312,27 @@ class StaggeredStreamingEngine(StreamingEngine):
     Every slot occupies a T = 40 window in the forward whatever its state (a fixed slot -> window map keeps the graph static): a
     fresh engine pays the steady-state price from its first frame on, where StreamingEngine runs shorter windows while it warms up.
     .eval() only (fp32); reuse= is refused (the reuse ring assumes lock-step frames).  A lost hand-off (StreamingEngine's
-    contract) re-attaches every attached slot with the s_init it was last attached with and raises TipHandoffError."""
+    contract) re-attaches every attached slot with the s_init it was last attached with and raises TipHandoffError.
 
-    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False):
+    compact=True: a pool whose cost follows its load.  The k attached slots hold window positions 0 .. k-1 (SlotPositions: a fresh
+    engine and reset() lay them out in slot order, a detach moves the last position into the hole, re-attaching keeps the position)
+    and the frame runs ingest_mapped -> forward_rows on B = bucket(k) windows (pool_ladder(n); bucket(n) = n) -> consume_mapped; the
+    positions k .. B-1 are empty (zero windows), and k = 0 launches nothing.  The map is one device buffer, refreshed between frames
+    by a non-blocking copy from pinned memory.  step() returns the same dict, indexed by slot, plus active (k) and batch (B); a slot
+    that detaches gets its y_last row set to NaN and its T to 0 on the host side.  use_graph=True keeps one captured frame per
+    bucket, captured on first use or by prewarm(); all of them share one workspace sized for n, `captures` counts them, and reset()
+    or a lost hand-off (which keeps the positions) drops them all.  Bits: with every slot attached and no detach, positions are the
+    slots and B = n — bit-identical to compact=False.  Under AUTO the plan follows B (and AUTO splits a batch into whole rounds plus
+    a remainder), so a slot's bits may change when k crosses a bucket edge or the slot moves — within the parity bound of the fp64
+    reference; on a pinned plan whose per-window results do not depend on the batch (set_plan("fused")) they do not change, and
+    compact=True is bit-identical per slot to compact=False under any attach / detach schedule."""
+
+    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False, compact: bool = False):
         if reuse:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine: reuse= is not supported (the reuse ring assumes lock-step frames)")
         if model.training:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine needs model.eval() (the inference kernels: forward_rows)")
+        self.compact = bool(compact)
         self._attached = None
         super().__init__(model, s_init, use_graph=use_graph, reuse=False)
         self.s_rest.zero_()          # (rows of slots that have not produced a row yet: defined, and unchanged until they do)
@@ -272,18 +364,46 @@ class StaggeredStreamingEngine(StreamingEngine):
 
     def reset(self):
         """Re-prime: every attached slot restarts at its frame 0 from the s_init it was last attached with; detached slots stay
-        detached.  Drops the captured graph."""
+        detached.  Drops the captured graph(s); a compact pool lays its attached slots out in slot order again."""
         if self._attached is None:
             self._attached = [True] * self.n
             self.s_cur = self.s_init.clone()
             self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
+            if self.compact:
+                self.ladder = pool_ladder(self.n)
+                self.captures = 0
+                self._graphs = {}
+                self._positions = SlotPositions(self.n)
+                self.s_host = self.s_init.cpu()       # the s_init rows slots were last attached with, on the host
+                # one device buffer for everything attach / detach hand the device between two frames, filled by ONE copy from
+                # pinned memory (_flush): the position map (words 0 .. n-1, where every captured frame reads it), then the slots to
+                # attach, the slots detached (int64) and the attached slots' s_init rows
+                self._stage = torch.empty(self.n * 118 + 2, dtype=torch.int32, device=self.device)
+                self.slot_at = self._stage[: self.n]                                         # position -> slot, -1: empty
+                self._pending_attach, self._pending_detach = {}, {}
+                self.y_slot = torch.full((self.n, self.model.size_s), float("nan"), dtype=torch.float32, device=self.device)
+                self.rows_slot = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+        if self.compact:
+            self._positions.reset([i for i in range(self.n) if self._attached[i]])
+        self._restart()
+
+    def _restart(self):
+        """Every attached slot back to its frame 0 (positions kept), graphs dropped."""
         self.frame = 0
         self._graph = None
         self._graph_refs = None
         self._y_last = None
         with torch.cuda.device(self.device):
             self._check(self.lib.tip_stream_reset(self.state.data_ptr(), self.s_cur.data_ptr(), self.n, self._stream()))
+        if self.compact:
+            self._graphs = {}
+            self._pending_attach = dict.fromkeys(i for i in range(self.n) if self._attached[i])   # (re-attached by the next step)
+            self._map_dirty = True
+            return
         self._attach_dev([i for i in range(self.n) if self._attached[i]])
+
+    def _handoff_reset(self):
+        self._restart()
 
     def attach(self, slots, s_init_rows):
         """(Re)start the listed slots at their frame 0 from s_init_rows [len(slots),114]."""
@@ -292,6 +412,13 @@ class StaggeredStreamingEngine(StreamingEngine):
         if rows is not None and rows.shape[0] != len(idx):
             raise ValueError("tip_amd.StaggeredStreamingEngine.attach: one s_init row [114] per slot")
         if not idx:
+            return
+        if self.compact:            # host only: the device work goes with the next step's single upload (_flush)
+            self.s_host[idx] = rows
+            for i in idx:
+                self._attached[i] = True
+                self._map_dirty |= self._positions.attach(i)
+                self._pending_attach[i] = None
             return
         with torch.cuda.device(self.device):
             self.s_cur.index_copy_(0, self._to_dev(torch.tensor(idx, dtype=torch.long)), self._to_dev(rows))
@@ -306,6 +433,11 @@ class StaggeredStreamingEngine(StreamingEngine):
             return
         for i in idx:
             self._attached[i] = False
+        if self.compact:            # host only (_flush); an unlisted slot is never ingested, so its attached flag does not matter
+            for i in idx:
+                self._map_dirty |= self._positions.detach(i)
+                self._pending_detach[i] = None
+            return
         with torch.cuda.device(self.device):
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
             self._check(self.lib.tip_stream_detach(self.state.data_ptr(), self.n, sl.data_ptr(), len(idx), self._stream()))
@@ -313,6 +445,15 @@ class StaggeredStreamingEngine(StreamingEngine):
     @property
     def attached(self):
         return list(self._attached)
+
+    @property
+    def positions(self):
+        """compact=True: the slot at each window position 0 .. k-1."""
+        return list(self._positions.slot_at)
+
+    def bucket(self, k: int) -> int:
+        """compact=True: the batch the forward runs on with k attached slots."""
+        return pool_bucket(k, self.ladder)
 
     def _frame_staggered(self):
         """ingest_staggered -> forward_rows -> consume_staggered: no frame index anywhere (capturable from the first frame on)."""
@@ -324,10 +465,118 @@ class StaggeredStreamingEngine(StreamingEngine):
                                                           self.s_rest.data_ptr(), self.c_t.data_ptr(), st))
         return y_last
 
+    # ---- compact pools ----------------------------------------------------------------------------------------------------------
+    def _ingest_mapped(self, B):
+        self._check(self.lib.tip_stream_ingest_mapped(self.state.data_ptr(), self.raw.data_ptr(), self.n, self.slot_at.data_ptr(), B,
+                                                      self.x_imu.data_ptr(), self.x_s.data_ptr(), self.rows.data_ptr(), self._stream()))
+
+    def _consume_mapped(self, B, y):
+        self._check(self.lib.tip_stream_consume_mapped(self.state.data_ptr(), y.data_ptr(), self.rows.data_ptr(), self.slot_at.data_ptr(),
+                                                       B, self.n, self.s_rest.data_ptr(), self.c_t.data_ptr(), self.y_slot.data_ptr(),
+                                                       self.rows_slot.data_ptr(), self._stream()))
+
+    def _forward_mapped(self, B, graph):
+        ws, out = (self._graph_ws, self._graph_y[:B]) if graph else (None, None)
+        return self.model.forward_rows(self.x_imu[:B], self.x_s[:B], self.rows[:B], workspace=ws, out=out)
+
+    def _frame_mapped(self, B):
+        """ingest_mapped -> forward_rows on B windows -> consume_mapped (what a bucket's graph holds)."""
+        self._ingest_mapped(B)
+        self._consume_mapped(B, self._forward_mapped(B, True))
+
+    def _flush(self):
+        """The attach / detach calls since the last frame, on the device: one non-blocking copy from pinned memory (position map,
+        slot lists, s_init rows), the attach kernel, and NaN / -1 into the y_last / T rows of the detached slots (no kernel writes
+        the rows of a slot that is not listed).  Stream order puts it after the previous frame and before this one."""
+        if not (self._map_dirty or self._pending_attach or self._pending_detach):
+            return
+        n, att, det = self.n, list(self._pending_attach), list(self._pending_detach)
+        o_det = (n + len(att) + 1) // 2 * 2          # (int64 entries: 8-byte aligned)
+        o_rows = o_det + 2 * len(det)
+        h = np.empty(o_rows + 114 * len(att), dtype=np.int32)
+        h[:n] = -1
+        h[: len(self._positions)] = self._positions.slot_at
+        h[n: n + len(att)] = att
+        h[o_det: o_rows] = np.asarray(det, dtype=np.int64).view(np.int32)
+        h[o_rows:] = self.s_host[att].numpy().reshape(-1).view(np.int32)
+        self._stage[: h.size].copy_(torch.from_numpy(h).pin_memory(), non_blocking=True)
+        base = self._stage.data_ptr()
+        if att:
+            self._check(self.lib.tip_stream_attach(self.state.data_ptr(), n, base + 4 * n, base + 4 * o_rows, len(att), self._stream()))
+        if det:
+            sl = self._stage[o_det: o_rows].view(torch.int64)
+            self.y_slot.index_fill_(0, sl, float("nan"))
+            self.rows_slot.index_fill_(0, sl, -1)
+        self._map_dirty = False
+        self._pending_attach, self._pending_detach = {}, {}
+
+    def _capture(self, B):
+        if self._graph_ws is None:
+            # one workspace and one output buffer for every bucket, sized for the largest (n): the one-launch form keeps its counters
+            # at offset 0 for any batch (include/tip_hip.h, tip_workspace_bytes), and the graphs replay one at a time on one stream
+            self._graph_ws = torch.empty(self.model.workspace_bytes(self.n, 40), dtype=torch.uint8, device=self.device)
+            self._graph_y = torch.empty((self.n, self.model.size_s), dtype=torch.float32, device=self.device)
+        rng = torch.cuda.get_rng_state(self.device)
+        self._forward_mapped(B, True)          # packs / attaches outside the capture
+        torch.cuda.set_rng_state(rng, self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        self._poll_handoff()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            self._frame_mapped(B)
+        self._graphs[B] = (g, self._graph_ws, self.model._packed_dev, self._graph_y)   # what the captured kernels point at
+        self.captures += 1
+
+    @torch.no_grad()
+    def prewarm(self, buckets=None):
+        """compact=True, use_graph=True: capture the frame of every bucket (default: the whole ladder) now, so that no capture
+        happens on the hot path.  Without use_graph there is nothing to capture."""
+        if not self.compact:
+            raise RuntimeError("tip_amd.StaggeredStreamingEngine.prewarm: compact=True only (the plain engine has one graph)")
+        bs = self.ladder if buckets is None else [int(b) for b in buckets]
+        if any(b not in self.ladder for b in bs):
+            raise ValueError(f"tip_amd.StaggeredStreamingEngine.prewarm: buckets must come from the ladder {self.ladder}")
+        if not self.use_graph:
+            return
+        with torch.cuda.device(self.device):
+            for B in bs:
+                if B not in self._graphs:
+                    self._capture(B)
+
+    def _step_compact(self, raw_imu):
+        k = len(self._positions)
+        B = self.bucket(k)
+        if k:
+            self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
+        with torch.cuda.device(self.device):
+            self._flush()
+            if k:
+                if self.use_graph:
+                    if B not in self._graphs:
+                        self._capture(B)
+                    else:
+                        self._poll_handoff()
+                    self._graphs[B][0].replay()
+                else:
+                    demotions = self.model.demotions + self.model.flow_demotions
+                    self._ingest_mapped(B)
+                    y = self._forward_mapped(B, False)
+                    if self.model.demotions + self.model.flow_demotions != demotions:
+                        self._handoff_reset()
+                        raise _lib.TipHandoffError(_lib.TIP_ERR_HANDOFF, "an earlier frame of this engine lost an inter-workgroup "
+                                                   "hand-off; the model now runs the non-cooperating plans and every attached slot "
+                                                   "was re-attached")
+                    self._consume_mapped(B, y)
+            T = self.rows_slot + 1
+        self.frame += 1
+        return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": self.y_slot, "T": T, "valid": T > 0, "active": k, "batch": B}
+
     @torch.no_grad()
     def step(self, raw_imu: torch.Tensor) -> dict:
         if self.model.training:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine needs model.eval() (the inference kernels: forward_rows)")
+        if self.compact:
+            return self._step_compact(raw_imu)
         self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
         with torch.cuda.device(self.device):
             if self.use_graph:
@@ -343,7 +592,7 @@ class StaggeredStreamingEngine(StreamingEngine):
                 y_last = self.model.forward_rows(self.x_imu, self.x_s, self.rows)
                 if self.model.demotions + self.model.flow_demotions != demotions:
                     # an EARLIER frame lost a hand-off (StreamingEngine.step): its NaN row went into the history rings — re-prime, raise
-                    self.reset()
+                    self._handoff_reset()
                     raise _lib.TipHandoffError(_lib.TIP_ERR_HANDOFF, "an earlier frame of this engine lost an inter-workgroup hand-off; "
                                                "the model now runs the non-cooperating plans and every attached slot was re-attached")
                 self._check(self.lib.tip_stream_consume_staggered(self.state.data_ptr(), y_last.data_ptr(), self.rows.data_ptr(),
