@@ -10,7 +10,7 @@
  *     TIP_S16_TRACE
  *   ablations (wrong results, timing only): TIP_FUSED_ABLATE, TIP_RNN_ABLATE (bits: 1 polls never wait, 2 no MFMAs, 4 no row touches,
  *     16 A fragments of the first two batches only — a quarter of the LDS reads, 32 clamp instead of tanh; 128+ trace stamp selection)
- *   A/B selections: TIP_AUTO_SPLIT=0 (no rounds + remainder split), TIP_RNN_ROWS4=0 / TIP_RNN_W4=0|1 / TIP_RNN_C16=4 / TIP_RNN_HANDOFF=0 /
+ *   A/B selections: TIP_AUTO_SPLIT=0 (no rounds + remainder split), TIP_AUTO_MERGE=0 (no shared tail), TIP_RNN_ROWS4=0 / TIP_RNN_W4=0|1 / TIP_RNN_C16=4 / TIP_RNN_HANDOFF=0 /
  *     TIP_RNN_PREPOLL=0 / TIP_RNN_ROTATE=0 (recurrence variants), TIP_HEAD=old (streaming projection kernel), TIP_GENERAL_PGEMM=0 /
  *     TIP_GENERAL_GEMM=32 / TIP_GENERAL_ATTN=v (general plan), TIP_TRAIN_FUSED=0 / TIP_TRAIN_FUSED_BWD=0 / TIP_TRAIN_FWD_PADDED /
  *     TIP_TRAIN_WIN_GEMM=0 / TIP_TRAIN_PGEMM=0 / TIP_TGEMM_TILE / TIP_TGEMM16_TILE / TIP_DW_KERNEL / TIP_DW_SPLITS / TIP_DW_SPLITDIV /
@@ -38,6 +38,13 @@ TIP_API int tip_debug_read_rnn_trace(unsigned long long* out, int n);  /* cluste
 TIP_API int tip_debug_clock_probe(unsigned long long* dev_out, void* stream); /* s_memtime / s_memrealtime pair (bench.py: clock under load) */
 TIP_API int tip_debug_read_head_wg(unsigned long long* out, int n);    /* output projection: per-workgroup lifetimes (tools/head_trace.py) */
 TIP_API int tip_debug_read_head_trace(unsigned long long* out, int n); /* output projection: tile stamps */
+/* The schedule tip_forward would take for B windows of length T on `cus` CUs (<= 0: the handle's own count; a handle made without
+ * a GPU reports 256), under the handle's options and a workspace of `workspace_bytes`; reuse_full: as tip_forward_reuse on full
+ * windows.  Touches no device.  out (cap >= 9): nparts, shared_tail, rnn_cluster, then first / count / plan of part 0 and part 1
+ * (zeros for an absent part); plan is resolved (never TIP_PLAN_AUTO).  nparts = 2: whole rounds + remainder, as two launch sequences,
+ * or (shared_tail) two encoders with one recurrence and one output projection.  Returns the schedule's status (TIP_OK, or
+ * TIP_ERR_UNSUPPORTED_CONFIG for a pinned plan that does not serve the shape), TIP_ERR_INVALID_ARG for bad arguments. */
+TIP_API int tip_debug_schedule(const tip_handle* h, int B, int T, int cus, int reuse_full, size_t workspace_bytes, int* out, int cap);
 
 #ifdef __cplusplus
 }

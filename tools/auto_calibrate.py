@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""AUTO's decisions against the box it runs on (the plan selection in csrc/tip_abi.hip is a cost model in absolute
+"""AUTO's decisions against the box it runs on (the plan selection in csrc/tip_schedule.hip is a cost model in absolute
 microseconds, calibrated on one MI355X at one clock).
 
   python tools/auto_calibrate.py            the 64-batch sweep: AUTO's step time next to every explicit plan that serves the batch;
@@ -7,7 +7,7 @@ microseconds, calibrated on one MI355X at one clock).
   python tools/auto_calibrate.py --stages   the stage costs the model is built from, re-measured through TIP_OPT_PROFILE = 1
                                             (encoder round of the one- / two-window kernels, window-split encoder on four / two CUs,
                                             recurrence + projection per round, the few-stream plan for 1 .. 44 windows) next to the
-                                            constants in csrc/tip_abi.hip
+                                            constants in csrc/tip_schedule.hip
 
 `sweep()` is what tests/test_auto_model_gpu.py runs."""
 import contextlib, os, sys
@@ -130,7 +130,7 @@ if __name__ == "__main__":
     m.load_state_dict({k: torch.tensor(v) for k, v in synth.make_weights(synth.PAPER, seed=0).items()})
     m = m.cuda().eval()
     if "--stages" in sys.argv:
-        print(f"{'ingredient of the AUTO cost model (csrc/tip_abi.hip)':68s} {'model us':>9s} {'here us':>9s}  ratio")
+        print(f"{'ingredient of the AUTO cost model (csrc/tip_schedule.hip)':68s} {'model us':>9s} {'here us':>9s}  ratio")
         for name, const, meas in stages(m):
             print(f"{name:68s} {const:9.0f} {meas:9.1f}  {meas / const:5.2f}")
     else:

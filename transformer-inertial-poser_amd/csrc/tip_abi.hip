@@ -129,7 +129,8 @@ void pack_linear(float* img, const PackedLinear& p, const float* W, const float*
     if (b) memcpy(bb, b, sizeof(float) * p.N);
 }
 
-Workspace carve_workspace(const Dims& d, int B, int T) {
+}  // namespace
+Workspace tip::carve_workspace(const Dims& d, int B, int T) {
     Workspace w;
     const size_t M = (size_t)B * T;
     const size_t Mp = align_up(M, 16);
@@ -156,6 +157,7 @@ Workspace carve_workspace(const Dims& d, int B, int T) {
     w.total_bytes = off * sizeof(float);
     return w;
 }
+namespace {
 
 int fail_hip(tip_handle* h, hipError_t e, const char* where) {
     h->last_hip_error = std::string(where) + ": " + hipGetErrorString(e);
@@ -689,11 +691,221 @@ struct ReuseCtx {
     const int* frame_ctr;
     int frame_idx;
 };
+// One launch sequence of a forward: the encoder of one or two parts of `n` consecutive windows, then ONE tail — the RNN input GEMM where
+// the encoder did not emit it, the recurrence, the output projection — over all n.  Pointers are at the sequence's first window; the
+// workspace is carved for n windows.
+struct LaunchSeq {
+    tip_handle* h;
+    hipStream_t s;
+    int cus;
+    const float* x_imu;
+    const float* x_s;
+    const float* mask;          // null: no keep mask from the caller
+    float keep_scale;
+    float* y;
+    const int* rows;
+    int n, T, flags;
+    float* W0;
+    Workspace ws;
+    int rnn_cluster;
+    const ReuseCtx* reuse;      // full windows: the two-window encoder reads the ring
+    const TrainDropout* td;     // tip_forward_dropout: the latency plan's dropout sites
+    // what the encoder leaves for the tail
+    int plan = TIP_PLAN_AUTO;
+    bool ih_done = false;       // the RNN input projection is in `big` already
+    bool hall_armed = false;    // ... and the HALL rows are pre-filled for the sentinel-polling recurrence
+    bool rnn_done = false, head_done = false;
+};
+
+#define TIP_TRY(expr, what)                                     \
+    do {                                                        \
+        const hipError_t e_ = (expr);                           \
+        if (e_ != hipSuccess) return fail_hip(q.h, e_, what);   \
+    } while (0)
+// one launch that is a profile stage of its own (tip_profile_read)
+#define TIP_STAGE(name, expr)              \
+    do {                                   \
+        StageScope stage_(q.h, q.s, name); \
+        TIP_TRY(expr, name);               \
+    } while (0)
+
+// The encoder of windows [off, off + p.count) of the sequence.  (A sequence of two parts is the shared tail's: both parts are on plans
+// that emit the RNN input term — only those write at a window offset.)
+static int run_encoder(LaunchSeq& q, const SchedPart& p, int off) {
+    tip_handle* h = q.h;
+    const Dims& d = h->d;
+    const float* P = h->packed_dev;
+    const PackedLayout& L = h->lay;
+    hipStream_t s = q.s;
+    const int B = p.count, T = q.T, cus = q.cus, M = B * T;
+    const size_t row_i = (size_t)T * d.n_imu_total, row_s = (size_t)T * d.S, row_r = (size_t)T * d.R;
+    const float* x_imu = q.x_imu + off * row_i;
+    const float* x_s = q.x_s + off * row_s;
+    const float* mask = q.mask ? q.mask + off * row_s : nullptr;
+    const float keep_scale = q.keep_scale;
+    float* xa = q.W0 + q.ws.xa;
+    float* xb = q.W0 + q.ws.xb;
+    float* big = q.W0 + q.ws.big;
+    float* att = q.W0 + q.ws.att;
+    float* ih = big + off * row_r;
+    float* hall = q.W0 + q.ws.hall + off * row_r;
+    const Guard gd = h->guard();
+    auto arm_hall = [&]() { return rnn_uses_sentinel(d, q.n, T, q.rnn_cluster); };
+    q.plan = p.plan;
+    if (p.plan == TIP_PLAN_LATENCY) {
+        StageScope sc(h, s, "latency_chain");
+        LatencyHead lh{P + L.out_frag_off, P + L.out_lin.b_off, q.y, d.S, d.S, (q.flags & TIP_FWD_LAST_ROW_ONLY) != 0, h->flow_epoch, &q.head_done,
+                       reinterpret_cast<unsigned long long*>(q.W0 + q.ws.flow)};
+        lh.rows = q.rows;
+        TIP_TRY(launch_latency_plan(d, P + L.fused_off, P + L.whh_frag_off, x_imu, x_s, mask, keep_scale, q.W0 + q.ws.lat, hall,
+                                    B, T, cus, gd, s, q.td, cus == h->num_cus && !h->no_flow ? &lh : nullptr), "latency_chain");
+        q.rnn_done = true;
+    } else if (p.plan == TIP_PLAN_FUSED1S) {
+        StageScope sc(h, s, "fused_encoder");
+        q.ih_done = true;
+        q.hall_armed = arm_hall();
+        TIP_TRY(launch_fused_encoder1s(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, ih, q.hall_armed ? hall : nullptr,
+                                       q.W0 + q.ws.xchg, B, cus, h->f1s_parts, gd, s), "fused_encoder1s");
+    } else if (p.plan == TIP_PLAN_FUSED2) {
+        StageScope sc(h, s, "fused_encoder");
+        q.ih_done = true;
+        q.hall_armed = arm_hall();
+        TIP_TRY(launch_fused_encoder2(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, ih, q.hall_armed ? hall : nullptr, B,
+                                      cus, s, q.reuse ? q.reuse->cache : nullptr, q.reuse ? q.reuse->frame_ctr : nullptr,
+                                      q.reuse ? q.reuse->frame_idx : 0), "fused_encoder2");
+    } else if (p.plan == TIP_PLAN_FUSEDH || p.plan == TIP_PLAN_FUSED) {
+        StageScope sc(h, s, "fused_encoder");
+        q.ih_done = fused_has_rnn_ih(d);
+        q.hall_armed = q.ih_done && arm_hall();   // the encoder pre-fills its HALL rows
+        if (p.plan == TIP_PLAN_FUSEDH)
+            TIP_TRY(launch_fused_encoder_h(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, q.ih_done ? nullptr : xa,
+                                           q.ih_done ? ih : nullptr, q.hall_armed ? hall : nullptr, B, T, cus, s), "fused_encoder_h");
+        else
+            TIP_TRY(launch_fused_encoder(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, q.ih_done ? nullptr : xa,
+                                         q.ih_done ? ih : nullptr, q.hall_armed ? hall : nullptr, B, T, cus, s), "fused_encoder");
+    } else {
+        TIP_STAGE("prologue", launch_prologue(d, x_imu, x_s, mask, keep_scale, big, M, s));
+        TIP_STAGE("in_linear", launch_gemm(big, d.InPad, P + L.in_lin.w_off, L.in_lin.Kpad, P + L.in_lin.b_off, nullptr, 0, xa,
+                                             d.D, M, d.D, L.in_lin.Npad, 0, s));
+        for (int l = 0; l < d.L; ++l) {
+            const PackedLayer& pl = L.layers[l];
+            TIP_STAGE("qkv_gemm", linear_gemm(P, pl.qkv, xa, d.D, nullptr, 0, big, 3 * d.D, M, 0, s));
+            TIP_STAGE("attention", launch_attention(d, big, att, B, T, s));
+            TIP_STAGE("out_proj_gemm", linear_gemm(P, pl.out, att, d.D, xa, d.D, xb, d.D, M, 2, s));
+            TIP_STAGE("layernorm1", launch_layernorm(xb, P + pl.g1_off, P + pl.be1_off, M, d.D, s));
+            TIP_STAGE("ffn1_gemm", linear_gemm(P, pl.ff1, xb, d.D, nullptr, 0, big, d.F, M, 1, s));
+            TIP_STAGE("ffn2_gemm", linear_gemm(P, pl.ff2, big, d.F, xb, d.D, xa, d.D, M, 2, s));
+            TIP_STAGE("layernorm2", launch_layernorm(xa, P + pl.g2_off, P + pl.be2_off, M, d.D, s));
+        }
+    }
+    return TIP_OK;
+}
+
+// RNN input GEMM (where the encoder left the plain rows in xa), recurrence, output projection — over all q.n windows
+static int run_tail(LaunchSeq& q) {
+    tip_handle* h = q.h;
+    const Dims& d = h->d;
+    const float* P = h->packed_dev;
+    const PackedLayout& L = h->lay;
+    hipStream_t s = q.s;
+    const int B = q.n, T = q.T, M = B * T;
+    float* big = q.W0 + q.ws.big;
+    float* hall = q.W0 + q.ws.hall;
+    const float* head_in = q.W0 + q.ws.xa;   // encoder output [M, D]
+    int head_ld = d.D;
+    if (d.with_rnn) {
+        if (!q.rnn_done && !q.ih_done)
+            TIP_STAGE("rnn_ih_gemm", launch_gemm(head_in, d.D, P + L.rnn_ih.w_off, L.rnn_ih.Kpad, P + L.rnn_ih.b_off, nullptr, 0, big, d.R, M, d.R,
+                                                 L.rnn_ih.Npad, 0, s));
+        if (!q.rnn_done)
+            TIP_STAGE("rnn_recurrence", launch_rnn(d, big, P + L.whh_frag_off, hall, reinterpret_cast<unsigned*>(q.W0 + q.ws.flags), B, T,
+                                                   q.rnn_cluster, q.cus, q.hall_armed, h->guard(), s));
+        head_in = hall;
+        head_ld = d.R;
+    }
+    if (!q.head_done) {
+        StageScope sc(h, s, "out_linear");
+        const bool last_only = (q.flags & TIP_FWD_LAST_ROW_ONLY) != 0;
+        const int* rows = q.rows;
+        const int Kh = d.with_rnn ? d.R : d.D;
+        // rows the projection runs on: all M, or row T-1 of every window (real_time_runner_minimal.py:150), or row rows[b] of window b
+        // (tip_forward_rows: A is then the first row, lda the row stride)
+        const float* hA = last_only && !rows ? head_in + (size_t)(T - 1) * head_ld : head_in;
+        const long long hlda = last_only && !rows ? (long long)T * head_ld : head_ld;
+        const int hM = last_only ? B : M;
+        if (q.plan == TIP_PLAN_LATENCY) {
+            TIP_TRY(launch_latency_head(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, q.y, d.S, hM, d.S, s, rows, T), "out_linear");
+        } else {
+            // window lengths that are multiples of 40 (the paper's and the scaled configuration's): the register-resident
+            // kernel for both forms of the output (bit-identical last rows); everything else: head_gemm_kernel for both
+            hipError_t he = hipErrorInvalidValue;
+            if (measure_switches().head_ksplit && T % 40 == 0)   // TIP_HEAD=old: measurement
+                he = launch_head_ksplit(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, q.y, d.S, hM, d.S, Kh, last_only, q.cus, s, rows, T);
+            if (he == hipErrorInvalidValue)
+                he = launch_head_gemm(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, q.y, d.S, hM, d.S, Kh, s, rows, T);
+            TIP_TRY(he, "out_linear");
+        }
+    }
+    return TIP_OK;
+}
+#undef TIP_STAGE
+#undef TIP_TRY
+
 // rows (tip_forward_rows; null: tip_forward): one output row per window, row rows[b] of window b — only the output projection's row
 // addressing differs (TIP_FWD_LAST_ROW_ONLY is set with it, so everything that depends on the output's shape takes the last-row form)
 static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, int flags,
                         const float* keep_mask, float keep_scale, void* workspace, size_t workspace_bytes,
-                        tip_stream_t stream, const ReuseCtx* reuse, const int* rows = nullptr);
+                        tip_stream_t stream, const ReuseCtx* reuse, const int* rows = nullptr) {
+    if (!h || !x_imu || !x_s || !y || B < 0 || T < 1) return TIP_ERR_INVALID_ARG;
+    // (cfg.t_max is a sizing hint, not a limit: the reference builds its causal mask for any window length, :56-58,85; what
+    // bounds B * T here are the 32-bit byte offsets of the buffer descriptors)
+    if ((long long)B * T * (long long)std::max(std::max(3 * h->d.D, h->d.F), std::max(h->d.R, h->d.InPad)) * 4 > 0x7fffffffLL)
+        return TIP_ERR_UNSUPPORTED_CONFIG;
+    if ((flags & TIP_FWD_KEEP_MASK) && !keep_mask) return TIP_ERR_INVALID_ARG;
+    if (!h->packed_dev) return TIP_ERR_NOT_READY;
+    if (tip_check(h, 0) != TIP_OK) return TIP_ERR_HANDOFF;   // sticky: an earlier launch lost a hand-off (tip_check(h, 1) clears)
+    if (B == 0) return TIP_OK;
+    const Dims& d = h->d;
+    const Workspace ws = carve_workspace(d, B, T);
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 || workspace_bytes < ws.total_bytes)
+        return TIP_ERR_WORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int cus = effective_cus(h->num_cus, s);   // the stream's CU mask counts, not the device's CU total
+    // (tip_forward_reuse, full windows: ONE launch sequence on the two-window encoder's reuse form, whatever the batch; while the windows
+    // still grow, T < 40, the ring update below is all the reuse form does and the forward is tip_forward's)
+    const bool reuse_full = reuse && T == 40;
+    const Schedule sc = schedule_forward(ScheduleIn{d, B, T, cus, h->num_cus, h->plan, h->rnn_cluster, h->f1s_parts, h->demoted != 0, reuse_full,
+                                                    workspace_bytes});
+    if (sc.status != TIP_OK) return sc.status;
+    const float* mask = (flags & TIP_FWD_KEEP_MASK) ? keep_mask : nullptr;
+    const size_t row_i = (size_t)T * d.n_imu_total, row_s = (size_t)T * d.S;
+    const size_t row_y = (flags & TIP_FWD_LAST_ROW_ONLY) ? (size_t)d.S : row_s;
+    // A shared tail: both parts in ONE launch sequence over the whole batch's carve-up.  Otherwise every part is a launch sequence of its
+    // own, carved for its own windows from the start of the same workspace (stream-ordered).
+    const int nseq = sc.shared_tail ? 1 : sc.nparts;
+    for (int i = 0; i < nseq; ++i) {
+        const int first = sc.part[i].first, n = sc.shared_tail ? B : sc.part[i].count;
+        LaunchSeq q{h, s, cus, x_imu + first * row_i, x_s + first * row_s, mask ? mask + first * row_s : nullptr, mask ? keep_scale : 1.f,
+                    y + first * row_y, rows ? rows + first : nullptr, n, T, flags, static_cast<float*>(workspace),
+                    n == B ? ws : carve_workspace(d, n, T), sc.part[i].rnn_cluster, reuse_full ? reuse : nullptr, nullptr};
+        CoopSerial serial(h->device, s);   // forwards of different streams do not overlap on the device (cooperating kernels)
+        if (serial.status != hipSuccess) return fail_hip(h, serial.status, "stream serialisation");
+        if (reuse) {
+            // the newest row of every window -> slot (frame mod 40) of its stream's ring (a reuse forward is always one sequence)
+            StageScope stage(h, s, "reuse_update");
+            const hipError_t e = launch_reuse_update(d, h->packed_dev + h->lay.fused_off, x_imu, x_s, reuse->cache, reuse->frame_ctr, reuse->frame_idx, B, T, s);
+            if (e != hipSuccess) return fail_hip(h, e, "reuse_update");
+        }
+        for (int p = i; p < (sc.shared_tail ? sc.nparts : i + 1); ++p) {
+            const int st = run_encoder(q, sc.part[p], sc.part[p].first - first);
+            if (st != TIP_OK) return st;
+        }
+        const int st = run_tail(q);
+        if (st != TIP_OK) return st;
+    }
+    h->forward_count++;   // one forward, however many launch sequences
+    return TIP_OK;
+}
 
 int tip_forward(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, int flags,
                 const float* keep_mask, float keep_scale, void* workspace, size_t workspace_bytes,
@@ -734,334 +946,6 @@ int tip_forward_reuse(tip_handle* h, const float* x_imu, const float* x_s, float
     return forward_impl(h, x_imu, x_s, y, B, T, flags, nullptr, 1.f, workspace, workspace_bytes, stream, &rc);
 }
 
-static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, int flags,
-                        const float* keep_mask, float keep_scale, void* workspace, size_t workspace_bytes,
-                        tip_stream_t stream, const ReuseCtx* reuse, const int* rows) {
-    if (!h || !x_imu || !x_s || !y || B < 0 || T < 1) return TIP_ERR_INVALID_ARG;
-    // (cfg.t_max is a sizing hint, not a limit: the reference builds its causal mask for any window length, :56-58,85; what
-    // bounds B * T here are the 32-bit byte offsets of the buffer descriptors)
-    if ((long long)B * T * (long long)std::max(std::max(3 * h->d.D, h->d.F), std::max(h->d.R, h->d.InPad)) * 4 > 0x7fffffffLL)
-        return TIP_ERR_UNSUPPORTED_CONFIG;
-    if ((flags & TIP_FWD_KEEP_MASK) && !keep_mask) return TIP_ERR_INVALID_ARG;
-    if (!h->packed_dev) return TIP_ERR_NOT_READY;
-    if (tip_check(h, 0) != TIP_OK) return TIP_ERR_HANDOFF;   // sticky: an earlier launch lost a hand-off (tip_check(h, 1) clears)
-    if (B == 0) return TIP_OK;
-    const Dims& d = h->d;
-    const Workspace ws = carve_workspace(d, B, T);
-    const Guard gd = h->guard();
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 || workspace_bytes < ws.total_bytes)
-        return TIP_ERR_WORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int cus = effective_cus(h->num_cus, s);   // the stream's CU mask counts, not the device's CU total
-    // AUTO, a batch that is whole rounds of #CUs windows plus a SMALL remainder: the one-window kernel takes a full round (0.53 ms +
-    // the tail) for the remainder alone; the few-stream latency plan takes 0.16-0.28 ms for up to 32 windows and the window-split
-    // encoder 0.30 ms for up to #CUs / 4 (one window on four CUs), 0.45 ms for up to #CUs / 2.  Run the whole rounds
-    // and the remainder as two launch sequences when the model below says so (stream-ordered: they share the workspace); every
-    // window's result is bit-identical to what its part's plan gives on its own (tests/test_benchmarked_shapes_gpu.py).
-    // Costs in us from profiles/r04/plan_bench_split.txt (B = 256 step 0.625 ms; the remainder's latency-plan forward measured
-    // 163 / 177 / 201 / 282 / 372 us for 1 / 8 / 16 / 32 / 44 windows behind it); TIP_AUTO_SPLIT=0 disables (measurement).
-    // (the cost model below is calibrated at T = 40 — the only window length the window-split plans serve — and its constants scale
-    // with the CU count only through `cus`, which is the device's: other window lengths take whole rounds)
-    // (tip_forward_reuse, full windows: ONE launch sequence on the two-window encoder's reuse form, whatever the batch)
-    const bool reuse_full = reuse && T == 40;
-    if (!reuse_full && h->plan == TIP_PLAN_AUTO && !h->demoted && cus == h->num_cus && B > cus && T == 40 && fused_supported(d, T) && fused_has_rnn_ih(d)) {
-        static const bool split_on = !(tip_env("TIP_AUTO_SPLIT") && tip_env("TIP_AUTO_SPLIT")[0] == '0');
-        const int r = B % cus, bm = B - r;
-        // what the remainder costs on its own (us; AUTO's choice for that many windows, below): the latency plan up to 32 windows
-        // (measured 163 / 177 / 201 / 282 / 372 us for 1 / 8 / 16 / 32 / 44), the window-split encoder up to #CUs / 4 (0.305 ms) and
-        // #CUs / 2 (0.45 ms)
-        long long rem = -1;
-        const bool quad = fused2_supported(d, T) && h->f1s_parts != 2 && fused1s_quad_fits(r, cus);
-        // (round 6, the few-stream plan as one launch: 147 / 149 / 181 / 241 us for <= 1 / 8 / 16 / 24 windows — a step per window that shares
-        //  an XCD — and the launch chain's 286 at 32, 372 at 44; tools/auto_calibrate.py --stages re-measures every constant here)
-        auto lat_us = [](int n) { return n <= 8 ? 147LL + n / 4 : n <= 16 ? 181LL : n <= 24 ? 241LL : n <= 32 ? 200LL + (long long)(3.6 * (n - 8)) : 286LL + 10LL * (n - 32); };
-        if (r >= 1 && r <= (quad ? 32 : 48) && latency_supported(d, r, T)) rem = lat_us(r);
-        else if (r >= 1 && fused2_supported(d, T) && fused1s_fits(r, cus)) rem = quad ? 305 : 452;
-        else if (r >= 1 && latency_supported(d, r, T)) rem = lat_us(r);
-        if (split_on && rem >= 0) {
-            auto single = [&](long long b) {   // encoder rounds of the cheaper of the two fused kernels + recurrence / projection rounds
-                const long long rh = (b + cus - 1) / cus, r2 = ((b + 1) / 2 + cus - 1) / cus;
-                const long long enc = (fused2_supported(d, T) && r2 * 1049 < rh * 527) ? r2 * 1049 : rh * 527;
-                return enc + 96 * rh;
-            };
-            // (a part never needs more workspace than the whole — carve_workspace is monotone, tests/test_host_cpu.py — but a caller's
-            // buffer sized by an older library must fall through to the single launch sequence, not fail)
-            // Round 5: a remainder that takes the window-split encoder shares ONE recurrence and ONE output projection with the whole
-            // rounds — the two encoders write their windows' input terms (and arm their HALL rows) side by side in the whole batch's
-            // workspace — instead of bringing a 62-us recurrence + a projection launch of its own: the recurrence serves the extra
-            // tiles next to the ones it has (their hops overlap), ~35 us for up to 128 more windows.  rnn_hidden 512 only (the
-            // four-window recurrence, whose per-window results do not depend on the tiling); bit-identical to the two sequences.
-            const bool rem_f1s = r >= 1 && !(r <= (quad ? 32 : 48) && latency_supported(d, r, T)) && fused2_supported(d, T) && fused1s_fits(r, cus);
-            static const bool merge_on = !(tip_env("TIP_AUTO_MERGE") && tip_env("TIP_AUTO_MERGE")[0] == '0');   // measurement
-            // (the recurrence advances 1, 2 or 4 tiles per cluster together: a third tile costs a fourth's time, and a fifth a second
-            // pass — B = 556 measured 1 533 us merged against 1 509: merge only where the remainder does not push the whole rounds'
-            // tile count per cluster across such a step, or the rounds have a single tile)
-            const int tpg_b = ((B + 3) / 4 + 63) / 64, tpg_m = ((bm + 3) / 4 + 63) / 64;
-            const bool tiles_ok = cus == 256 && (tpg_b <= 2 || (tpg_b <= 4 && tpg_m >= 3));
-            if (merge_on && rem_f1s && tiles_ok && d.with_rnn && d.R == 512 && h->rnn_cluster == 0 && single(bm) + (quad ? 232 : 375) + 35 < single(B)) {
-                CoopSerial serial(h->device, s);
-                if (serial.status != hipSuccess) return fail_hip(h, serial.status, "stream serialisation");
-                const float* P = h->packed_dev;
-                const PackedLayout& L = h->lay;
-                float* W0 = static_cast<float*>(workspace);
-                float* big = W0 + ws.big;
-                float* hall = W0 + ws.hall;
-                const float* mask = (flags & TIP_FWD_KEEP_MASK) ? keep_mask : nullptr;
-                const float ks = mask ? keep_scale : 1.f;
-                const size_t row_i = (size_t)T * d.n_imu_total, row_s = (size_t)T * d.S, row_r = (size_t)T * d.R;
-                const bool armed = rnn_uses_sentinel(d, B, T, kRnnRows4);
-                hipError_t e;
-                {
-                    StageScope sc(h, s, "fused_encoder");
-                    const long long cusl = cus, rounds_h = (bm + cusl - 1) / cusl, rounds_2 = ((bm + 1) / 2 + cusl - 1) / cusl;
-                    if (fused2_supported(d, T) && rounds_2 * 1049 < rounds_h * 527)
-                        e = launch_fused_encoder2(d, P + L.fused_off, x_imu, x_s, mask, ks, big, armed ? hall : nullptr, bm, cus, s);
-                    else
-                        e = launch_fused_encoder_h(d, P + L.fused_off, x_imu, x_s, mask, ks, nullptr, big, armed ? hall : nullptr, bm, T, cus, s);
-                    if (e != hipSuccess) return fail_hip(h, e, "fused_encoder");
-                }
-                {
-                    StageScope sc(h, s, "fused_encoder");   // (the remainder's encoder: a stage of its own in the profile, as in the two-sequence form)
-                    e = launch_fused_encoder1s(d, P + L.fused_off, x_imu + bm * row_i, x_s + bm * row_s, mask ? mask + bm * row_s : nullptr, ks,
-                                               big + bm * row_r, armed ? hall + bm * row_r : nullptr, W0 + ws.xchg, r, cus, h->f1s_parts, gd, s);
-                    if (e != hipSuccess) return fail_hip(h, e, "fused_encoder1s");
-                }
-                {
-                    StageScope sc(h, s, "rnn_recurrence");
-                    e = launch_rnn(d, big, P + L.whh_frag_off, hall, reinterpret_cast<unsigned*>(W0 + ws.flags), B, T, kRnnRows4, cus, armed, gd, s);
-                    if (e != hipSuccess) return fail_hip(h, e, "rnn_recurrence");
-                }
-                {
-                    StageScope sc(h, s, "out_linear");
-                    const bool last_only = (flags & TIP_FWD_LAST_ROW_ONLY) != 0;
-                    const float* hA = last_only && !rows ? hall + (size_t)(T - 1) * d.R : hall;
-                    const long long hlda = last_only && !rows ? (long long)T * d.R : d.R;
-                    const int hM = last_only ? B : B * T;
-                    static const bool ksplit = !(tip_env("TIP_HEAD") && tip_env("TIP_HEAD")[0] == 'o');   // TIP_HEAD=old: measurement
-                    e = hipErrorInvalidValue;
-                    if (ksplit && T % 40 == 0)
-                        e = launch_head_ksplit(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, d.R, last_only, cus, s,
-                                               rows, T);
-                    if (e == hipErrorInvalidValue)
-                        e = launch_head_gemm(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, d.R, s, rows, T);
-                    if (e != hipSuccess) return fail_hip(h, e, "out_linear");
-                }
-                h->forward_count++;
-                return TIP_OK;
-            }
-            if (single(bm) + rem < single(B) && carve_workspace(d, bm, T).total_bytes <= workspace_bytes &&
-                carve_workspace(d, r, T).total_bytes <= workspace_bytes) {
-                const size_t row_i = (size_t)T * d.n_imu_total, row_s = (size_t)T * d.S;
-                const size_t row_y = (flags & TIP_FWD_LAST_ROW_ONLY) ? (size_t)d.S : row_s;
-                const uint64_t count0 = h->forward_count;
-                int st = forward_impl(h, x_imu, x_s, y, bm, T, flags, keep_mask, keep_scale, workspace, workspace_bytes, stream, nullptr, rows);
-                if (st != TIP_OK) return st;
-                st = forward_impl(h, x_imu + bm * row_i, x_s + bm * row_s, y + bm * row_y, r, T, flags, keep_mask ? keep_mask + bm * row_s : nullptr,
-                                  keep_scale, workspace, workspace_bytes, stream, nullptr, rows ? rows + bm : nullptr);
-                if (st != TIP_OK) return st;
-                h->forward_count = count0 + 1;   // one forward, two launch sequences
-                return TIP_OK;
-            }
-        }
-    }
-    CoopSerial serial(h->device, s);   // forwards of different streams do not overlap on the device (cooperating kernels)
-    if (serial.status != hipSuccess) return fail_hip(h, serial.status, "stream serialisation");
-    const float* P = h->packed_dev;
-    const PackedLayout& L = h->lay;
-    float* W0 = static_cast<float*>(workspace);
-    float* xa = W0 + ws.xa;
-    float* xb = W0 + ws.xb;
-    float* big = W0 + ws.big;
-    float* att = W0 + ws.att;
-    float* hall = W0 + ws.hall;
-    unsigned* rflags = reinterpret_cast<unsigned*>(W0 + ws.flags);
-    const int M = B * T;
-    const float* mask = (flags & TIP_FWD_KEEP_MASK) ? keep_mask : nullptr;
-    if (!mask) keep_scale = 1.f;
-    hipError_t e;
-
-#define TIP_TRY(expr, what)                          \
-    do {                                             \
-        e = (expr);                                  \
-        if (e != hipSuccess) return fail_hip(h, e, what); \
-    } while (0)
-
-    if (reuse) {
-        // the newest row of every window -> slot (frame mod 40) of its stream's ring; while the windows still grow (T < 40) that is all
-        // the reuse form does, and the forward below is tip_forward's
-        StageScope sc(h, s, "reuse_update");
-        TIP_TRY(launch_reuse_update(d, P + L.fused_off, x_imu, x_s, reuse->cache, reuse->frame_ctr, reuse->frame_idx, B, T, s), "reuse_update");
-    }
-    int plan = reuse_full ? TIP_PLAN_FUSED2 : h->plan;
-    if (plan == TIP_PLAN_AUTO) {
-        // (a demoted handle — TIP_OPT_DEMOTED, after a lost hand-off — takes no cooperating kernel: the latency plan's GEMV recurrence is one)
-        // few streams: the latency plan up to 32 windows (0.17-0.28 ms), then ONE window on FOUR CUs up to #CUs / 4 windows (0.30 ms
-        // per step; the latency plan takes 0.36 ms for 40 windows) and on TWO up to #CUs / 2 (0.45 ms against 0.60 for one window
-        // per CU) — the window-split encoder, T = 40 only; the latency plan again where that does not apply (<= 64 shorter windows)
-        const bool f1s4 = fused2_supported(d, T) && h->f1s_parts != 2 && fused1s_quad_fits(B, cus);
-        if (!h->demoted && B <= (f1s4 ? 32 : 48) && latency_supported(d, B, T)) plan = TIP_PLAN_LATENCY;
-        else if (!h->demoted && fused2_supported(d, T) && fused1s_fits(B, cus)) plan = TIP_PLAN_FUSED1S;
-        else if (!h->demoted && latency_supported(d, B, T)) plan = TIP_PLAN_LATENCY;   // <= 64 streams: spread each window over many CUs
-        else plan = fused_supported(d, T) ? TIP_PLAN_FUSED : TIP_PLAN_GENERAL;
-    }
-    if (plan == TIP_PLAN_FUSED && h->plan == TIP_PLAN_AUTO && !reuse_full) {
-        // One window per workgroup with the hybrid row tiling (no hand-offs, 0.527 ms per round of #CUs windows at T = 40), or
-        // two windows per workgroup (80 rows = 5 full MFMA row blocks, 1.049 ms per round of 2 x #CUs windows; only the RATIO of
-        // the two matters, and #CUs is the stream's effective count): whichever
-        // needs less time for this batch.  (The pair-split plan, 0.605 ms per round with 8 hand-offs per pair, lost its
-        // place to the hybrid kernel and stays selectable for measurement.)
-        const long long cusl = cus;
-        const long long rounds_h = (B + cusl - 1) / cusl, rounds_2 = ((B + 1) / 2 + cusl - 1) / cusl;
-        plan = (fused2_supported(d, T) && rounds_2 * 1049 < rounds_h * 527) ? TIP_PLAN_FUSED2 : TIP_PLAN_FUSEDH;
-    }
-    if ((plan == TIP_PLAN_FUSED || plan == TIP_PLAN_FUSEDH) && !fused_supported(d, T)) return TIP_ERR_UNSUPPORTED_CONFIG;
-    if (plan == TIP_PLAN_FUSED2 && !fused2_supported(d, T)) return TIP_ERR_UNSUPPORTED_CONFIG;
-    if (plan == TIP_PLAN_FUSED1S && !(fused2_supported(d, T) && fused1s_fits(B, cus) && (h->f1s_parts != 4 || fused1s_quad_fits(B, cus))))
-        return TIP_ERR_UNSUPPORTED_CONFIG;
-    if (plan == TIP_PLAN_LATENCY && !latency_supported(d, B, T)) return TIP_ERR_UNSUPPORTED_CONFIG;
-    float* enc_out = xa;  // encoder output [M, D]
-    bool ih_done = false;  // the fused plan also emits the RNN input projection
-    bool rnn_done = false;
-    bool hall_armed = false;
-    int rnn_cluster = h->rnn_cluster;
-    if (rnn_cluster == 0 && h->demoted) {
-        rnn_cluster = 1;   // one workgroup per 16-window tile: no inter-workgroup hand-off
-    } else if (rnn_cluster == 0) {
-        // auto: spread one 16-window tile over as many CUs as the tile count leaves idle
-        const int ntiles = (B + kRnnTile - 1) / kRnnTile;
-        rnn_cluster = 16;
-        while (rnn_cluster > 1 && ntiles * rnn_cluster > cus) rnn_cluster >>= 1;
-        // rnn_hidden 512: four-row tiles on 4-workgroup clusters at every batch size (76 us at B = 256 against 114 for the best
-        // 16-row variant; tools/rnn_variants2.py).  TIP_RNN_ROWS4=0 keeps the 16-row kernels (measurement).
-        static const bool rows4 = !(tip_env("TIP_RNN_ROWS4") && tip_env("TIP_RNN_ROWS4")[0] == '0');
-        if (rows4 && d.R == 512) rnn_cluster = kRnnRows4;
-    }
-    bool head_done = false;
-    auto arm_hall = [&]() { return rnn_uses_sentinel(d, B, T, rnn_cluster); };
-    if (plan == TIP_PLAN_LATENCY) {
-        StageScope sc(h, s, "latency_chain");
-        LatencyHead lh{P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, d.S, (flags & TIP_FWD_LAST_ROW_ONLY) != 0, h->flow_epoch, &head_done,
-                       reinterpret_cast<unsigned long long*>(W0 + ws.flow)};
-        lh.rows = rows;
-        TIP_TRY(launch_latency_plan(d, P + L.fused_off, P + L.whh_frag_off, x_imu, x_s, mask, keep_scale, W0 + ws.lat, hall,
-                                    B, T, cus, gd, s, nullptr, cus == h->num_cus && !h->no_flow ? &lh : nullptr), "latency_chain");
-        rnn_done = true;
-    } else if (plan == TIP_PLAN_FUSED1S) {
-        StageScope sc(h, s, "fused_encoder");
-        ih_done = true;
-        hall_armed = arm_hall();
-        TIP_TRY(launch_fused_encoder1s(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, big, hall_armed ? hall : nullptr,
-                                       W0 + ws.xchg, B, cus, h->f1s_parts, gd, s), "fused_encoder1s");
-    } else if (plan == TIP_PLAN_FUSED2) {
-        StageScope sc(h, s, "fused_encoder");
-        ih_done = true;
-        hall_armed = arm_hall();
-        TIP_TRY(launch_fused_encoder2(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, big, hall_armed ? hall : nullptr, B,
-                                      cus, s, reuse_full ? reuse->cache : nullptr, reuse_full ? reuse->frame_ctr : nullptr,
-                                      reuse_full ? reuse->frame_idx : 0), "fused_encoder2");
-    } else if (plan == TIP_PLAN_FUSEDH) {
-        StageScope sc(h, s, "fused_encoder");
-        ih_done = fused_has_rnn_ih(d);
-        hall_armed = ih_done && arm_hall();
-        TIP_TRY(launch_fused_encoder_h(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, ih_done ? nullptr : xa,
-                                       ih_done ? big : nullptr, hall_armed ? hall : nullptr, B, T, cus, s),
-                "fused_encoder_h");
-    } else if (plan == TIP_PLAN_FUSED) {
-        StageScope sc(h, s, "fused_encoder");
-        ih_done = fused_has_rnn_ih(d);
-        hall_armed = ih_done && arm_hall();   // the encoder pre-fills its HALL rows
-        TIP_TRY(launch_fused_encoder(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, ih_done ? nullptr : xa,
-                                     ih_done ? big : nullptr, hall_armed ? hall : nullptr, B, T, cus, s),
-                "fused_encoder");
-    } else {
-        {
-            StageScope sc(h, s, "prologue");
-            TIP_TRY(launch_prologue(d, x_imu, x_s, mask, keep_scale, big, M, s), "prologue");
-        }
-        {
-            StageScope sc(h, s, "in_linear");
-            TIP_TRY(launch_gemm(big, d.InPad, P + L.in_lin.w_off, L.in_lin.Kpad, P + L.in_lin.b_off, nullptr, 0, xa,
-                                d.D, M, d.D, L.in_lin.Npad, 0, s), "in_linear");
-        }
-        for (int l = 0; l < d.L; ++l) {
-            const PackedLayer& pl = L.layers[l];
-            {
-                StageScope sc(h, s, "qkv_gemm");
-                TIP_TRY(linear_gemm(P, pl.qkv, xa, d.D, nullptr, 0, big, 3 * d.D, M, 0, s), "qkv_gemm");
-            }
-            {
-                StageScope sc(h, s, "attention");
-                TIP_TRY(launch_attention(d, big, att, B, T, s), "attention");
-            }
-            {
-                StageScope sc(h, s, "out_proj_gemm");
-                TIP_TRY(linear_gemm(P, pl.out, att, d.D, xa, d.D, xb, d.D, M, 2, s), "out_proj_gemm");
-            }
-            {
-                StageScope sc(h, s, "layernorm1");
-                TIP_TRY(launch_layernorm(xb, P + pl.g1_off, P + pl.be1_off, M, d.D, s), "layernorm1");
-            }
-            {
-                StageScope sc(h, s, "ffn1_gemm");
-                TIP_TRY(linear_gemm(P, pl.ff1, xb, d.D, nullptr, 0, big, d.F, M, 1, s), "ffn1_gemm");
-            }
-            {
-                StageScope sc(h, s, "ffn2_gemm");
-                TIP_TRY(linear_gemm(P, pl.ff2, big, d.F, xb, d.D, xa, d.D, M, 2, s), "ffn2_gemm");
-            }
-            {
-                StageScope sc(h, s, "layernorm2");
-                TIP_TRY(launch_layernorm(xa, P + pl.g2_off, P + pl.be2_off, M, d.D, s), "layernorm2");
-            }
-        }
-    }
-
-    const bool last_only = (flags & TIP_FWD_LAST_ROW_ONLY) != 0;
-    const float* head_in = enc_out;
-    int head_ld = d.D;
-    if (d.with_rnn && rnn_done) {
-        head_in = hall;
-        head_ld = d.R;
-    } else if (d.with_rnn) {
-        if (!ih_done) {
-            StageScope sc(h, s, "rnn_ih_gemm");
-            TIP_TRY(launch_gemm(enc_out, d.D, P + L.rnn_ih.w_off, L.rnn_ih.Kpad, P + L.rnn_ih.b_off, nullptr, 0, big,
-                                d.R, M, d.R, L.rnn_ih.Npad, 0, s), "rnn_ih_gemm");
-        }
-        {
-            StageScope sc(h, s, "rnn_recurrence");
-            TIP_TRY(launch_rnn(d, big, P + L.whh_frag_off, hall, rflags, B, T, rnn_cluster, cus, hall_armed, gd, s), "rnn_recurrence");
-        }
-        head_in = hall;
-        head_ld = d.R;
-    }
-    if (!head_done) {
-        StageScope sc(h, s, "out_linear");
-        const int Kh = d.with_rnn ? d.R : d.D;
-        // rows the projection runs on: all M, or row T-1 of every window (real_time_runner_minimal.py:150), or row rows[b] of window b
-        // (tip_forward_rows: A is then the first row, lda the row stride)
-        const float* hA = last_only && !rows ? head_in + (size_t)(T - 1) * head_ld : head_in;
-        const long long hlda = last_only && !rows ? (long long)T * head_ld : head_ld;
-        const int hM = last_only ? B : M;
-        if (plan == TIP_PLAN_LATENCY) {
-            TIP_TRY(launch_latency_head(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, s, rows, T), "out_linear");
-        } else {
-            // window lengths that are multiples of 40 (the paper's and the scaled configuration's): the register-resident
-            // kernel for both forms of the output (bit-identical last rows); everything else: head_gemm_kernel for both
-            static const bool ksplit = !(tip_env("TIP_HEAD") && tip_env("TIP_HEAD")[0] == 'o');   // TIP_HEAD=old: measurement
-            hipError_t he = hipErrorInvalidValue;
-            if (ksplit && T % 40 == 0)
-                he = launch_head_ksplit(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, Kh, last_only, cus, s, rows, T);
-            if (he == hipErrorInvalidValue)
-                he = launch_head_gemm(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, hM, d.S, Kh, s, rows, T);
-            TIP_TRY(he, "out_linear");
-        }
-    }
-#undef TIP_TRY
-    h->forward_count++;
-    return TIP_OK;
-}
-
 int tip_draw_keep_mask(float p_state, unsigned long long state_seed, float* mask, size_t n, tip_stream_t stream) {
     unsigned key = 0, thresh = 0;
     if ((!mask && n) || !state_mask_params(p_state, state_seed, &key, &thresh)) return TIP_ERR_INVALID_ARG;
@@ -1089,33 +973,15 @@ int tip_forward_dropout(tip_handle* h, const float* x_imu, const float* x_s, flo
     const int cus = effective_cus(h->num_cus, s);
     CoopSerial serial(h->device, s);
     if (serial.status != hipSuccess) return fail_hip(h, serial.status, "stream serialisation");
-    const float* P = h->packed_dev;
-    const PackedLayout& L = h->lay;
-    float* W0 = static_cast<float*>(workspace);
-    float* hall = W0 + ws.hall;
     const float* mask = (flags & TIP_FWD_KEEP_MASK) ? keep_mask : nullptr;
     if (!mask && !mthresh) keep_scale = 1.f;
     TrainDropout td = make_train_dropout(p_drop, seed);
     td.mkey = mkey;
     td.mthresh = mthresh;
-    hipError_t e;
-    bool head_done = false;
-    {
-        StageScope sc(h, s, "latency_chain");
-        const LatencyHead lh{P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, d.S, (flags & TIP_FWD_LAST_ROW_ONLY) != 0, h->flow_epoch, &head_done,
-                             reinterpret_cast<unsigned long long*>(W0 + ws.flow)};
-        e = launch_latency_plan(d, P + L.fused_off, P + L.whh_frag_off, x_imu, x_s, mask, keep_scale, W0 + ws.lat, hall, B, T, cus,
-                                h->guard(), s, &td, cus == h->num_cus && !h->no_flow ? &lh : nullptr);
-        if (e != hipSuccess) return fail_hip(h, e, "latency_chain");
-    }
-    if (!head_done) {
-        StageScope sc(h, s, "out_linear");
-        const bool last_only = (flags & TIP_FWD_LAST_ROW_ONLY) != 0;
-        const float* hA = last_only ? hall + (size_t)(T - 1) * d.R : hall;
-        const long long hlda = last_only ? (long long)T * d.R : d.R;
-        e = launch_latency_head(hA, hlda, P + L.out_frag_off, P + L.out_lin.b_off, y, d.S, last_only ? B : B * T, d.S, s);
-        if (e != hipSuccess) return fail_hip(h, e, "out_linear");
-    }
+    LaunchSeq q{h, s, cus, x_imu, x_s, mask, keep_scale, y, nullptr, B, T, flags, static_cast<float*>(workspace), ws, 0, nullptr, &td};
+    int st = run_encoder(q, SchedPart{0, B, TIP_PLAN_LATENCY, 0}, 0);
+    if (st == TIP_OK) st = run_tail(q);
+    if (st != TIP_OK) return st;
     h->forward_count++;
     return TIP_OK;
 }

@@ -160,6 +160,38 @@ struct Workspace {
     size_t total_bytes;
 };
 
+Workspace carve_workspace(const Dims& d, int B, int T);   // tip_abi.hip
+
+// ---- the forward's schedule (tip_schedule.hip): which plan(s) a batch takes.  Pure host arithmetic, no HIP call ----
+// The four measurement switches of the decision (-DTIP_MEASURE only; all true in the default build), read once:
+// TIP_AUTO_SPLIT=0, TIP_AUTO_MERGE=0, TIP_RNN_ROWS4=0, TIP_HEAD=old
+struct MeasureSwitches {
+    bool split, merge, rows4, head_ksplit;
+};
+const MeasureSwitches& measure_switches();
+struct ScheduleIn {
+    const Dims& d;
+    int B, T;
+    int cus, num_cus;                   // the stream's effective CU count (effective_cus), the device's
+    int plan, rnn_cluster, f1s_parts;   // TIP_OPT_PLAN, TIP_OPT_RNN_CLUSTER, TIP_OPT_F1S_PARTS
+    bool demoted;                       // TIP_OPT_DEMOTED
+    bool reuse_full;                    // tip_forward_reuse on full windows: ONE sequence on the two-window encoder's ring-reading form
+    size_t workspace_bytes;             // the caller's buffer: a part that would not fit its own carve-up is not split off
+};
+struct SchedPart {
+    int first, count;   // windows [first, first + count) of the batch
+    int plan;           // resolved: never AUTO, and plain FUSED only where the caller pinned it
+    int rnn_cluster;    // resolved: 1..32 or kRnnRows4 (under a shared tail: the tail's)
+};
+struct Schedule {
+    int status;         // TIP_OK, or TIP_ERR_UNSUPPORTED_CONFIG: a pinned plan does not serve the shape
+    int nparts;         // 1, or 2 = whole rounds of #CUs windows + the remainder
+    SchedPart part[2];
+    bool shared_tail;   // 2 parts in ONE launch sequence: two encoders, then one recurrence + one output projection over all B windows;
+                        // clear: every part is a launch sequence of its own over the same workspace
+};
+Schedule schedule_forward(const ScheduleIn& in);
+
 struct StageTimer {
     std::string name;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pairs;  // one (start, stop) per recorded launch

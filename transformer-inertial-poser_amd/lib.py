@@ -178,6 +178,8 @@ def load() -> ctypes.CDLL:
     lib.tip_loss_backward.argtypes = [vp, ll, vp, ll, i32, i32, i32, i32, i32, i32, vp, vp, vp, ll, vp]
     lib.tip_loss_forward_f64.argtypes = lib.tip_loss_forward.argtypes
     lib.tip_loss_backward_f64.argtypes = lib.tip_loss_backward.argtypes
+    lib.tip_debug_schedule.argtypes = [vp, i32, i32, i32, i32, sz, ctypes.POINTER(i32), i32]   # include/tip_hip_debug.h
+    lib.tip_debug_schedule.restype = i32
     for name in EXPORTS:
         if name not in ("tip_destroy", "tip_strerror", "tip_last_hip_error"):
             getattr(lib, name).restype = i32
@@ -249,6 +251,16 @@ class Handle:
         n = ctypes.c_size_t()
         self._check(self.lib.tip_workspace_bytes(self._h, B, T, ctypes.byref(n)))
         return n.value
+
+    def schedule(self, B: int, T: int, cus: int = 0, reuse_full: bool = False, workspace_bytes: Optional[int] = None) -> dict:
+        """tip_debug_schedule: what forward() would launch for B windows of length T under this handle's options, without touching a
+        device — {"nparts", "shared_tail", "rnn_cluster", "parts": [(first, count, plan), ...]}.  cus: the stream's CU count (0: the
+        handle's own; 256 without a GPU); workspace_bytes: the caller's buffer (default: what workspace_bytes(B, T) asks for)."""
+        out = (ctypes.c_int * 9)()
+        wsb = self.workspace_bytes(B, T) if workspace_bytes is None else workspace_bytes
+        self._check(self.lib.tip_debug_schedule(self._h, B, T, cus, 1 if reuse_full else 0, wsb, out, 9))
+        return {"nparts": out[0], "shared_tail": bool(out[1]), "rnn_cluster": out[2],
+                "parts": [tuple(out[3 + 3 * i: 6 + 3 * i]) for i in range(out[0])]}
 
     def max_batch(self, T: int, fp64: bool = False) -> int:
         """Largest batch one forward / forward_f64 call serves at window length T (the host chunks beyond it)."""
