@@ -31,7 +31,8 @@ extern "C" {
                              5: exact streaming reuse — tip_reuse_cache_bytes, tip_reuse_reset, tip_forward_reuse, tip_stream_frame_counter_offset,
                                 tip_stream_ingest_newest; later, backward compatible: tip_forward_rows and the staggered streaming entry points
                                 (tip_stream_attach, tip_stream_detach, tip_stream_ingest_staggered, tip_stream_consume_staggered,
-                                tip_stream_ingest_mapped, tip_stream_consume_mapped) */
+                                tip_stream_ingest_mapped, tip_stream_consume_mapped); the model shapes of the streaming entry points
+                                (tip_stream_reset_shaped) and the host override of the fed-back pose (tip_stream_history_override) */
 
 /* The library is built with -fvisibility=hidden: the functions declared here (and the measurement hooks of
  * tip_hip_debug.h) are its whole dynamic symbol table (tests/test_host_cpu.py compares `nm -D` with the two headers). */
@@ -262,6 +263,7 @@ TIP_API int tip_check(tip_handle* h, int clear);
  *          tip_stream_ingest(state, raw_imu[n,72], n, f, x_imu[n,T,90], x_s[n,T,131], stream);
  *          if (T > 0) { tip_forward(..., TIP_FWD_LAST_ROW_ONLY) -> y_last[n,131];
  *                       tip_stream_consume(state, y_last, n, f - 5, s_rest[n,111] (= s_t[3:114]), c_t[n,20], stream); }
+ *      (widths of the paper's model; x_imu [.., 72|90], x_s / y_last [.., 119|131], c_t [.., 8|20] by the buffer's shape: "model shapes" below)
  *      PyBullet FK and the SBP root-translation correction (:169-194) stay with the host.
  *      HIP graphs: kernel arguments are frozen at capture, so once the window is full (frame_idx >= 43 has been ingested, T = 40
  *      from then on) both calls accept TIP_STREAM_FRAME_AUTO for frame_idx / call_idx — "the frame after the last one ingested",
@@ -272,9 +274,32 @@ TIP_API int tip_check(tip_handle* h, int clear);
  *      (tip_forward itself may be captured the same way for any batch; the clustered recurrence's per-launch XCC-exchange words are
  *      cleared by the kernels at their end for T >= 2, so a replay never reads a previous replay's words; capture T = 1 launches of
  *      more than 64 windows only if they are not replayed.) */
+/* ---- model shapes.  The reference's runners serve four models: with or without the acc-sum feature (RTRunner / RTRunnerMin
+ *      with_acc_sum) times five or two stationary body points (RTRunner five_sbp; real_time_runner.py:39).  A state buffer has ONE
+ *      shape, fixed by its reset and kept until the next one (an attach keeps it); every streaming entry point reads it from the
+ *      buffer, so none of them takes it as an argument.  Buffer widths per shape, wherever the comments of this section say 90, 131, 20:
+ *          x_imu        [.., 72 | 90]     72 without acc-sum, 90 with
+ *          x_s, y_last,
+ *          y, y_slot    [.., 119 | 131]   108 + 3 + 4 * n_sbps: 119 with two SBPs, 131 with five
+ *          c_t          [..,   8 |  20]   4 * n_sbps
+ *          raw_imu [.., 72], s_init [.., 114], s_rest [.., 111]: the same at every shape
+ *      tip_stream_state_bytes does not depend on the shape.  tip_stream_reset is tip_stream_reset_shaped with n_sbps = 5,
+ *      with_acc_sum = 1 (the paper's model); n_sbps other than 2 or 5 gives TIP_ERR_INVALID_ARG. */
 #define TIP_STREAM_FRAME_AUTO (-1)
 TIP_API int tip_stream_state_bytes(int n_streams, size_t* bytes);
 TIP_API int tip_stream_reset(void* state, const float* s_init /* [n,114] device */, int n_streams, tip_stream_t stream);
+TIP_API int tip_stream_reset_shaped(void* state, const float* s_init /* [n,114] device */, int n_streams, int n_sbps, int with_acc_sum,
+                            tip_stream_t stream);
+/* Host override of the fed-back pose.  RTRunner with multi_sbp_terrain_and_correction feeds back a history row that is NOT the pose
+ * it returns: its two-joint IK corrects hip / knee / ankle angles first (real_time_runner.py:334-382, 483-495).  For each j < count
+ * the 6D pose columns 0 .. 107 of slot slots[j]'s NEWEST history row (the one its last consume wrote) are replaced by the 6D form
+ * (data_utils.py:182-187) of the 18 axis-angle joints q_aa[j] (= s_t[3:57] of the corrected state).  Root-velocity and c_t columns of
+ * that row, the pose average, the output filter and every other slot are untouched.  Call it after the consume of the frame it
+ * corrects and before the next ingest, on the same stream; it addresses slots, so it serves lock-step, staggered and
+ * position-mapped buffers alike, and runs between two replays of a captured frame.  slots / q_aa are DEVICE arrays; a slot outside
+ * [0, n_streams) or one that has not consumed a frame yet is skipped. */
+TIP_API int tip_stream_history_override(void* state, int n_streams, const int* slots /* [count] */, const float* q_aa /* [count,54] */,
+                                int count, tip_stream_t stream);
 TIP_API int tip_stream_window_len(int frame_idx); /* 0 while the 11-tap smoother primes (frames 0..4), then 1..40 */
 TIP_API int tip_stream_ingest(void* state, const float* raw_imu, int n_streams, int frame_idx, float* x_imu, float* x_s,
                       tip_stream_t stream);
@@ -290,7 +315,8 @@ TIP_API int tip_stream_ingest_newest(void* state, const float* raw_imu, int n_st
  *      without touching the other slots.  Each slot keeps its own frame counter f_i (in `state`; no host frame index anywhere) and a
  *      flag, attached or detached; detached is the flag's zero value, so after tip_stream_reset every slot is detached.  A NEW state
  *      buffer goes through tip_stream_reset once before its first staggered call: freshly allocated memory holds garbage flags.
- *      Windows sit in fixed 40-row slots, x_imu [n,40,90] / x_s [n,40,131]; per frame, on one stream:
+ *      Windows sit in fixed 40-row slots, x_imu [n,40,90] / x_s [n,40,131] (x_imu [n,40,72|90], x_s / y_last [n,40|-,119|131],
+ *      c_t [n,8|20], s_rest [n,111] by the buffer's shape); per frame, on one stream:
  *          tip_stream_ingest_staggered(state, raw_imu[n,72], n, x_imu, x_s, rows[n], stream);
  *              attached slot i: f_i advances, T_i = tip_stream_window_len(f_i); rows 0 .. T_i-1 of its window are what
  *              tip_stream_ingest writes for frame f_i (bit for bit), rows T_i .. 39 are zero, rows[i] = T_i - 1 (-1 while priming);
@@ -318,7 +344,8 @@ TIP_API int tip_stream_consume_staggered(void* state, const float* y_last, const
  *      int [B]: window position p (0 <= p < B) carries slot slot_at[p], and -1 (any value outside [0, n)) marks an empty position.
  *      Each slot appears AT MOST ONCE in slot_at: that is the host's duty, it is not checked on the device (a slot listed twice would
  *      advance twice in one frame).  Indexing: raw_imu, state, s_rest, c_t, y_slot and rows_slot are by SLOT ([n, *]); x_imu, x_s,
- *      rows and y are by POSITION ([B, *]).  Per frame, on one stream:
+ *      rows and y are by POSITION ([B, *]); x_imu [B,40,72|90], x_s [B,40,119|131], y / y_slot [.,119|131], c_t [n,8|20],
+ *      s_rest [n,111] by the buffer's shape.  Per frame, on one stream:
  *          tip_stream_ingest_mapped(state, raw_imu[n,72], n, slot_at, B, x_imu[B,40,90], x_s[B,40,131], rows[B], stream);
  *              position p with slot s = slot_at[p]: window p and rows[p] are bit for bit what tip_stream_ingest_staggered writes for
  *              slot s (s's state, frame counter and attached flag); an empty position, or a detached slot: zero window, rows[p] = -1.

@@ -15,9 +15,19 @@
 // root translation, which is not a model input.
 //
 // State per stream (floats, caller-owned device buffer): raw[11][72] | loc[40][72] | accs[40][18] | hist[40][131] |
-// outs[6][131] | last[54] | frame counter (int) | attached flag (int; the staggered entry points only, 0 = detached).  Frame / call counters live on the host (all streams advance in lock step); the
+// outs[6][131] | last[54] | frame counter (int) | attached flag (int; the staggered entry points only, 0 = detached) | shape word
+// (int).  Frame / call counters live on the host (all streams advance in lock step); the
 // ingest kernel also leaves the frame index in the state, so that a call with TIP_STREAM_FRAME_AUTO continues from it — kernel
 // arguments are frozen in a captured HIP graph, a counter in HBM is not.
+//
+// Shapes: the reference's runners serve four models — with or without the acc-sum feature (x_imu 90 / 72 columns; RTRunner(Min)'s
+// with_acc_sum) times five or two stationary body points (state 131 / 119 columns, c_t 20 / 8; real_time_runner.py:39).  The
+// smaller shapes live inside the same block at the same offsets (hist / outs rows are NS wide, accs is unused without acc-sum), so
+// the block size does not depend on the shape.  The shape is ONE per state buffer: tip_stream_reset(_shaped) writes it into the
+// shape word of every block (an attach keeps it), next to the frame counter and the attached flag — the three share a cache line, and
+// a kernel asks for them together: read on its own, ahead of everything else, the word cost the one-stream frame 0.8 us per kernel.
+// A workgroup reads its own block's word (block 0's for an empty position of a compact pool, which still zeroes a window of the
+// right width) and branches once into its <NS, NX> body — the window loops have compile-time trip counts.  0 is (5 SBPs, acc-sum).
 #include "tip_internal.h"
 
 namespace tip {
@@ -32,8 +42,17 @@ constexpr int OUTS = HIST + WIN * NS;         // 9632
 constexpr int LAST = OUTS + OUTN * NS;        // 10418
 constexpr int CTR = LAST + 54;                // 10472: frame index of the last ingest (int)
 constexpr int ATT = CTR + 1;                  // 10473: staggered slots: 1 = attached (int); the lock-step entry points ignore it
-constexpr int STRIDE = 10496;                 // ATT + 1 = 10474, padded to a multiple of 64
+constexpr int SHP = ATT + 1;                  // 10474: shape of the whole buffer (int): bit 0 = two SBPs (NS 119), bit 1 = no acc-sum (NX 72)
+constexpr int STRIDE = 10496;                 // SHP + 1 = 10475, padded to a multiple of 64
+constexpr int NS2 = 119;                      // 108 + 3 + 2 * 4
 }  // namespace sz
+
+// the three control words of a block, requested together: frame counter, attached flag, shape
+struct StreamWords { int ctr, att, shape; };
+__device__ __forceinline__ StreamWords stream_words(const float* S) {
+    const int* w = reinterpret_cast<const int*>(S + sz::CTR);
+    return {w[0], w[1], w[2] & 3};
+}
 
 // ---- scipy.spatial.transform.Rotation restated (fp32) -------------------------------------------------------
 // from_matrix() first replaces a non-orthogonal input by the NEAREST rotation (U V^T of its SVD), then extracts the
@@ -170,15 +189,19 @@ __host__ __device__ __forceinline__ int window_len(int frame_idx) {   // T of th
 // ---- reset: history row 0 from s_init (:45, :78-85) ----------------------------------------------------------
 // slots == nullptr: every stream b = blockIdx.x (tip_stream_reset: all detached).  Otherwise (tip_stream_attach) the block rebuilds
 // stream slots[blockIdx.x] from s_init row blockIdx.x and marks it attached, its next staggered ingest being its frame 0.
+// The shape word is set by the reset only (`shape`, the same in every block); an attach puts back what it found: a buffer has one
+// shape from reset to reset.  History row 0 is 108 + 3 columns and zeros at every shape.
 __global__ __launch_bounds__(64) void stream_reset_kernel(float* __restrict__ state, const float* __restrict__ s_init, int B,
-                                                          const int* __restrict__ slots) {
+                                                          const int* __restrict__ slots, int shape) {
     using namespace sz;
     const int tid = threadIdx.x;
     const int b = slots ? slots[blockIdx.x] : (int)blockIdx.x;
     if (b < 0 || b >= B) return;
     float* S = state + (size_t)b * STRIDE;
+    if (slots) shape = reinterpret_cast<const int*>(S + SHP)[0];   // (one wave: read before its own zeroing below, put back after it)
     for (int i = tid; i < STRIDE; i += 64) S[i] = 0.f;
     __syncthreads();
+    if (tid == 0) reinterpret_cast<int*>(S + SHP)[0] = shape;
     if (slots && tid == 0) {
         reinterpret_cast<int*>(S + CTR)[0] = -1;   // "last ingested frame": the next one is frame 0
         reinterpret_cast<int*>(S + ATT)[0] = 1;
@@ -210,20 +233,20 @@ __global__ __launch_bounds__(64) void stream_detach_kernel(float* __restrict__ s
 // (-1 while priming).  A detached stream gets a zero window and -1, and its state is not touched.
 // slot_at != nullptr (tip_stream_ingest_mapped, staggered only): block p builds window p (x_imu, x_s, rows_out by POSITION) for slot
 // slot_at[p] (state, raw_in by SLOT); a position whose entry is outside [0, n) is empty: zero window, -1.  nullptr: slot = position.
-__global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ state, const float* __restrict__ raw_in, int n,
-                                                            int f, float* __restrict__ x_imu, float* __restrict__ x_s, int T, int newest,
-                                                            int* __restrict__ rows_out, const int* __restrict__ slot_at) {
+template <int NS_, int NX_>
+__device__ __forceinline__ void stream_ingest_body(float* __restrict__ sm, float* __restrict__ loc, float* __restrict__ S, int b,
+                                                   bool listed, StreamWords w, const float* __restrict__ raw_in, int f,
+                                                   float* __restrict__ x_imu, float* __restrict__ x_s, int T, int newest,
+                                                   int* __restrict__ rows_out) {
     using namespace sz;
-    __shared__ float sm[NIMU], loc[NIMU];
+    constexpr int NS = NS_, NX = NX_;      // this shape's widths (they hide sz::NS / sz::NX, the widest shape's)
+    constexpr bool ACC = NX_ > NIMU;       // the acc-sum feature: ring accs[40][18], columns 72-89
     const int p = blockIdx.x, tid = threadIdx.x;
-    const int b = slot_at ? slot_at[p] : p;
-    const bool listed = b >= 0 && b < n;
-    float* S = state + (size_t)(listed ? b : 0) * STRIDE;
     int* ctr = reinterpret_cast<int*>(S + CTR);
     int ldw = T;   // rows between two windows of x_imu / x_s
     if (rows_out) {
-        const bool attached = listed && reinterpret_cast<const int*>(S + ATT)[0] != 0;
-        f = attached ? *ctr + 1 : 0;
+        const bool attached = listed && w.att != 0;
+        f = attached ? w.ctr + 1 : 0;
         __syncthreads();   // every thread reads before thread 0 writes
         T = attached ? window_len(f) : 0;
         ldw = WIN;
@@ -234,7 +257,7 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
         if (tid == 0) rows_out[p] = T - 1;
         if (!attached) return;
     } else if (f < 0) {   // TIP_STREAM_FRAME_AUTO: the frame after the last one ingested (every thread reads before thread 0 writes)
-        f = *ctr + 1;
+        f = w.ctr + 1;
         __syncthreads();
     }
     if (tid == 0) *ctr = f;
@@ -264,9 +287,13 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
         for (int u = 0; u < XI_IT; ++u) {
             const int i = tid + 256 * u, ic = i < (T - 1) * NX ? i : 0;
             const int t = ic / NX, c = ic - t * NX, j = k - T + 1 + t;
-            const float* pv = c < NIMU ? S + LOC + (j % WIN) * NIMU + c : S + ACCS + (j % WIN) * 18 + (c - NIMU);
-            const float x = *pv;
-            vi[u] = c < NIMU ? x : x / 15.0f;                                                            // :139-141
+            if constexpr (ACC) {
+                const float* pv = c < NIMU ? S + LOC + (j % WIN) * NIMU + c : S + ACCS + (j % WIN) * 18 + (c - NIMU);
+                const float x = *pv;
+                vi[u] = c < NIMU ? x : x / 15.0f;                                                        // :139-141
+            } else {
+                vi[u] = S[LOC + (j % WIN) * NIMU + c];
+            }
         }
 #pragma unroll
         for (int u = 0; u < XS_IT; ++u)
@@ -275,7 +302,7 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
         for (int u = 0; u < XI_IT; ++u)
             if (tid + 256 * u < (T - 1) * NX) xi[tid + 256 * u] = vi[u];
         }
-        if (tid < 18) {   // all (up to 39) loads first, then the sum in the reference's order: one round trip, not one per frame
+        if (ACC && tid < 18) {   // all (up to 39) loads first, then the sum in the reference's order: one round trip, not one per frame
             float av[WIN - 1];
 #pragma unroll
             for (int u = 0; u < WIN - 1; ++u) {
@@ -345,10 +372,36 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
         S[LOC + (k % WIN) * NIMU + tid] = loc[tid];
         xin[tid] = loc[tid];
     }
-    if (tid < 18) {   // acc-sum feature over the (<= 40-frame) window: the older frames' partial + this frame, added last (:136)
+    if (ACC && tid < 18) {   // acc-sum feature over the (<= 40-frame) window: the older frames' partial + this frame, added last (:136)
         const float acc = acc_old + loc[54 + tid];
         S[ACCS + (k % WIN) * 18 + tid] = acc;
         xin[NIMU + tid] = acc / 15.0f;                        // :139-141
+    }
+}
+
+__global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ state, const float* __restrict__ raw_in, int n,
+                                                            int f, float* __restrict__ x_imu, float* __restrict__ x_s, int T, int newest,
+                                                            int* __restrict__ rows_out, const int* __restrict__ slot_at) {
+    __shared__ float sm[sz::NIMU], loc[sz::NIMU];
+    const int b = slot_at ? slot_at[blockIdx.x] : (int)blockIdx.x;
+    const bool listed = b >= 0 && b < n;
+    float* S = state + (size_t)(listed ? b : 0) * sz::STRIDE;
+    const StreamWords w = stream_words(S);
+    // The paper's shape is tested on its own and marked likely, so that its body follows the prologue in the code, where the
+    // instruction fetch already is: as one four-way switch the compiler put it behind a 13-KB jump, one more instruction miss for a
+    // cold one-stream launch.  (The empty asm keeps the second test from being merged with the first into that switch again.)
+    if (__builtin_expect(w.shape == 0, 1)) {
+        stream_ingest_body<sz::NS, sz::NX>(sm, loc, S, b, listed, w, raw_in, f, x_imu, x_s, T, newest, rows_out);
+        return;
+    }
+    int other = w.shape;
+    asm volatile("" : "+s"(other));
+    if (other == 1) {
+        stream_ingest_body<sz::NS2, sz::NX>(sm, loc, S, b, listed, w, raw_in, f, x_imu, x_s, T, newest, rows_out);
+    } else if (other == 2) {
+        stream_ingest_body<sz::NS, sz::NIMU>(sm, loc, S, b, listed, w, raw_in, f, x_imu, x_s, T, newest, rows_out);
+    } else {
+        stream_ingest_body<sz::NS2, sz::NIMU>(sm, loc, S, b, listed, w, raw_in, f, x_imu, x_s, T, newest, rows_out);
     }
 }
 
@@ -358,35 +411,19 @@ __global__ __launch_bounds__(256) void stream_ingest_kernel(float* __restrict__ 
 // slot_at != nullptr (tip_stream_consume_mapped): block p consumes y_last[p] / rows[p] (by POSITION) for slot slot_at[p] (state,
 // s_rest, c_out by SLOT), after copying them to y_slot[slot] / rows_slot[slot] when given; an empty position (entry outside
 // [0, n_slots)) does nothing.  nullptr: slot = position.
-__global__ __launch_bounds__(192) void stream_consume_kernel(float* __restrict__ state, const float* __restrict__ y_last, int n_slots,
-                                                             int k, float* __restrict__ s_rest, float* __restrict__ c_out,
-                                                             const int* __restrict__ rows, const int* __restrict__ slot_at,
-                                                             float* __restrict__ y_slot, int* __restrict__ rows_slot) {
+// The kernel is one body for every shape except its first phase (stream_consume_filter: the NS-wide row, its ring and the SBP
+// columns, where the width is a compile-time constant); the pose half behind the first barrier takes the width as a value — it
+// enters one address computation — so that its rotation code, whose small matrices the compiler keeps in LDS, exists once.
+template <int NS_>
+__device__ __forceinline__ void stream_consume_filter(float* __restrict__ s, float* __restrict__ S, const float* __restrict__ y_row,
+                                                      float* __restrict__ c_row, int k, int tid) {
     using namespace sz;
-    __shared__ float s[NS], aa[54], rootv[3];
-    const int p = blockIdx.x, tid = threadIdx.x;
-    const int b = slot_at ? slot_at[p] : p;
-    if (slot_at) {
-        if (b < 0 || b >= n_slots) return;
-        if (y_slot && tid < NS) y_slot[(size_t)b * NS + tid] = y_last[(size_t)p * NS + tid];
-        if (rows_slot && tid == 0) rows_slot[b] = rows[p];
-    }
-    if (rows && rows[p] < 0) return;
-    float* S = state + (size_t)b * STRIDE;
+    constexpr int NS = NS_;
     const float coeff[OUTN] = {0.07776f, 0.1296f, 0.216f, 0.36f, 0.6f, 1.0f};   // 0.6^(5..0) (:57)
     const float csum = 0.07776f + 0.1296f + 0.216f + 0.36f + 0.6f + 1.0f;
-    if (k < 0) k = *reinterpret_cast<const int*>(S + CTR) - 5;   // TIP_STREAM_FRAME_AUTO: the call that belongs to the last ingested frame
     const int n = k + 1;
-    // requested up front, with the prediction row: the previous pose / root velocity (the averaging below) and the root IMU rotation
-    // — behind the first barrier each was one more exposed round trip
-    float last3[3] = {0.f, 0.f, 0.f}, rr[9];
-    if (tid >= 1 && tid < 18 && k > 0)
-        for (int e = 0; e < 3; ++e) last3[e] = S[LAST + (tid - 1) * 3 + e];
-    if (tid >= 64 && tid < 67 && k > 0) last3[0] = S[LAST + 51 + (tid - 64)];
-    if (tid == 0)
-        for (int e = 0; e < 9; ++e) rr[e] = S[LOC + (k % WIN) * NIMU + e];
     if (tid < NS) {
-        const float y = y_last[(size_t)p * NS + tid];
+        const float y = y_row[tid];
         S[OUTS + (k % OUTN) * NS + tid] = y;
         float v;
         if (n >= OUTN) {
@@ -401,14 +438,48 @@ __global__ __launch_bounds__(192) void stream_consume_kernel(float* __restrict__
         }
         if (tid >= 111) {
             const int ci = tid - 111;
-            v = (ci & 3) == 0 ? (v > 0.f ? 1.f : 0.f) : v / 5.0f;      // :107-110
+            v = (ci & 3) == 0 ? (v > 0.f ? 1.f : 0.f) : v / 5.0f;      // :107-110 (real_time_runner.py:323-330: 4 columns per SBP)
             // reference quirk: with fewer than 6 buffered rows the decode happens IN PLACE in the buffered row (:99)
             if (n < OUTN) S[OUTS + (k % OUTN) * NS + tid] = v;
-            c_out[(size_t)b * 20 + ci] = v;
+            c_row[ci] = v;
         }
         s[tid] = v;
     }
+}
+
+__global__ __launch_bounds__(192) void stream_consume_kernel(float* __restrict__ state, const float* __restrict__ y_last, int n_slots,
+                                                             int k, float* __restrict__ s_rest, float* __restrict__ c_out,
+                                                             const int* __restrict__ rows, const int* __restrict__ slot_at,
+                                                             float* __restrict__ y_slot, int* __restrict__ rows_slot) {
+    using namespace sz;
+    __shared__ float s[NS], aa[54], rootv[3];
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int b = slot_at ? slot_at[p] : p;
+    if (slot_at && (b < 0 || b >= n_slots)) return;
+    float* S = state + (size_t)b * STRIDE;
+    const StreamWords w = stream_words(S);
+    const int row = rows ? rows[p] : 0;
+    const int ns = (w.shape & 1) ? NS2 : NS;   // this buffer's state width; ns - 111 SBP columns (20 / 8)
+    if (slot_at) {
+        if (y_slot && tid < ns) y_slot[(size_t)b * ns + tid] = y_last[(size_t)p * ns + tid];
+        if (rows_slot && tid == 0) rows_slot[b] = row;
+    }
+    if (row < 0) return;
+    if (k < 0) k = w.ctr - 5;   // TIP_STREAM_FRAME_AUTO: the call that belongs to the last ingested frame
+    // requested up front, with the prediction row: the previous pose / root velocity (the averaging below) and the root IMU rotation
+    // — behind the first barrier each was one more exposed round trip
+    float last3[3] = {0.f, 0.f, 0.f}, rr[9];
+    if (tid >= 1 && tid < 18 && k > 0)
+        for (int e = 0; e < 3; ++e) last3[e] = S[LAST + (tid - 1) * 3 + e];
+    if (tid >= 64 && tid < 67 && k > 0) last3[0] = S[LAST + 51 + (tid - 64)];
+    if (tid == 0)
+        for (int e = 0; e < 9; ++e) rr[e] = S[LOC + (k % WIN) * NIMU + e];
+    if (__builtin_expect(ns == NS, 1))
+        stream_consume_filter<NS>(s, S, y_last + (size_t)p * NS, c_out + (size_t)b * (NS - 111), k, tid);
+    else
+        stream_consume_filter<NS2>(s, S, y_last + (size_t)p * NS2, c_out + (size_t)b * (NS2 - 111), k, tid);
     __syncthreads();
+    float* hrow = S + HIST + ((k + 1) % WIN) * ns;   // the history row this call feeds back
     if (tid < 18) {
         float rv[3];
         if (tid == 0) {   // root rotation comes from the IMU, not from the prediction (:160-162)
@@ -436,20 +507,44 @@ __global__ __launch_bounds__(192) void stream_consume_kernel(float* __restrict__
         for (int e = 0; e < 3; ++e) aa[tid * 3 + e] = rv[e];
         float o6[6];
         rotvec_to_6d(rv, o6);   // :78-85
-        for (int e = 0; e < 6; ++e) S[HIST + ((k + 1) % WIN) * NS + tid * 6 + e] = o6[e];
+        for (int e = 0; e < 6; ++e) hrow[tid * 6 + e] = o6[e];
     } else if (tid >= 64 && tid < 67) {
         const int e = tid - 64;
         float v = s[108 + e];
         if (k > 0) v = (v + last3[0]) * 0.5f;
         S[LAST + 51 + e] = v;
         rootv[e] = v;
-        S[HIST + ((k + 1) % WIN) * NS + 108 + e] = v;
-    } else if (tid >= 128 && tid < 148) {
-        S[HIST + ((k + 1) % WIN) * NS + 111 + (tid - 128)] = s[111 + (tid - 128)];
+        hrow[108 + e] = v;
+    } else if (tid >= 128 && tid < 128 + ns - 111) {
+        hrow[111 + (tid - 128)] = s[111 + (tid - 128)];
     }
     __syncthreads();
     // s_t[3:114]: 54 axis-angles, root velocity, 54 zeros
     if (tid < 111) s_rest[(size_t)b * 111 + tid] = tid < 54 ? aa[tid] : (tid < 57 ? rootv[tid - 54] : 0.f);
+}
+
+// ---- host override of the fed-back pose: columns 0-107 of the NEWEST history row of the listed slots ------------------------
+// RTRunner with multi_sbp_terrain_and_correction feeds back a pose its two-joint IK corrected on the host, not the pose it returns
+// (real_time_runner.py:483-495: record_state_aa_and_c(st_hist_copy, c_t)).  Block j rewrites, for slot slots[j], the 6D columns of
+// the row the last consume wrote (call k = frame counter - 5 -> hist[(k + 1) % 40]) from the 18 axis-angle joints q_aa[j]
+// (data_utils.py:182-187).  Root velocity and c_t columns, last[54], the output ring and every other slot are not touched; a slot
+// that has not consumed a frame yet (k < 0) or lies outside [0, B) is skipped.
+__global__ __launch_bounds__(64) void stream_history_override_kernel(float* __restrict__ state, int B, const int* __restrict__ slots,
+                                                                     const float* __restrict__ q_aa) {
+    using namespace sz;
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const int b = slots[j];
+    if (b < 0 || b >= B) return;
+    float* S = state + (size_t)b * STRIDE;
+    const StreamWords w = stream_words(S);
+    const int ns = (w.shape & 1) ? NS2 : NS;
+    const int k = w.ctr - 5;
+    if (k < 0 || tid >= 18) return;
+    const float* q = q_aa + (size_t)j * 54 + tid * 3;
+    const float rv[3] = {q[0], q[1], q[2]};
+    float o6[6];
+    rotvec_to_6d(rv, o6);
+    for (int e = 0; e < 6; ++e) S[HIST + ((k + 1) % WIN) * ns + tid * 6 + e] = o6[e];
 }
 
 }  // namespace tip
@@ -464,11 +559,24 @@ int tip_stream_state_bytes(int n_streams, size_t* bytes) {
     return TIP_OK;
 }
 
-int tip_stream_reset(void* state, const float* s_init, int n_streams, tip_stream_t stream) {
-    if (!state || !s_init || n_streams < 0) return TIP_ERR_INVALID_ARG;
+int tip_stream_reset_shaped(void* state, const float* s_init, int n_streams, int n_sbps, int with_acc_sum, tip_stream_t stream) {
+    if (!state || !s_init || n_streams < 0 || (n_sbps != 2 && n_sbps != 5)) return TIP_ERR_INVALID_ARG;
     if (n_streams == 0) return TIP_OK;
+    const int shape = (n_sbps == 2 ? 1 : 0) | (with_acc_sum ? 0 : 2);
     hipLaunchKernelGGL(stream_reset_kernel, dim3(n_streams), dim3(64), 0, static_cast<hipStream_t>(stream),
-                       static_cast<float*>(state), s_init, n_streams, nullptr);
+                       static_cast<float*>(state), s_init, n_streams, nullptr, shape);
+    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+}
+
+int tip_stream_reset(void* state, const float* s_init, int n_streams, tip_stream_t stream) {
+    return tip_stream_reset_shaped(state, s_init, n_streams, 5, 1, stream);
+}
+
+int tip_stream_history_override(void* state, int n_streams, const int* slots, const float* q_aa, int count, tip_stream_t stream) {
+    if (!state || n_streams < 0 || count < 0 || (count > 0 && (!slots || !q_aa))) return TIP_ERR_INVALID_ARG;
+    if (count == 0) return TIP_OK;
+    hipLaunchKernelGGL(stream_history_override_kernel, dim3(count), dim3(64), 0, static_cast<hipStream_t>(stream),
+                       static_cast<float*>(state), n_streams, slots, q_aa);
     return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 
@@ -516,7 +624,7 @@ int tip_stream_attach(void* state, int n_streams, const int* slots, const float*
     if (!state || n_streams < 0 || count < 0 || (count > 0 && (!slots || !s_init))) return TIP_ERR_INVALID_ARG;
     if (count == 0) return TIP_OK;
     hipLaunchKernelGGL(stream_reset_kernel, dim3(count), dim3(64), 0, static_cast<hipStream_t>(stream), static_cast<float*>(state),
-                       s_init, n_streams, slots);
+                       s_init, n_streams, slots, 0);
     return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 

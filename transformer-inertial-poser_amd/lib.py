@@ -39,7 +39,7 @@ EXPORTS = (
     "tip_spin_timeouts", "tip_check", "tip_stream_state_bytes", "tip_stream_reset", "tip_stream_window_len", "tip_stream_ingest", "tip_stream_consume",
     "tip_reuse_cache_bytes", "tip_reuse_reset", "tip_forward_reuse", "tip_stream_frame_counter_offset", "tip_stream_ingest_newest",
     "tip_forward_rows", "tip_stream_attach", "tip_stream_detach", "tip_stream_ingest_staggered", "tip_stream_consume_staggered",
-    "tip_stream_ingest_mapped", "tip_stream_consume_mapped",
+    "tip_stream_ingest_mapped", "tip_stream_consume_mapped", "tip_stream_reset_shaped", "tip_stream_history_override",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
     "tip_train_bytes_f64", "tip_train_forward_f64", "tip_train_backward_f64",
     "tip_combine_frames", "tip_combine_scratch_bytes", "tip_combine_sequence", "tip_gather_windows",
@@ -143,6 +143,8 @@ def load() -> ctypes.CDLL:
     lib.tip_check.argtypes = [vp, i32]
     lib.tip_stream_state_bytes.argtypes = [i32, ctypes.POINTER(sz)]
     lib.tip_stream_reset.argtypes = [vp, vp, i32, vp]
+    lib.tip_stream_reset_shaped.argtypes = [vp, vp, i32, i32, i32, vp]
+    lib.tip_stream_history_override.argtypes = [vp, i32, vp, vp, i32, vp]
     lib.tip_stream_window_len.argtypes = [i32]
     lib.tip_stream_ingest.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     lib.tip_stream_consume.argtypes = [vp, vp, i32, i32, vp, vp, vp]

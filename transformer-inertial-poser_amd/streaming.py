@@ -42,6 +42,11 @@ steady-state price from its first frame on.  No frame index anywhere: use_graph=
 StaggeredStreamingEngine(..., compact=True) makes that cost follow the load instead: the attached slots are packed into window
 positions 0 .. k-1 (include/tip_hip.h: tip_stream_ingest_mapped) and the forward runs on the top of the step of AUTO's cost staircase
 that holds them (POOL_LADDER below).
+
+Model shapes (stream_shape below): the engines serve the four models the reference's runners accept — with or without the acc-sum
+feature (x_imu 90 / 72 columns) times five or two stationary body points (size_s 131 / 119, c_t 20 / 8 columns) — and take the
+shape from the model.  override_history(q, slots): RTRunner with multi_sbp_terrain_and_correction feeds back a pose its host-side
+IK corrected, not the pose it returns (real_time_runner.py:483-495); the host hands that pose back between two frames.
 """
 from __future__ import annotations
 
@@ -86,6 +91,20 @@ def pool_bucket(k: int, ladder) -> int:
     return ladder[bisect.bisect_left(ladder, k)]
 
 
+SHAPES = ((72, 119), (72, 131), (90, 119), (90, 131))     # (x_imu columns, size_s) the streaming kernels serve
+
+
+def stream_shape(model):
+    """(n_sbps, with_acc_sum) of a model the streaming engines can serve: input_size_imu 72 (six IMUs), size_s = 111 + 4 * n_sbps
+    with 2 or 5 stationary body points, with or without the 18 acc-sum columns.  Anything else raises ValueError."""
+    n_imu, size_s, acc = int(model.input_size_imu), int(model.size_s), bool(model.with_acc_sum)
+    if n_imu != 72 or size_s not in (119, 131):
+        raise ValueError(f"tip_amd streaming engines serve x_imu / x_s widths {' | '.join(f'{a} / {b}' for a, b in SHAPES)} "
+                         "(input_size_imu 72, with or without acc-sum; size_s 119 or 131: two or five stationary body points); "
+                         f"this model has input_size_imu {n_imu}, with_acc_sum {acc}, size_s {size_s}")
+    return (size_s - 111) // 4, acc
+
+
 class SlotPositions:
     """Window positions of a compact pool (host only): the k attached slots hold positions 0 .. k-1, each exactly once.  A slot that
     attaches takes position k; one that detaches leaves its hole to the slot at the last position; re-attaching an attached slot
@@ -127,6 +146,8 @@ class SlotPositions:
 class StreamingEngine:
     def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False):
         self.model = model
+        self.n_sbps, self.with_acc_sum = stream_shape(model)
+        self.nx, self.ns, self.nc = 72 + (18 if self.with_acc_sum else 0), int(model.size_s), 4 * self.n_sbps
         self.use_graph = bool(use_graph)
         self.reuse = reuse          # True / False / "auto" (resolved below, once the stream count is known)
         self._graph = None
@@ -148,10 +169,10 @@ class StreamingEngine:
         self._check(self.lib.tip_stream_state_bytes(self.n, ctypes.byref(nbytes)))
         self.state = torch.empty(max(nbytes.value, 4), dtype=torch.uint8, device=self.device)
         self.s_init = s_init.to(self.device).contiguous()
-        self.x_imu = torch.empty((self.n, 40, 90), dtype=torch.float32, device=self.device)
-        self.x_s = torch.empty((self.n, 40, 131), dtype=torch.float32, device=self.device)
+        self.x_imu = torch.empty((self.n, 40, self.nx), dtype=torch.float32, device=self.device)
+        self.x_s = torch.empty((self.n, 40, self.ns), dtype=torch.float32, device=self.device)
         self.s_rest = torch.empty((self.n, 111), dtype=torch.float32, device=self.device)
-        self.c_t = torch.empty((self.n, 20), dtype=torch.float32, device=self.device)
+        self.c_t = torch.empty((self.n, self.nc), dtype=torch.float32, device=self.device)
         self.raw = torch.empty((self.n, 72), dtype=torch.float32, device=self.device)    # static input of the captured graph
         self._graph_ws = None
         self._graph_y = None
@@ -184,6 +205,12 @@ class StreamingEngine:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    def _reset_state(self, s_init):
+        """tip_stream_reset_shaped: every block rebuilt from its s_init row, the buffer's shape recorded for the kernels."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tip_stream_reset_shaped(self.state.data_ptr(), s_init.data_ptr(), self.n, self.n_sbps,
+                                                         1 if self.with_acc_sum else 0, self._stream()))
+
     def reset(self):
         self.frame = 0
         self._graph = None
@@ -191,8 +218,52 @@ class StreamingEngine:
         self._y_last = None
         if self._ring is not None:
             self.model.reuse_reset(self._ring)
+        self._reset_state(self.s_init)
+
+    # ---- host override of the fed-back pose ----------------------------------------------------------------------------------------
+    def _override_ready(self, idx):
+        """The slots of `idx` have consumed a frame (lock-step: all of them, from frame 5 on)."""
+        if self.frame < 6:
+            raise RuntimeError("tip_amd.StreamingEngine.override_history: no frame has been consumed yet (step() returns None while "
+                               "the smoother primes: frames 0 .. 4)")
+
+    def override_history(self, q, slots=None):
+        """Replace the pose the last step() fed back — columns 0 .. 107 of the newest history row — by the host's corrected one.
+        q: [len(slots), 54] (root + 17 joints, axis-angle: s_t[3:57] of the reference) or [len(slots), 114] (a full qdq, of which
+        [3:57] is taken); host or CUDA tensor.  slots: slot indices, None = all.  Call it after step() returned the frame it corrects
+        and before the next step() (RTRunner's multi_sbp_terrain_and_correction: real_time_runner.py:483-495 feeds back
+        st_hist_copy, the IK-corrected copy of the pose it returns).  Root velocity, c_t, the pose average and the output filter are
+        not touched.  One small launch on the current stream; with use_graph=True it runs between two replays, nothing is
+        re-captured."""
+        name = type(self).__name__
+        if slots is None:
+            idx = list(range(self.n))
+        else:
+            try:
+                idx = [int(i) for i in slots]
+            except TypeError:
+                raise ValueError(f"tip_amd.{name}.override_history: slots must be a list of slot indices") from None
+            if any(i < 0 or i >= self.n for i in idx):
+                raise ValueError(f"tip_amd.{name}.override_history: slot index outside [0, {self.n})")
+            if len(set(idx)) != len(idx):
+                raise ValueError(f"tip_amd.{name}.override_history: duplicate slot index")
+        q = torch.as_tensor(q, dtype=torch.float32)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.dim() != 2 or q.shape[0] != len(idx) or q.shape[1] not in (54, 114):
+            raise ValueError(f"tip_amd.{name}.override_history: q is [len(slots), 54] (axis-angle root + 17 joints) or "
+                             f"[len(slots), 114] (qdq); got {tuple(q.shape)} for {len(idx)} slots")
+        if q.shape[1] == 114:
+            q = q[:, 3:57]
+        self._override_ready(idx)
+        if not idx:
+            return
         with torch.cuda.device(self.device):
-            self._check(self.lib.tip_stream_reset(self.state.data_ptr(), self.s_init.data_ptr(), self.n, self._stream()))
+            to_dev = (lambda t: t.to(self.device, non_blocking=True) if t.is_cuda else t.pin_memory().to(self.device, non_blocking=True))
+            q = to_dev(q.contiguous()).contiguous()
+            sl = to_dev(torch.tensor(idx, dtype=torch.int32))
+            self._check(self.lib.tip_stream_history_override(self.state.data_ptr(), self.n, sl.data_ptr(), q.data_ptr(), len(idx),
+                                                             self._stream()))
 
     def _poll_handoff(self):
         """Graph mode: tip_forward's entry check never runs during a replay, so the engine reads the hand-off word itself."""
@@ -268,8 +339,8 @@ class StreamingEngine:
             self.frame += 1
             if T == 0:
                 return None
-            x_imu = self.x_imu.view(-1)[: self.n * T * 90].view(self.n, T, 90)
-            x_s = self.x_s.view(-1)[: self.n * T * 131].view(self.n, T, 131)
+            x_imu = self.x_imu.view(-1)[: self.n * T * self.nx].view(self.n, T, self.nx)
+            x_s = self.x_s.view(-1)[: self.n * T * self.ns].view(self.n, T, self.ns)
             demotions = self.model.demotions + self.model.flow_demotions
             if self.reuse:
                 try:
@@ -305,7 +376,8 @@ class StaggeredStreamingEngine(StreamingEngine):
         eng.detach([3])                                    # slot 3 stops (its state is kept, its rows are skipped)
         eng.attach([3], s_init_rows)                       # slot 3 restarts at its frame 0 from s_init_rows [1,114]
 
-    step() returns s_rest [n,111], c_t [n,20], y_last [n,131], T (int32 [n]: the slot's window length this frame, 0 while priming
+    step() returns s_rest [n,111], c_t [n,20], y_last [n,131] (c_t [n,8], y_last [n,119] for a two-SBP model), T (int32 [n]: the
+    slot's window length this frame, 0 while priming
     or detached) and valid (bool [n]: the slot produced a row this frame).  Rows of slots that are not valid are NaN in y_last and
     unchanged in s_rest / c_t.  A frame is ingest_staggered -> forward_rows -> consume_staggered with no frame index, so with
     use_graph=True it is captured once, at the first step, and replayed from then on; attach / detach run between replays.
@@ -393,8 +465,8 @@ class StaggeredStreamingEngine(StreamingEngine):
         self._graph = None
         self._graph_refs = None
         self._y_last = None
-        with torch.cuda.device(self.device):
-            self._check(self.lib.tip_stream_reset(self.state.data_ptr(), self.s_cur.data_ptr(), self.n, self._stream()))
+        self._attach_frame = [0] * self.n       # engine frame at which the slot was last attached (override_history: its age)
+        self._reset_state(self.s_cur)
         if self.compact:
             self._graphs = {}
             self._pending_attach = dict.fromkeys(i for i in range(self.n) if self._attached[i])   # (re-attached by the next step)
@@ -413,6 +485,8 @@ class StaggeredStreamingEngine(StreamingEngine):
             raise ValueError("tip_amd.StaggeredStreamingEngine.attach: one s_init row [114] per slot")
         if not idx:
             return
+        for i in idx:
+            self._attach_frame[i] = self.frame
         if self.compact:            # host only: the device work goes with the next step's single upload (_flush)
             self.s_host[idx] = rows
             for i in idx:
@@ -441,6 +515,14 @@ class StaggeredStreamingEngine(StreamingEngine):
         with torch.cuda.device(self.device):
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
             self._check(self.lib.tip_stream_detach(self.state.data_ptr(), self.n, sl.data_ptr(), len(idx), self._stream()))
+
+    def _override_ready(self, idx):
+        for i in idx:
+            if not self._attached[i]:
+                raise RuntimeError(f"tip_amd.StaggeredStreamingEngine.override_history: slot {i} is detached")
+            if self.frame - self._attach_frame[i] < 6:
+                raise RuntimeError(f"tip_amd.StaggeredStreamingEngine.override_history: slot {i} has not consumed a frame yet (its "
+                                   "first five frames prime the smoother)")
 
     @property
     def attached(self):
