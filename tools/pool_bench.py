@@ -67,7 +67,8 @@ def main():
         def churn_step(i):
             det = [int(s) for s in rng.choice(churn.positions, 10, replace=False)]
             churn.detach(det)
-            free = [s for s in range(N) if not churn._attached[s]]
+            attached = churn.attached
+            free = [s for s in range(N) if not attached[s]]
             att = [int(s) for s in rng.choice(free, 10, replace=False)]
             churn.attach(att, s_init[att])
             churn.step(fr[i % 8])

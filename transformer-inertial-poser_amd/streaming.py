@@ -143,14 +143,45 @@ class SlotPositions:
         return True
 
 
-class StreamingEngine:
-    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False):
+
+def slot_list(slots, n: int, who: str) -> list:
+    """`slots` as a list of ints, each in [0, n) and at most once; anything else is a ValueError in `who`'s name."""
+    try:
+        idx = [int(i) for i in slots]
+    except TypeError:
+        raise ValueError(f"tip_amd.{who}: slots must be a list of slot indices") from None
+    if any(i < 0 or i >= n for i in idx):
+        raise ValueError(f"tip_amd.{who}: slot index outside [0, {n})")
+    if len(set(idx)) != len(idx):
+        raise ValueError(f"tip_amd.{who}: duplicate slot index")
+    return idx
+
+
+def stage_image(n: int, positions, attach, detach, s_rows):
+    """What a compact pool hands the device between two frames, as ONE int32 array: the position map (words 0 .. n-1: position ->
+    slot, -1: empty), the slots to attach, the detached slots as int64 (8-byte aligned) and the attached slots' s_init rows (s_rows
+    [len(attach), 114] float32, bit-cast).  Returns (image, (o_attach, o_detach, o_rows)), offsets in words."""
+    o_det = (n + len(attach) + 1) // 2 * 2
+    o_rows = o_det + 2 * len(detach)
+    h = np.empty(o_rows + 114 * len(attach), dtype=np.int32)
+    h[:n] = -1
+    h[: len(positions)] = positions
+    h[n: n + len(attach)] = attach
+    h[o_det: o_rows] = np.asarray(detach, dtype=np.int64).view(np.int32)
+    h[o_rows:] = np.ascontiguousarray(s_rows, dtype=np.float32).reshape(-1).view(np.int32)
+    return h, (n, o_det, o_rows)
+
+
+class _StreamBase:
+    """What both engines share: shape, state block, frame buffers, the graph cache and the hand-off contract.  A subclass allocates
+    its own in _allocate() (once, before the first reset()), says what a lost hand-off does to it (_reprime, _REPRIMED) and supplies
+    the forward that warms a capture up (_warm_forward) and the frame that is captured (_captured_frame)."""
+
+    def __init__(self, model, s_init: torch.Tensor, use_graph: bool):
         self.model = model
         self.n_sbps, self.with_acc_sum = stream_shape(model)
         self.nx, self.ns, self.nc = 72 + (18 if self.with_acc_sum else 0), int(model.size_s), 4 * self.n_sbps
         self.use_graph = bool(use_graph)
-        self.reuse = reuse          # True / False / "auto" (resolved below, once the stream count is known)
-        self._graph = None
         self.lib = _lib.load()
         s_init = torch.as_tensor(s_init, dtype=torch.float32)
         if s_init.dim() == 1:
@@ -174,10 +205,135 @@ class StreamingEngine:
         self.s_rest = torch.empty((self.n, 111), dtype=torch.float32, device=self.device)
         self.c_t = torch.empty((self.n, self.nc), dtype=torch.float32, device=self.device)
         self.raw = torch.empty((self.n, 72), dtype=torch.float32, device=self.device)    # static input of the captured graph
-        self._graph_ws = None
-        self._graph_y = None
-        self._ring = None
-        self._ctr_ptr = None
+        # captured frames by key (None: the one frame of a lock-step or plain staggered engine; a compact pool: one per bucket), each
+        # (graph, workspace, packed weight image, y_last): the graph and what its kernels point at
+        self._graphs, self.captures = {}, 0
+        self._graph_ws = self._graph_y = None      # the engine's own, sized for n, shared by every entry and kept across reset()
+        self._allocate()
+        self.reset()
+
+    def _check(self, status: int):
+        if status < 0:
+            raise _lib.TipStatusError(status, self.lib.tip_strerror(status).decode())
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _to_dev(self, t):
+        """Host -> device without a synchronising copy from pageable memory (an attach between two frames must not drain the queue)."""
+        return t.to(self.device, non_blocking=True) if t.is_cuda else t.pin_memory().to(self.device, non_blocking=True)
+
+    def _reset_state(self, s_init):
+        """tip_stream_reset_shaped: every block rebuilt from its s_init row, the buffer's shape recorded for the kernels."""
+        with torch.cuda.device(self.device):
+            self._check(self.lib.tip_stream_reset_shaped(self.state.data_ptr(), s_init.data_ptr(), self.n, self.n_sbps,
+                                                         1 if self.with_acc_sum else 0, self._stream()))
+
+    def _forget(self):
+        """Frame counter back to 0, every captured frame dropped."""
+        self.frame = 0
+        self._graphs = {}
+        self._y_last = None
+
+    # the single captured frame and what it points at; None before the capture and after reset() or a lost hand-off
+    _graph = property(lambda self: self._graphs[None][0] if None in self._graphs else None)
+    _graph_refs = property(lambda self: self._graphs[None][1:] if None in self._graphs else None)
+
+    # ---- host override of the fed-back pose ----------------------------------------------------------------------------------------
+    def override_history(self, q, slots=None):
+        """Replace the pose the last step() fed back — columns 0 .. 107 of the newest history row — by the host's corrected one.
+        q: [len(slots), 54] (root + 17 joints, axis-angle: s_t[3:57] of the reference) or [len(slots), 114] (a full qdq, of which
+        [3:57] is taken); host or CUDA tensor.  slots: slot indices, None = all.  Call it after step() returned the frame it corrects
+        and before the next step() (RTRunner's multi_sbp_terrain_and_correction: real_time_runner.py:483-495 feeds back
+        st_hist_copy, the IK-corrected copy of the pose it returns).  Root velocity, c_t, the pose average and the output filter are
+        not touched.  One small launch on the current stream; with use_graph=True it runs between two replays, nothing is
+        re-captured."""
+        who = f"{type(self).__name__}.override_history"
+        idx = list(range(self.n)) if slots is None else slot_list(slots, self.n, who)
+        q = torch.as_tensor(q, dtype=torch.float32)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.dim() != 2 or q.shape[0] != len(idx) or q.shape[1] not in (54, 114):
+            raise ValueError(f"tip_amd.{who}: q is [len(slots), 54] (axis-angle root + 17 joints) or "
+                             f"[len(slots), 114] (qdq); got {tuple(q.shape)} for {len(idx)} slots")
+        if q.shape[1] == 114:
+            q = q[:, 3:57]
+        self._override_ready(idx)
+        if not idx:
+            return
+        with torch.cuda.device(self.device):
+            q = self._to_dev(q.contiguous()).contiguous()
+            sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
+            self._check(self.lib.tip_stream_history_override(self.state.data_ptr(), self.n, sl.data_ptr(), q.data_ptr(), len(idx),
+                                                             self._stream()))
+
+    # ---- the hand-off contract ------------------------------------------------------------------------------------------------------
+    def _demotions(self):
+        """Read by a frame body before and after its forward: a change says that the model answered a lost hand-off in between."""
+        return self.model.demotions + self.model.flow_demotions
+
+    def _lost_handoff(self, err=None):
+        """An EARLIER frame lost an inter-workgroup hand-off: its NaN row is in the history ring (the prologue would scrub it to 0
+        for the next 40 windows: finite, degraded poses) and in the reuse ring.  Re-prime and raise TipHandoffError instead of
+        consuming on top of it.  err None: tip_forward's entry check found it, the model demoted itself and served this call.  err:
+        the poll before a replay or the reuse forward raised it — demote the handle to the plans without hand-offs when allowed (a
+        launch chain instead of the one-launch form first), and pass err on."""
+        if err is not None:
+            h = self.model._ensure_handle()
+            if self.model._answer_handoff(h) is None:
+                h.check_clear()
+        self._reprime()
+        raise err or _lib.TipHandoffError(_lib.TIP_ERR_HANDOFF, "an earlier frame of this engine lost an inter-workgroup hand-off; "
+                                          f"the model now runs the non-cooperating plans and {self._REPRIMED}")
+
+    def _poll_handoff(self):
+        """Graph mode: tip_forward's entry check never runs during a replay, so the engine reads the hand-off word itself."""
+        try:
+            self.model.check_handoffs(synchronize=False)
+        except _lib.TipHandoffError as e:
+            self._lost_handoff(e)
+
+    # ---- captured frames ------------------------------------------------------------------------------------------------------------
+    def _capture(self, key):
+        """Capture the frame `key` (_captured_frame) into a HIP graph, after its forward ran once outside the capture (_warm_forward)."""
+        if self._graph_ws is None:
+            # what the captured kernels will point at: allocated OUTSIDE the capture, held by the engine, one for every key and sized for
+            # n (the one-launch form keeps its counters at offset 0 for any batch: include/tip_hip.h, tip_workspace_bytes; replays are serial)
+            self._graph_ws = torch.empty(self.model.workspace_bytes(self.n, 40), dtype=torch.uint8, device=self.device)
+            self._graph_y = torch.empty((self.n, self.model.size_s), dtype=torch.float32, device=self.device)
+        # packs / attaches outside the capture.  The device RNG is put back afterwards: with past_state_dropout or in_dropout live
+        # this warm-up would otherwise draw once more than the launch-by-launch loop does
+        rng = torch.cuda.get_rng_state(self.device)
+        self._warm_forward(key)
+        torch.cuda.set_rng_state(rng, self.device)
+        torch.cuda.current_stream(self.device).synchronize()
+        self._poll_handoff()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            self._y_last = self._captured_frame(key)
+        self._graphs[key] = (g, self._graph_ws, self.model._packed_dev, self._graph_y)
+        self.captures += 1
+        return g
+
+    def _replay(self, key):
+        """One replay of the frame `key`, captured first if it is not; a frame that is already there polls the hand-off word."""
+        e = self._graphs.get(key)
+        if e is None:
+            return self._capture(key).replay()
+        self._poll_handoff()
+        e[0].replay()
+
+
+class StreamingEngine(_StreamBase):
+    _REPRIMED = "the engine was reset (re-prime it)"
+
+    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False):
+        self.reuse = reuse          # True / False / "auto" (resolved in _allocate, once the stream count is known)
+        super().__init__(model, s_init, use_graph)
+
+    def _allocate(self):
+        model = self.model
+        self._ring = self._ctr_ptr = None
         if self.reuse == "auto":
             # the reuse form runs on the two-window encoder (1.049 ms per round of 2 x #CUs windows, ~5.8 % less with the ring); below
             # two windows per CU the one-window kernel (0.527 ms per round of #CUs) is the better plan even without it
@@ -196,178 +352,74 @@ class StreamingEngine:
             off = ctypes.c_size_t()
             self._check(self.lib.tip_stream_frame_counter_offset(ctypes.byref(off)))
             self._ctr_ptr = self.state.data_ptr() + off.value      # the frame index the ingest kernel keeps (stream 0's block)
-        self.reset()
-
-    def _check(self, status: int):
-        if status < 0:
-            raise _lib.TipStatusError(status, self.lib.tip_strerror(status).decode())
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _reset_state(self, s_init):
-        """tip_stream_reset_shaped: every block rebuilt from its s_init row, the buffer's shape recorded for the kernels."""
-        with torch.cuda.device(self.device):
-            self._check(self.lib.tip_stream_reset_shaped(self.state.data_ptr(), s_init.data_ptr(), self.n, self.n_sbps,
-                                                         1 if self.with_acc_sum else 0, self._stream()))
 
     def reset(self):
-        self.frame = 0
-        self._graph = None
-        self._graph_refs = None      # (workspace, packed weight image, y_last): what the captured kernels point at
-        self._y_last = None
+        self._forget()
         if self._ring is not None:
             self.model.reuse_reset(self._ring)
         self._reset_state(self.s_init)
 
-    # ---- host override of the fed-back pose ----------------------------------------------------------------------------------------
+    _reprime = reset        # (a lost hand-off: the NaN row is in the reuse ring too)
+
     def _override_ready(self, idx):
         """The slots of `idx` have consumed a frame (lock-step: all of them, from frame 5 on)."""
         if self.frame < 6:
             raise RuntimeError("tip_amd.StreamingEngine.override_history: no frame has been consumed yet (step() returns None while "
                                "the smoother primes: frames 0 .. 4)")
 
-    def override_history(self, q, slots=None):
-        """Replace the pose the last step() fed back — columns 0 .. 107 of the newest history row — by the host's corrected one.
-        q: [len(slots), 54] (root + 17 joints, axis-angle: s_t[3:57] of the reference) or [len(slots), 114] (a full qdq, of which
-        [3:57] is taken); host or CUDA tensor.  slots: slot indices, None = all.  Call it after step() returned the frame it corrects
-        and before the next step() (RTRunner's multi_sbp_terrain_and_correction: real_time_runner.py:483-495 feeds back
-        st_hist_copy, the IK-corrected copy of the pose it returns).  Root velocity, c_t, the pose average and the output filter are
-        not touched.  One small launch on the current stream; with use_graph=True it runs between two replays, nothing is
-        re-captured."""
-        name = type(self).__name__
-        if slots is None:
-            idx = list(range(self.n))
-        else:
-            try:
-                idx = [int(i) for i in slots]
-            except TypeError:
-                raise ValueError(f"tip_amd.{name}.override_history: slots must be a list of slot indices") from None
-            if any(i < 0 or i >= self.n for i in idx):
-                raise ValueError(f"tip_amd.{name}.override_history: slot index outside [0, {self.n})")
-            if len(set(idx)) != len(idx):
-                raise ValueError(f"tip_amd.{name}.override_history: duplicate slot index")
-        q = torch.as_tensor(q, dtype=torch.float32)
-        if q.dim() == 1:
-            q = q.unsqueeze(0)
-        if q.dim() != 2 or q.shape[0] != len(idx) or q.shape[1] not in (54, 114):
-            raise ValueError(f"tip_amd.{name}.override_history: q is [len(slots), 54] (axis-angle root + 17 joints) or "
-                             f"[len(slots), 114] (qdq); got {tuple(q.shape)} for {len(idx)} slots")
-        if q.shape[1] == 114:
-            q = q[:, 3:57]
-        self._override_ready(idx)
-        if not idx:
-            return
-        with torch.cuda.device(self.device):
-            to_dev = (lambda t: t.to(self.device, non_blocking=True) if t.is_cuda else t.pin_memory().to(self.device, non_blocking=True))
-            q = to_dev(q.contiguous()).contiguous()
-            sl = to_dev(torch.tensor(idx, dtype=torch.int32))
-            self._check(self.lib.tip_stream_history_override(self.state.data_ptr(), self.n, sl.data_ptr(), q.data_ptr(), len(idx),
-                                                             self._stream()))
-
-    def _poll_handoff(self):
-        """Graph mode: tip_forward's entry check never runs during a replay, so the engine reads the hand-off word itself."""
-        try:
-            self.model.check_handoffs(synchronize=False)
-        except _lib.TipHandoffError:
-            h = self.model._ensure_handle()
-            if self.model._answer_handoff(h) is None:     # (launch chain instead of the one-launch form, or the plans without hand-offs)
-                h.check_clear()
-            self._handoff_reset()   # the NaN row of the lost frame is in the history ring: re-prime (and re-capture on the new plan)
-            raise
-
-    def _handoff_reset(self):
-        """What a lost hand-off does to the engine before TipHandoffError is raised."""
-        self.reset()
-
-    def _replay_graph(self, warm, body):
-        """One replay of the captured frame `body` (capturing it first); `warm` runs the frame's forward once outside the capture."""
-        if self._graph is None:
-            # buffers the captured kernels will point at: allocated OUTSIDE the capture and held by the engine
-            if self._graph_ws is None:
-                self._graph_ws = torch.empty(self.model.workspace_bytes(self.n, 40), dtype=torch.uint8, device=self.device)
-                self._graph_y = torch.empty((self.n, self.model.size_s), dtype=torch.float32, device=self.device)
-            # packs / attaches outside the capture.  The device RNG is put back afterwards: with past_state_dropout or
-            # in_dropout live this warm-up would otherwise draw once more than the launch-by-launch loop does
-            rng = torch.cuda.get_rng_state(self.device)
-            warm()
-            torch.cuda.set_rng_state(rng, self.device)
-            torch.cuda.current_stream(self.device).synchronize()
-            self._poll_handoff()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                self._y_last = body()
-            self._graph = g
-            self._graph_refs = (self._graph_ws, self.model._packed_dev, self._graph_y)
-        else:
-            self._poll_handoff()
-        self._graph.replay()
-
-    def _frame_auto(self):
-        """ingest -> forward_last -> consume with the frame index taken from the state buffer (capturable)."""
+    def _frame(self, raw, f, f_consume, T, ws, out):
+        """ingest -> forward_last -> consume on windows of T rows; None while the smoother primes (T = 0).  Launch by launch: frame
+        indices f and f - 5, the module's own buffers (ws = out = None).  Captured: TIP_STREAM_FRAME_AUTO twice, T = 40, the engine's."""
         st = self._stream()
         # (full windows: the reuse forward reads only the newest row of x_imu / x_s — the 35-KB window gather per stream is skipped)
-        ingest = self.lib.tip_stream_ingest_newest if self.reuse else self.lib.tip_stream_ingest
-        self._check(ingest(self.state.data_ptr(), self.raw.data_ptr(), self.n, _lib.TIP_STREAM_FRAME_AUTO,
-                           self.x_imu.data_ptr(), self.x_s.data_ptr(), st))
+        ingest = self.lib.tip_stream_ingest_newest if (self.reuse and T == 40) else self.lib.tip_stream_ingest
+        self._check(ingest(self.state.data_ptr(), raw.data_ptr(), self.n, f, self.x_imu.data_ptr(), self.x_s.data_ptr(), st))
+        if T == 0:
+            return None
+        x_imu, x_s = self.x_imu, self.x_s
+        if T < 40:      # windows are written densely as [n, T, *] at the head of the preallocated buffers
+            x_imu = x_imu.view(-1)[: self.n * T * self.nx].view(self.n, T, self.nx)
+            x_s = x_s.view(-1)[: self.n * T * self.ns].view(self.n, T, self.ns)
+        mark = self._demotions()
         if self.reuse:
-            y_last = self.model.forward_last_reuse(self.x_imu, self.x_s, self._ring, 0, frame_ctr_ptr=self._ctr_ptr,
-                                                   workspace=self._graph_ws, out=self._graph_y)
+            f_fwd, ctr = (f, None) if ws is None else (0, self._ctr_ptr)
+            try:
+                y_last = self.model.forward_last_reuse(x_imu, x_s, self._ring, f_fwd, frame_ctr_ptr=ctr, workspace=ws, out=out)
+            except _lib.TipHandoffError as e:
+                self._lost_handoff(e)
         else:
-            y_last = self.model.forward_last(self.x_imu, self.x_s, workspace=self._graph_ws, out=self._graph_y)
-        self._check(self.lib.tip_stream_consume(self.state.data_ptr(), y_last.data_ptr(), self.n, _lib.TIP_STREAM_FRAME_AUTO,
+            y_last = self.model.forward_last(x_imu, x_s, workspace=ws, out=out)
+        if self._demotions() != mark:
+            self._lost_handoff()
+        self._check(self.lib.tip_stream_consume(self.state.data_ptr(), y_last.data_ptr(), self.n, f_consume,
                                                 self.s_rest.data_ptr(), self.c_t.data_ptr(), st))
         return y_last
 
+    def _warm_forward(self, key):
+        self.model.forward_last(self.x_imu, self.x_s, workspace=self._graph_ws, out=self._graph_y)   # (never touches the ring)
+
+    def _captured_frame(self, key):
+        return self._frame(self.raw, _lib.TIP_STREAM_FRAME_AUTO, _lib.TIP_STREAM_FRAME_AUTO, 40, self._graph_ws, self._graph_y)
+
     @torch.no_grad()
     def step(self, raw_imu: torch.Tensor) -> Optional[dict]:
-        if self.use_graph and self.frame >= 44 and not self.model.training:
+        f = self.frame
+        if self.use_graph and f >= 44 and not self.model.training:
             # steady state (T = 40): one copy + one graph launch per frame
             self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
             with torch.cuda.device(self.device):
-                self._replay_graph(lambda: self.model.forward_last(self.x_imu, self.x_s, workspace=self._graph_ws, out=self._graph_y),
-                                   self._frame_auto)   # (the warm-up never touches the ring)
-            self.frame += 1
+                self._replay(None)
+            self.frame = f + 1
             return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": self._y_last, "T": 40}
         raw = torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72).to(self.device, non_blocking=True).contiguous()
-        f = self.frame
         T = int(self.lib.tip_stream_window_len(f))
+        self.frame = f + 1          # (the frame is ingested whatever its forward does; a lost hand-off resets the counter)
         with torch.cuda.device(self.device):
-            # windows are written densely as [n, T, *] at the head of the preallocated buffers
-            ingest = self.lib.tip_stream_ingest_newest if (self.reuse and T == 40) else self.lib.tip_stream_ingest
-            self._check(ingest(self.state.data_ptr(), raw.data_ptr(), self.n, f, self.x_imu.data_ptr(), self.x_s.data_ptr(), self._stream()))
-            self.frame += 1
-            if T == 0:
-                return None
-            x_imu = self.x_imu.view(-1)[: self.n * T * self.nx].view(self.n, T, self.nx)
-            x_s = self.x_s.view(-1)[: self.n * T * self.ns].view(self.n, T, self.ns)
-            demotions = self.model.demotions + self.model.flow_demotions
-            if self.reuse:
-                try:
-                    y_last = self.model.forward_last_reuse(x_imu, x_s, self._ring, f)
-                except _lib.TipHandoffError:
-                    # an EARLIER frame lost an inter-workgroup hand-off (its NaN row is in the history ring and in the reuse ring): same
-                    # contract as the other paths — demote the handle to the plans without hand-offs when allowed, re-prime, raise
-                    h = self.model._ensure_handle()
-                    if self.model._answer_handoff(h) is None:
-                        h.check_clear()
-                    self.reset()
-                    raise
-            else:
-                y_last = self.model.forward_last(x_imu, x_s)
-            if self.model.demotions + self.model.flow_demotions != demotions:
-                # tip_forward's entry check found that an EARLIER frame lost a hand-off: the model demoted itself and served this
-                # call, but that frame's NaN row already went into the history ring (the prologue would scrub it to 0 for the
-                # next 40 windows: finite, degraded poses).  Same contract as the graph path: re-prime and raise.
-                self.reset()
-                raise _lib.TipHandoffError(_lib.TIP_ERR_HANDOFF, "an earlier frame of this engine lost an inter-workgroup hand-off; "
-                                           "the model now runs the non-cooperating plans and the engine was reset (re-prime it)")
-            self._check(self.lib.tip_stream_consume(self.state.data_ptr(), y_last.data_ptr(), self.n, f - 5,
-                                                    self.s_rest.data_ptr(), self.c_t.data_ptr(), self._stream()))
-        return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": y_last, "T": T}
+            y_last = self._frame(raw, f, f - 5, T, None, None)
+        return None if T == 0 else {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": y_last, "T": T}
 
 
-class StaggeredStreamingEngine(StreamingEngine):
+class StaggeredStreamingEngine(_StreamBase):
     """Streams that start, warm up and stop on their own (include/tip_hip.h, "staggered streams"): n fixed slots, each with its
     own frame counter, attached or detached.
 
@@ -377,14 +429,14 @@ class StaggeredStreamingEngine(StreamingEngine):
         eng.attach([3], s_init_rows)                       # slot 3 restarts at its frame 0 from s_init_rows [1,114]
 
     step() returns s_rest [n,111], c_t [n,20], y_last [n,131] (c_t [n,8], y_last [n,119] for a two-SBP model), T (int32 [n]: the
-    slot's window length this frame, 0 while priming
-    or detached) and valid (bool [n]: the slot produced a row this frame).  Rows of slots that are not valid are NaN in y_last and
-    unchanged in s_rest / c_t.  A frame is ingest_staggered -> forward_rows -> consume_staggered with no frame index, so with
-    use_graph=True it is captured once, at the first step, and replayed from then on; attach / detach run between replays.
-    Every slot occupies a T = 40 window in the forward whatever its state (a fixed slot -> window map keeps the graph static): a
-    fresh engine pays the steady-state price from its first frame on, where StreamingEngine runs shorter windows while it warms up.
-    .eval() only (fp32); reuse= is refused (the reuse ring assumes lock-step frames).  A lost hand-off (StreamingEngine's
-    contract) re-attaches every attached slot with the s_init it was last attached with and raises TipHandoffError.
+    slot's window length this frame, 0 while priming or detached) and valid (bool [n]: the slot produced a row this frame).
+    Rows of slots that are not valid are NaN in y_last and unchanged in s_rest / c_t.  A frame is ingest_staggered ->
+    forward_rows -> consume_staggered with no frame index, so with use_graph=True it is captured once, at the first step, and
+    replayed from then on; attach / detach run between replays.  Every slot occupies a T = 40 window in the forward whatever its
+    state (a fixed slot -> window map keeps the graph static): a fresh engine pays the steady-state price from its first frame
+    on, where StreamingEngine runs shorter windows while it warms up.  .eval() only (fp32); reuse= is refused (the reuse ring
+    assumes lock-step frames).  A lost hand-off (StreamingEngine's contract) re-attaches every attached slot with the s_init it
+    was last attached with and raises TipHandoffError.
 
     compact=True: a pool whose cost follows its load.  The k attached slots hold window positions 0 .. k-1 (SlotPositions: a fresh
     engine and reset() lay them out in slot order, a detach moves the last position into the hole, re-attaching keeps the position)
@@ -399,31 +451,35 @@ class StaggeredStreamingEngine(StreamingEngine):
     reference; on a pinned plan whose per-window results do not depend on the batch (set_plan("fused")) they do not change, and
     compact=True is bit-identical per slot to compact=False under any attach / detach schedule."""
 
+    _REPRIMED = "every attached slot was re-attached"
+
     def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False, compact: bool = False):
         if reuse:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine: reuse= is not supported (the reuse ring assumes lock-step frames)")
         if model.training:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine needs model.eval() (the inference kernels: forward_rows)")
+        self.reuse, self._ring = False, None          # (lock-step only)
         self.compact = bool(compact)
-        self._attached = None
-        super().__init__(model, s_init, use_graph=use_graph, reuse=False)
+        super().__init__(model, s_init, use_graph)
         self.s_rest.zero_()          # (rows of slots that have not produced a row yet: defined, and unchanged until they do)
         self.c_t.zero_()
 
-    def _slots(self, slots, what):
-        try:
-            idx = [int(i) for i in slots]
-        except TypeError:
-            raise ValueError(f"tip_amd.StaggeredStreamingEngine.{what}: slots must be a list of slot indices") from None
-        if any(i < 0 or i >= self.n for i in idx):
-            raise ValueError(f"tip_amd.StaggeredStreamingEngine.{what}: slot index outside [0, {self.n})")
-        if len(set(idx)) != len(idx):
-            raise ValueError(f"tip_amd.StaggeredStreamingEngine.{what}: duplicate slot index")
-        return idx
-
-    def _to_dev(self, t):
-        """Host -> device without a synchronising copy from pageable memory (an attach between two frames must not drain the queue)."""
-        return t.to(self.device, non_blocking=True) if t.is_cuda else t.pin_memory().to(self.device, non_blocking=True)
+    def _allocate(self):
+        self._attached = [True] * self.n
+        self.s_cur = self.s_init.clone()
+        self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        if self.compact:
+            self.ladder = pool_ladder(self.n)
+            self._positions = SlotPositions(self.n)
+            self.s_host = self.s_init.cpu()       # the s_init rows slots were last attached with, on the host
+            # one device buffer for everything attach / detach hand the device between two frames, filled by ONE copy from
+            # pinned memory (_flush, stage_image): the position map (words 0 .. n-1, where every captured frame reads it), then the
+            # slots to attach, the slots detached (int64) and the attached slots' s_init rows
+            self._stage = torch.empty(self.n * 118 + 2, dtype=torch.int32, device=self.device)
+            self.slot_at = self._stage[: self.n]                                         # position -> slot, -1: empty
+            self._pending_attach, self._pending_detach = {}, {}
+            self.y_slot = torch.full((self.n, self.model.size_s), float("nan"), dtype=torch.float32, device=self.device)
+            self.rows_slot = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
 
     def _attach_dev(self, idx):
         if not idx:
@@ -437,49 +493,26 @@ class StaggeredStreamingEngine(StreamingEngine):
     def reset(self):
         """Re-prime: every attached slot restarts at its frame 0 from the s_init it was last attached with; detached slots stay
         detached.  Drops the captured graph(s); a compact pool lays its attached slots out in slot order again."""
-        if self._attached is None:
-            self._attached = [True] * self.n
-            self.s_cur = self.s_init.clone()
-            self.rows = torch.empty(self.n, dtype=torch.int32, device=self.device)
-            if self.compact:
-                self.ladder = pool_ladder(self.n)
-                self.captures = 0
-                self._graphs = {}
-                self._positions = SlotPositions(self.n)
-                self.s_host = self.s_init.cpu()       # the s_init rows slots were last attached with, on the host
-                # one device buffer for everything attach / detach hand the device between two frames, filled by ONE copy from
-                # pinned memory (_flush): the position map (words 0 .. n-1, where every captured frame reads it), then the slots to
-                # attach, the slots detached (int64) and the attached slots' s_init rows
-                self._stage = torch.empty(self.n * 118 + 2, dtype=torch.int32, device=self.device)
-                self.slot_at = self._stage[: self.n]                                         # position -> slot, -1: empty
-                self._pending_attach, self._pending_detach = {}, {}
-                self.y_slot = torch.full((self.n, self.model.size_s), float("nan"), dtype=torch.float32, device=self.device)
-                self.rows_slot = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
         if self.compact:
             self._positions.reset([i for i in range(self.n) if self._attached[i]])
         self._restart()
 
     def _restart(self):
         """Every attached slot back to its frame 0 (positions kept), graphs dropped."""
-        self.frame = 0
-        self._graph = None
-        self._graph_refs = None
-        self._y_last = None
+        self._forget()
         self._attach_frame = [0] * self.n       # engine frame at which the slot was last attached (override_history: its age)
         self._reset_state(self.s_cur)
         if self.compact:
-            self._graphs = {}
-            self._pending_attach = dict.fromkeys(i for i in range(self.n) if self._attached[i])   # (re-attached by the next step)
+            self._pending_attach = dict.fromkeys([i for i in range(self.n) if self._attached[i]])   # (re-attached by the next step)
             self._map_dirty = True
-            return
-        self._attach_dev([i for i in range(self.n) if self._attached[i]])
+        else:
+            self._attach_dev([i for i in range(self.n) if self._attached[i]])
 
-    def _handoff_reset(self):
-        self._restart()
+    _reprime = _restart
 
     def attach(self, slots, s_init_rows):
         """(Re)start the listed slots at their frame 0 from s_init_rows [len(slots),114]."""
-        idx = self._slots(slots, "attach")
+        idx = slot_list(slots, self.n, "StaggeredStreamingEngine.attach")
         rows = torch.as_tensor(s_init_rows, dtype=torch.float32).reshape(-1, 114) if len(idx) else None
         if rows is not None and rows.shape[0] != len(idx):
             raise ValueError("tip_amd.StaggeredStreamingEngine.attach: one s_init row [114] per slot")
@@ -502,7 +535,7 @@ class StaggeredStreamingEngine(StreamingEngine):
 
     def detach(self, slots):
         """Stop the listed slots: from the next frame on they are skipped (NaN y_last row, s_rest / c_t rows unchanged)."""
-        idx = self._slots(slots, "detach")
+        idx = slot_list(slots, self.n, "StaggeredStreamingEngine.detach")
         if not idx:
             return
         for i in idx:
@@ -537,54 +570,48 @@ class StaggeredStreamingEngine(StreamingEngine):
         """compact=True: the batch the forward runs on with k attached slots."""
         return pool_bucket(k, self.ladder)
 
-    def _frame_staggered(self):
-        """ingest_staggered -> forward_rows -> consume_staggered: no frame index anywhere (capturable from the first frame on)."""
+    def _frame_staggered(self, ws, out):
+        """ingest_staggered -> forward_rows -> consume_staggered: no frame index anywhere (capturable from the first frame on).
+        Launch by launch on the module's own workspace and output (ws = out = None), captured on the engine's."""
         st = self._stream()
         self._check(self.lib.tip_stream_ingest_staggered(self.state.data_ptr(), self.raw.data_ptr(), self.n, self.x_imu.data_ptr(),
                                                          self.x_s.data_ptr(), self.rows.data_ptr(), st))
-        y_last = self.model.forward_rows(self.x_imu, self.x_s, self.rows, workspace=self._graph_ws, out=self._graph_y)
+        mark = self._demotions()
+        y_last = self.model.forward_rows(self.x_imu, self.x_s, self.rows, workspace=ws, out=out)
+        if self._demotions() != mark:
+            self._lost_handoff()
         self._check(self.lib.tip_stream_consume_staggered(self.state.data_ptr(), y_last.data_ptr(), self.rows.data_ptr(), self.n,
                                                           self.s_rest.data_ptr(), self.c_t.data_ptr(), st))
         return y_last
 
     # ---- compact pools ----------------------------------------------------------------------------------------------------------
-    def _ingest_mapped(self, B):
+    def _frame_mapped(self, B, ws, out):
+        """ingest_mapped -> forward_rows on B windows -> consume_mapped (what a bucket's graph holds); ws / out as _frame_staggered's."""
+        st = self._stream()
         self._check(self.lib.tip_stream_ingest_mapped(self.state.data_ptr(), self.raw.data_ptr(), self.n, self.slot_at.data_ptr(), B,
-                                                      self.x_imu.data_ptr(), self.x_s.data_ptr(), self.rows.data_ptr(), self._stream()))
-
-    def _consume_mapped(self, B, y):
+                                                      self.x_imu.data_ptr(), self.x_s.data_ptr(), self.rows.data_ptr(), st))
+        mark = self._demotions()
+        y = self.model.forward_rows(self.x_imu[:B], self.x_s[:B], self.rows[:B], workspace=ws, out=out)
+        if self._demotions() != mark:
+            self._lost_handoff()
         self._check(self.lib.tip_stream_consume_mapped(self.state.data_ptr(), y.data_ptr(), self.rows.data_ptr(), self.slot_at.data_ptr(),
                                                        B, self.n, self.s_rest.data_ptr(), self.c_t.data_ptr(), self.y_slot.data_ptr(),
-                                                       self.rows_slot.data_ptr(), self._stream()))
-
-    def _forward_mapped(self, B, graph):
-        ws, out = (self._graph_ws, self._graph_y[:B]) if graph else (None, None)
-        return self.model.forward_rows(self.x_imu[:B], self.x_s[:B], self.rows[:B], workspace=ws, out=out)
-
-    def _frame_mapped(self, B):
-        """ingest_mapped -> forward_rows on B windows -> consume_mapped (what a bucket's graph holds)."""
-        self._ingest_mapped(B)
-        self._consume_mapped(B, self._forward_mapped(B, True))
+                                                       self.rows_slot.data_ptr(), st))
+        return y
 
     def _flush(self):
-        """The attach / detach calls since the last frame, on the device: one non-blocking copy from pinned memory (position map,
-        slot lists, s_init rows), the attach kernel, and NaN / -1 into the y_last / T rows of the detached slots (no kernel writes
-        the rows of a slot that is not listed).  Stream order puts it after the previous frame and before this one."""
+        """The attach / detach calls since the last frame, on the device: one non-blocking copy from pinned memory (stage_image:
+        position map, slot lists, s_init rows), the attach kernel, and NaN / -1 into the y_last / T rows of the detached slots (no
+        kernel writes the rows of a slot that is not listed).  Stream order puts it after the previous frame and before this one."""
         if not (self._map_dirty or self._pending_attach or self._pending_detach):
             return
-        n, att, det = self.n, list(self._pending_attach), list(self._pending_detach)
-        o_det = (n + len(att) + 1) // 2 * 2          # (int64 entries: 8-byte aligned)
-        o_rows = o_det + 2 * len(det)
-        h = np.empty(o_rows + 114 * len(att), dtype=np.int32)
-        h[:n] = -1
-        h[: len(self._positions)] = self._positions.slot_at
-        h[n: n + len(att)] = att
-        h[o_det: o_rows] = np.asarray(det, dtype=np.int64).view(np.int32)
-        h[o_rows:] = self.s_host[att].numpy().reshape(-1).view(np.int32)
+        att, det = list(self._pending_attach), list(self._pending_detach)
+        h, (o_att, o_det, o_rows) = stage_image(self.n, self._positions.slot_at, att, det, self.s_host[att].numpy())
         self._stage[: h.size].copy_(torch.from_numpy(h).pin_memory(), non_blocking=True)
         base = self._stage.data_ptr()
         if att:
-            self._check(self.lib.tip_stream_attach(self.state.data_ptr(), n, base + 4 * n, base + 4 * o_rows, len(att), self._stream()))
+            self._check(self.lib.tip_stream_attach(self.state.data_ptr(), self.n, base + 4 * o_att, base + 4 * o_rows, len(att),
+                                                   self._stream()))
         if det:
             sl = self._stage[o_det: o_rows].view(torch.int64)
             self.y_slot.index_fill_(0, sl, float("nan"))
@@ -592,22 +619,13 @@ class StaggeredStreamingEngine(StreamingEngine):
         self._map_dirty = False
         self._pending_attach, self._pending_detach = {}, {}
 
-    def _capture(self, B):
-        if self._graph_ws is None:
-            # one workspace and one output buffer for every bucket, sized for the largest (n): the one-launch form keeps its counters
-            # at offset 0 for any batch (include/tip_hip.h, tip_workspace_bytes), and the graphs replay one at a time on one stream
-            self._graph_ws = torch.empty(self.model.workspace_bytes(self.n, 40), dtype=torch.uint8, device=self.device)
-            self._graph_y = torch.empty((self.n, self.model.size_s), dtype=torch.float32, device=self.device)
-        rng = torch.cuda.get_rng_state(self.device)
-        self._forward_mapped(B, True)          # packs / attaches outside the capture
-        torch.cuda.set_rng_state(rng, self.device)
-        torch.cuda.current_stream(self.device).synchronize()
-        self._poll_handoff()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._frame_mapped(B)
-        self._graphs[B] = (g, self._graph_ws, self.model._packed_dev, self._graph_y)   # what the captured kernels point at
-        self.captures += 1
+    def _warm_forward(self, B):
+        B = self.n if B is None else B          # (the plain engine: all n windows)
+        self.model.forward_rows(self.x_imu[:B], self.x_s[:B], self.rows[:B], workspace=self._graph_ws, out=self._graph_y[:B])
+
+    def _captured_frame(self, B):
+        ws, y = self._graph_ws, self._graph_y
+        return self._frame_staggered(ws, y) if B is None else self._frame_mapped(B, ws, y[:B])
 
     @torch.no_grad()
     def prewarm(self, buckets=None):
@@ -634,21 +652,9 @@ class StaggeredStreamingEngine(StreamingEngine):
             self._flush()
             if k:
                 if self.use_graph:
-                    if B not in self._graphs:
-                        self._capture(B)
-                    else:
-                        self._poll_handoff()
-                    self._graphs[B][0].replay()
+                    self._replay(B)
                 else:
-                    demotions = self.model.demotions + self.model.flow_demotions
-                    self._ingest_mapped(B)
-                    y = self._forward_mapped(B, False)
-                    if self.model.demotions + self.model.flow_demotions != demotions:
-                        self._handoff_reset()
-                        raise _lib.TipHandoffError(_lib.TIP_ERR_HANDOFF, "an earlier frame of this engine lost an inter-workgroup "
-                                                   "hand-off; the model now runs the non-cooperating plans and every attached slot "
-                                                   "was re-attached")
-                    self._consume_mapped(B, y)
+                    self._frame_mapped(B, None, None)
             T = self.rows_slot + 1
         self.frame += 1
         return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": self.y_slot, "T": T, "valid": T > 0, "active": k, "batch": B}
@@ -662,23 +668,10 @@ class StaggeredStreamingEngine(StreamingEngine):
         self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
         with torch.cuda.device(self.device):
             if self.use_graph:
-                self._replay_graph(lambda: self.model.forward_rows(self.x_imu, self.x_s, self.rows, workspace=self._graph_ws,
-                                                                   out=self._graph_y),
-                                   self._frame_staggered)
+                self._replay(None)
                 y_last = self._y_last
             else:
-                demotions = self.model.demotions + self.model.flow_demotions
-                st = self._stream()
-                self._check(self.lib.tip_stream_ingest_staggered(self.state.data_ptr(), self.raw.data_ptr(), self.n,
-                                                                 self.x_imu.data_ptr(), self.x_s.data_ptr(), self.rows.data_ptr(), st))
-                y_last = self.model.forward_rows(self.x_imu, self.x_s, self.rows)
-                if self.model.demotions + self.model.flow_demotions != demotions:
-                    # an EARLIER frame lost a hand-off (StreamingEngine.step): its NaN row went into the history rings — re-prime, raise
-                    self._handoff_reset()
-                    raise _lib.TipHandoffError(_lib.TIP_ERR_HANDOFF, "an earlier frame of this engine lost an inter-workgroup hand-off; "
-                                               "the model now runs the non-cooperating plans and every attached slot was re-attached")
-                self._check(self.lib.tip_stream_consume_staggered(self.state.data_ptr(), y_last.data_ptr(), self.rows.data_ptr(),
-                                                                  self.n, self.s_rest.data_ptr(), self.c_t.data_ptr(), st))
+                y_last = self._frame_staggered(None, None)
             T = self.rows + 1
         self.frame += 1
         return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": y_last, "T": T, "valid": T > 0}
