@@ -13,6 +13,9 @@
  *   ./c_host y.bin B 40 reuse F    # F frames of B lock-stepped streams through tip_forward_reuse (a frame's in_linear
  *                                  # and layer-0 Q / K / V rows computed once, kept in a ring for the 40 windows it appears in):
  *                                  # windows grow 1 .. 40, then slide; writes F*B*131 float32 (row T-1 of every call)
+ *   ./c_host y.bin B T live        # the model as the reference deploys it (past_state_dropout = 0.8, never .eval()): ONE tip_forward_live
+ *                                  # call — encoder dropout 0.1 and the keep mask live under fixed seeds, any B; writes B*131 float32
+ *                                  # (row T-1 of every window)
  */
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
@@ -131,6 +134,28 @@ int main(int argc, char** argv) {
     CHECK_HIP(hipMemcpy(xs_d, xs, ns * sizeof(float), hipMemcpyHostToDevice));
     hipStream_t stream;
     CHECK_HIP(hipStreamCreate(&stream));
+    if (argc > 4 && !strcmp(argv[4], "live")) {
+        /* ---- the deployed forward: every shipped loader builds the model with past_state_dropout = 0.8 and leaves it in .train() mode.
+         *      keep_scale = 1 / (1 - p_state); the seeds are host arguments here (a captured graph would pass a device pair and advance
+         *      it with tip_seeds_next in front of every replay). ---- */
+        const float p_state = 0.8f, p_drop = 0.1f;
+        const float keep_scale = (float)(1.0 / (1.0 - 0.8));   /* 1 / (1 - p) in double, rounded once: what torch's dropout and the Python host use */
+        CHECK_TIP(tip_forward_live(h, xi_d, xs_d, y_d, B, T, NULL, TIP_FWD_LAST_ROW_ONLY, NULL, keep_scale, p_state, 2024ull,
+                                   p_drop, 1234ull, NULL, ws, ws_bytes, stream));
+        CHECK_HIP(hipStreamSynchronize(stream));
+        CHECK_TIP(tip_check(h, 0));
+        const size_t nl = (size_t)B * 131;
+        float* yl = (float*)malloc(nl * sizeof(float));
+        CHECK_HIP(hipMemcpy(yl, y_d, nl * sizeof(float), hipMemcpyDeviceToHost));
+        double suml = 0.0;
+        for (size_t e = 0; e < nl; ++e) suml += (double)yl[e];
+        FILE* fl = fopen(out_path, "wb");
+        if (!fl || fwrite(yl, sizeof(float), nl, fl) != nl) return 4;
+        fclose(fl);
+        printf("c_host live: B=%d T=%d y[0]=%.9g sum=%.9g\n", B, T, (double)yl[0], suml);
+        tip_destroy(h);
+        return 0;
+    }
     CHECK_TIP(tip_forward(h, xi_d, xs_d, y_d, B, T, 0, NULL, 1.0f, ws, ws_bytes, stream));
     CHECK_HIP(hipStreamSynchronize(stream));
     CHECK_TIP(tip_check(h, 0));   /* a lost inter-workgroup hand-off is an error, not a number */

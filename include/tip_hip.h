@@ -32,7 +32,8 @@ extern "C" {
                                 tip_stream_ingest_newest; later, backward compatible: tip_forward_rows and the staggered streaming entry points
                                 (tip_stream_attach, tip_stream_detach, tip_stream_ingest_staggered, tip_stream_consume_staggered,
                                 tip_stream_ingest_mapped, tip_stream_consume_mapped); the model shapes of the streaming entry points
-                                (tip_stream_reset_shaped) and the host override of the fed-back pose (tip_stream_history_override) */
+                                (tip_stream_reset_shaped) and the host override of the fed-back pose (tip_stream_history_override); the deployed forward at any
+                                batch and its device seeds (tip_forward_live, tip_seeds_next) */
 
 /* The library is built with -fvisibility=hidden: the functions declared here (and the measurement hooks of
  * tip_hip_debug.h) are its whole dynamic symbol table (tests/test_host_cpu.py compares `nm -D` with the two headers). */
@@ -214,6 +215,29 @@ TIP_API int tip_forward_dropout(tip_handle* h, const float* x_imu, const float* 
                         unsigned long long seed, void* workspace, size_t workspace_bytes, tip_stream_t stream);
 /* mask[i] = 1 (keep) or 0 for i < n: the counter-based hash of the training step at site 0xFFFFFFF0, drop probability p_state in [0, 1) */
 TIP_API int tip_draw_keep_mask(float p_state, unsigned long long state_seed, float* mask, size_t n, tip_stream_t stream);
+
+/* The deployed forward at ANY batch: the function tip_forward_dropout computes (encoder dropout at p_drop under `seed`, past-state keep
+ * mask at p_state under `state_seed` or an explicit keep_mask, nothing stashed), for every B up to tip_max_batch and with
+ * tip_forward_rows' output forms (rows NULL: flags decide between the full output and the last row; rows non-NULL: one chosen row per
+ * window, NaN for an index outside [0, T)).  Every shipped loader of the reference builds the model with past_state_dropout = 0.8 and
+ * never calls .eval(): this is what such a runner evaluates, whatever the size of its pool.
+ * Plan: the few-stream latency plan where tip_forward_dropout takes it (B <= 64, T <= 40, handle not demoted); otherwise ONE launch
+ * sequence — the one-window hybrid encoder in its live mode (the training instantiation's four dropout sites, the keep mask drawn in its
+ * prologue, no stash), then the recurrence and the output projection of tip_forward.  A demoted handle is served by the second form (it
+ * has no cooperating encoder).  Configurations the hybrid training forward does not serve: TIP_ERR_UNSUPPORTED_CONFIG.  The keep
+ * decisions are a function of (seed, site, element index) alone: both plans, tip_train_forward and tip_draw_keep_mask agree on them.
+ * seeds_dev (nullable): DEVICE unsigned long long [2] = {seed, state_seed}, read by the kernels at launch time INSTEAD of the two
+ * arguments — so a captured HIP graph holding "tip_seeds_next, tip_forward_live" draws fresh masks at every replay with no kernel
+ * argument changing.  p_state / p_drop (the thresholds) stay host arguments.
+ * flags, workspace (tip_workspace_bytes), hand-off checks, CU-masked streams and HIP-graph capture as in tip_forward_rows. */
+TIP_API int tip_forward_live(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, const int* rows, int flags,
+                     const float* keep_mask, float keep_scale, float p_state, unsigned long long state_seed, float p_drop,
+                     unsigned long long seed, const unsigned long long* seeds_dev, void* workspace, size_t workspace_bytes,
+                     tip_stream_t stream);
+/* One tiny launch: each of the two words of seeds_dev (DEVICE, 8-byte aligned) is replaced by its splitmix64 successor,
+ *     z = s + 0x9E3779B97F4A7C15;  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;
+ *     next(s) = z ^ (z >> 31)                                                  (all arithmetic modulo 2^64) */
+TIP_API int tip_seeds_next(unsigned long long* seeds_dev, tip_stream_t stream);
 
 /* ---- forward in fp64: the module built under `--double` (train_model.py:62-63,84-85: torch.set_default_dtype(float64), fp64
  *      windows :161-164).  Same function as tip_forward (simple_transformer_with_state.py:60-102) with every operation in IEEE

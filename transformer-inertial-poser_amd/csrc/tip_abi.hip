@@ -710,6 +710,7 @@ struct LaunchSeq {
     int rnn_cluster;
     const ReuseCtx* reuse;      // full windows: the two-window encoder reads the ring
     const TrainDropout* td;     // tip_forward_dropout: the latency plan's dropout sites
+    const LiveTrain* live = nullptr;   // tip_forward_live off the latency plan: the hybrid encoder runs in its live mode
     // what the encoder leaves for the tail
     int plan = TIP_PLAN_AUTO;
     bool ih_done = false;       // the RNN input projection is in `big` already
@@ -777,7 +778,10 @@ static int run_encoder(LaunchSeq& q, const SchedPart& p, int off) {
         StageScope sc(h, s, "fused_encoder");
         q.ih_done = fused_has_rnn_ih(d);
         q.hall_armed = q.ih_done && arm_hall();   // the encoder pre-fills its HALL rows
-        if (p.plan == TIP_PLAN_FUSEDH)
+        if (p.plan == TIP_PLAN_FUSEDH && q.live)
+            TIP_TRY(launch_fused_live_h(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, q.ih_done ? nullptr : xa, q.ih_done ? ih : nullptr,
+                                        q.hall_armed ? hall : nullptr, *q.live, q.live->lv, B, T, cus, s), "fused_encoder_h live");
+        else if (p.plan == TIP_PLAN_FUSEDH)
             TIP_TRY(launch_fused_encoder_h(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, q.ih_done ? nullptr : xa,
                                            q.ih_done ? ih : nullptr, q.hall_armed ? hall : nullptr, B, T, cus, s), "fused_encoder_h");
         else
@@ -984,6 +988,64 @@ int tip_forward_dropout(tip_handle* h, const float* x_imu, const float* x_s, flo
     if (st != TIP_OK) return st;
     h->forward_count++;
     return TIP_OK;
+}
+
+int tip_forward_live(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, const int* rows, int flags,
+                     const float* keep_mask, float keep_scale, float p_state, unsigned long long state_seed, float p_drop,
+                     unsigned long long seed, const unsigned long long* seeds_dev, void* workspace, size_t workspace_bytes,
+                     tip_stream_t stream) {
+    if (!h || !x_imu || !x_s || !y || B < 0 || T < 1) return TIP_ERR_INVALID_ARG;
+    if (p_drop < 0.f || p_drop >= 1.f) return TIP_ERR_INVALID_ARG;
+    if (rows) flags |= TIP_FWD_LAST_ROW_ONLY;
+    unsigned mkey = 0, mthresh = 0;
+    if (!(flags & TIP_FWD_KEEP_MASK) && p_state > 0.f && !state_mask_params(p_state, state_seed, &mkey, &mthresh)) return TIP_ERR_INVALID_ARG;
+    if ((flags & TIP_FWD_KEEP_MASK) && !keep_mask) return TIP_ERR_INVALID_ARG;
+    const Dims& d = h->d;
+    if ((long long)B * T * (long long)std::max(std::max(3 * d.D, d.F), std::max(d.R, d.InPad)) * 4 > 0x7fffffffLL) return TIP_ERR_UNSUPPORTED_CONFIG;
+    if (!h->packed_dev) return TIP_ERR_NOT_READY;
+    if (tip_check(h, 0) != TIP_OK) return TIP_ERR_HANDOFF;
+    if (B == 0) return TIP_OK;
+    // the few-stream plan where tip_forward_dropout takes it; everything else — a demoted handle too: no cooperating encoder — on the
+    // one-window hybrid encoder's live mode, which serves what the hybrid training forward serves
+    const bool latency = !h->demoted && latency_supported(d, B, T);
+    if (!latency && !(fused_supported(d, T) && fused_has_rnn_ih(d))) return TIP_ERR_UNSUPPORTED_CONFIG;
+    const Workspace ws = carve_workspace(d, B, T);
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 || workspace_bytes < ws.total_bytes) return TIP_ERR_WORKSPACE;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int cus = effective_cus(h->num_cus, s);
+    int rnn_cluster = 0;
+    if (!latency) {   // (the recurrence variant as the forward pinned to the hybrid plan resolves it)
+        const Schedule sc = schedule_forward(ScheduleIn{d, B, T, cus, h->num_cus, TIP_PLAN_FUSEDH, h->rnn_cluster, h->f1s_parts, h->demoted != 0, false,
+                                                        workspace_bytes});
+        if (sc.status != TIP_OK) return sc.status;
+        rnn_cluster = sc.part[0].rnn_cluster;
+    }
+    CoopSerial serial(h->device, s);
+    if (serial.status != hipSuccess) return fail_hip(h, serial.status, "stream serialisation");
+    const float* mask = (flags & TIP_FWD_KEEP_MASK) ? keep_mask : nullptr;
+    if (!mask && !mthresh) keep_scale = 1.f;
+    TrainDropout td = make_train_dropout(p_drop, seed);
+    td.mkey = mkey;
+    td.mthresh = mthresh;
+    td.seeds_dev = seeds_dev;
+    td.state_seed = state_seed;
+    LiveTrain lt;
+    lt.sv = nullptr;
+    lt.x0 = lt.qkv = lt.ast = lt.att = lt.z1 = lt.st1 = lt.x1 = lt.hid = lt.z2 = lt.st2 = lt.xo = lt.layer_stride = 0;
+    lt.seed = seed; lt.thresh = td.thresh; lt.scale = td.scale;
+    lt.lv = LiveArgs{seeds_dev, state_seed, mask ? 0u : mthresh};
+    LaunchSeq q{h, s, cus, x_imu, x_s, mask, keep_scale, y, rows, B, T, flags, static_cast<float*>(workspace), ws, rnn_cluster, nullptr,
+                latency ? &td : nullptr, latency ? nullptr : &lt};
+    int st = run_encoder(q, SchedPart{0, B, latency ? TIP_PLAN_LATENCY : TIP_PLAN_FUSEDH, rnn_cluster}, 0);
+    if (st == TIP_OK) st = run_tail(q);
+    if (st != TIP_OK) return st;
+    h->forward_count++;
+    return TIP_OK;
+}
+
+int tip_seeds_next(unsigned long long* seeds_dev, tip_stream_t stream) {
+    if (!seeds_dev || reinterpret_cast<uintptr_t>(seeds_dev) % 8) return TIP_ERR_INVALID_ARG;
+    return launch_seeds_next(seeds_dev, static_cast<hipStream_t>(stream)) == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 
 }  // extern "C"

@@ -121,8 +121,8 @@ __device__ __forceinline__ void attention_head_mfma(float* Qc, float* Kc, const 
 // output without touching LDS and without a workgroup barrier in between.  O is written to the plane `Oc` (out-projection
 // A operand) at column c0.
 // TRAIN: dropout on the probabilities (keep = hash(seed, site, (bh*T + query)*T + key) >= thresh) and the softmax statistics
-// (row max, 1 / row sum) of every real query written to ast[(bh*T + query)*2 ..] for the backward.
-template <int LDC, bool TRAIN = false>
+// (row max, 1 / row sum) of every real query written to ast[(bh*T + query)*2 ..] for the backward (STATS; the live forward has none).
+template <int LDC, bool TRAIN = false, bool STATS = true>
 __device__ __forceinline__ void attention_head_regs(const f32x4_att (&qt)[3], const f32x4_att (&kt)[3], const f32x4_att (&v)[3],
                                                     float* Oc, int c0, int lane, int row_limit = 48, float* ast = nullptr,
                                                     unsigned long long bh = 0, int T = 0, unsigned long long seed = 0,
@@ -185,7 +185,7 @@ __device__ __forceinline__ void attention_head_regs(const f32x4_att (&qt)[3], co
         for (int r = 0; r < RB; ++r) {
             const int q = r * 16 + l15;
             const ln_u32x2 mr = {__float_as_uint(mx[r]), __float_as_uint(rsum[r])};
-            __builtin_amdgcn_raw_buffer_store_b64(mr, ars, lg == 0 ? q * 8 : T * 8, 0, 0);
+            if (STATS) __builtin_amdgcn_raw_buffer_store_b64(mr, ars, lg == 0 ? q * 8 : T * 8, 0, 0);
             if (thresh) {
                 const unsigned pb = (unsigned)((bh * T + q) * T);
 #pragma unroll

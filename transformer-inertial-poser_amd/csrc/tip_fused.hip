@@ -823,11 +823,11 @@ __device__ unsigned long long g_fh_wg[2 * 1024];   // TRACE: [workgroup][entry, 
 
 // TR: training forward (tip_train_forward) — the encoder's four dropout sites and the activation stash of the backward, exactly
 // as fused_encoder_kernel<8> writes them (same arrays, same per-element dropout keys: the masks do not depend on the tiling).
-template <bool TRACE, bool TR>
+template <bool TRACE, bool TR, bool LIVE = false>
 __global__ __launch_bounds__(fz::THREADS) void fused_encoder_h_kernel(
     const float* __restrict__ wts, const float* __restrict__ x_imu, const float* __restrict__ x_s,
     const float* __restrict__ keep_mask, float keep_scale, float* __restrict__ xout, float* __restrict__ ih_out,
-    unsigned* __restrict__ hall_sentinel, int B, int T, int NI, int S, int L, int wbytes, int ih_off_b, FusedTrain tr) {
+    unsigned* __restrict__ hall_sentinel, int B, int T, int NI, int S, int L, int wbytes, int ih_off_b, FusedEncArgs<LIVE> tr) {
     using namespace fz;
     using namespace fzh;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -841,6 +841,17 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_h_kernel(
     // this lane's LDS offsets (floats) inside a [rows][ld] operand: 16-row blocks / tail blocks
     auto am = [&](int ld) { return l15 * ld + lg * 4; };
     auto at = [&](int ld) { return (TAIL0 + (lane & 3)) * ld + lg * 4; };
+    // LIVE: the deployed forward (tip_forward_live) — the TR instantiation's four dropout sites and the past-state keep mask drawn in the
+    // prologue, no stash; the inference instantiation's outputs.  Both seeds come from lv.seeds (device, {seed, state_seed}) when given:
+    // scalar loads, and every key below is computed from them once per site on the scalar unit.
+    constexpr bool DR = TR || LIVE;
+    const LiveArgs lv = live_args_of(tr);
+    unsigned long long dseed = tr.seed, sseed = 0;
+    if (LIVE) {
+        sseed = lv.state_seed;
+        if (lv.seeds) { dseed = lv.seeds[0]; sseed = lv.seeds[1]; }
+    }
+    const unsigned mkey = LIVE && lv.mthresh ? tip_drop_key_s(sseed, kStateMaskSite) : 0u;
 
     // rows 40..47 of the residual stream: zero once, never written again (finite pad keys / values for the attention)
     for (int i = tid; i < 8 * LDX; i += THREADS) X[TMAX * LDX + i] = 0.f;
@@ -897,6 +908,8 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_h_kernel(
                             float v = vs[j][q];
                             if (v != v) v = 0.f;                               // :65
                             if (keep_mask) v = v * vk[j][q] * keep_scale;     // :77 with an explicit keep-mask
+                            else if (LIVE && lv.mthresh)                       // ... or drawn here: tip_draw_keep_mask's decision of this element of x_s
+                                v = v * (tip_drop_hash_k(mkey, ((unsigned)win * (unsigned)T + (unsigned)(wave + 8 * j)) * (unsigned)S + (unsigned)(lane + 64 * q)) >= lv.mthresh ? 1.f : 0.f) * keep_scale;
                             pu_s[8 * j * LDU + 64 * q] = v;
                         }
                 }
@@ -937,9 +950,9 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_h_kernel(
             const float* LW = wts + LAYER0 + (size_t)layer * LAYER_FLOATS;
             const int lbase = (int)((LAYER0 + (size_t)layer * LAYER_FLOATS) * 4);
             float* svl = TR ? tr.sv + (size_t)layer * tr.layer_stride * 64 : nullptr;   // this layer's stash
-            const unsigned dk1 = TR ? tip_drop_key_s(tr.seed, (unsigned)(layer * 4 + 1)) : 0u;
-            const unsigned dk2 = TR ? tip_drop_key_s(tr.seed, (unsigned)(layer * 4 + 2)) : 0u;
-            const unsigned dk3 = TR ? tip_drop_key_s(tr.seed, (unsigned)(layer * 4 + 3)) : 0u;
+            const unsigned dk1 = DR ? tip_drop_key_s(dseed, (unsigned)(layer * 4 + 1)) : 0u;
+            const unsigned dk2 = DR ? tip_drop_key_s(dseed, (unsigned)(layer * 4 + 2)) : 0u;
+            const unsigned dk3 = DR ? tip_drop_key_s(dseed, (unsigned)(layer * 4 + 3)) : 0u;
             float bvo[2], bv2[2];   // out-projection / linear2 biases of this wave's columns: requested a phase (or eight) ahead of their use
 #pragma unroll
             for (int n = 0; n < 2; ++n) {
@@ -1019,6 +1032,9 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_h_kernel(
                     attention_head_regs<LDX, true>(qt, kt, vv, Oc, head * 16, lo, TMAX, svl + (size_t)tr.ast * 64,
                                                    (unsigned long long)win * H + head, T, tr.seed, (unsigned)(layer * 4 + 0), tr.thresh,
                                                    tr.scale);
+                } else if (LIVE) {   // dropout on the probabilities as TR draws it, no statistics
+                    attention_head_regs<LDX, true, false>(qt, kt, vv, Oc, head * 16, opaque(lane), TMAX, nullptr, (unsigned long long)win * H + head, T,
+                                                          dseed, (unsigned)(layer * 4 + 0), tr.thresh, tr.scale);
                 } else {
                     attention_head_regs<LDX>(qt, kt, vv, Oc, head * 16, lane, TMAX);   // rows 40..47 of the O plane are never read
                 }
@@ -1054,20 +1070,21 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_h_kernel(
             for (int n = 0; n < 2; ++n) {
                 const int col = (wave * 2 + n) * 16 + l15;
                 const float bv = bvo[n];
+                    const int hl = LIVE ? opaque(lane) : lane, hlg = LIVE ? hl >> 4 : lg, hcol = LIVE ? (wave * 2 + n) * 16 + (hl & 15) : col;   // (LIVE: the hash indices are formed here, not hoisted out of the layer loop and spilled)
 #pragma unroll
                 for (int r = 0; r < RBM; ++r)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float v = acc_o[r][n][e] + bv;
-                        if (TR && tr.thresh)
-                            v = tip_drop_hash_k(dk1, (grow0 + r * 16 + lg * 4 + e) * D + col) >= tr.thresh ? v * tr.scale : 0.f;
+                        if (DR && tr.thresh)
+                            v = tip_drop_hash_k(dk1, (grow0 + r * 16 + hlg * 4 + e) * D + hcol) >= tr.thresh ? v * tr.scale : 0.f;
                         X[(r * 16 + lg * 4 + e) * LDX + col] = xr[n][r][e] + v;
                     }
 #pragma unroll
                 for (int r = 0; r < RBT; ++r) {
                     float v = tail_reduce(acc_ot[r][n], lg) + bv;
-                    if (TR && tr.thresh)
-                        v = tip_drop_hash_k(dk1, (grow0 + TAIL0 + 4 * r + lg) * D + col) >= tr.thresh ? v * tr.scale : 0.f;
+                    if (DR && tr.thresh)
+                        v = tip_drop_hash_k(dk1, (grow0 + TAIL0 + 4 * r + hlg) * D + hcol) >= tr.thresh ? v * tr.scale : 0.f;
                     X[(TAIL0 + 4 * r + lg) * LDX + col] = xt[n][r] + v;
                 }
             }
@@ -1101,20 +1118,21 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_h_kernel(
                     for (int n = 0; n < 2; ++n) {
                         const int col = (wave * 2 + n) * 16 + l15;
                         const float bv = bv1[n];
+                    const int hl = LIVE ? opaque(lane) : lane, hlg = LIVE ? hl >> 4 : lg, hcol = LIVE ? (wave * 2 + n) * 16 + (hl & 15) : col;   // (LIVE: the hash indices are formed here, not hoisted out of the layer loop and spilled)
 #pragma unroll
                         for (int r = 0; r < RBM; ++r)
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
                                 float v = fmaxf(acc[r][n][e] + bv, 0.f);
-                                if (TR && tr.thresh)
-                                    v = tip_drop_hash_k(dk2, (grow0 + r * 16 + lg * 4 + e) * F + f * 256 + col) >= tr.thresh ? v * tr.scale : 0.f;
+                                if (DR && tr.thresh)
+                                    v = tip_drop_hash_k(dk2, (grow0 + r * 16 + hlg * 4 + e) * F + f * 256 + hcol) >= tr.thresh ? v * tr.scale : 0.f;
                                 Hc[(r * 16 + lg * 4 + e) * LDX + col] = v;
                             }
 #pragma unroll
                         for (int r = 0; r < RBT; ++r) {
                             float v = fmaxf(tail_reduce(acct[r][n], lg) + bv, 0.f);
-                            if (TR && tr.thresh)
-                                v = tip_drop_hash_k(dk2, (grow0 + TAIL0 + 4 * r + lg) * F + f * 256 + col) >= tr.thresh ? v * tr.scale : 0.f;
+                            if (DR && tr.thresh)
+                                v = tip_drop_hash_k(dk2, (grow0 + TAIL0 + 4 * r + hlg) * F + f * 256 + hcol) >= tr.thresh ? v * tr.scale : 0.f;
                             Hc[(TAIL0 + 4 * r + lg) * LDX + col] = v;
                         }
                     }
@@ -1150,20 +1168,21 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_h_kernel(
             for (int n = 0; n < 2; ++n) {
                 const int col = (wave * 2 + n) * 16 + l15;
                 const float bv = bv2[n];
+                    const int hl = LIVE ? opaque(lane) : lane, hlg = LIVE ? hl >> 4 : lg, hcol = LIVE ? (wave * 2 + n) * 16 + (hl & 15) : col;   // (LIVE: the hash indices are formed here, not hoisted out of the layer loop and spilled)
 #pragma unroll
                 for (int r = 0; r < RBM; ++r)
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float v = acc_f[r][n][e] + bv;
-                        if (TR && tr.thresh)
-                            v = tip_drop_hash_k(dk3, (grow0 + r * 16 + lg * 4 + e) * D + col) >= tr.thresh ? v * tr.scale : 0.f;
+                        if (DR && tr.thresh)
+                            v = tip_drop_hash_k(dk3, (grow0 + r * 16 + hlg * 4 + e) * D + hcol) >= tr.thresh ? v * tr.scale : 0.f;
                         X[(r * 16 + lg * 4 + e) * LDX + col] = xr[n][r][e] + v;
                     }
 #pragma unroll
                 for (int r = 0; r < RBT; ++r) {
                     float v = tail_reduce(acc_ft[r][n], lg) + bv;
-                    if (TR && tr.thresh)
-                        v = tip_drop_hash_k(dk3, (grow0 + TAIL0 + 4 * r + lg) * D + col) >= tr.thresh ? v * tr.scale : 0.f;
+                    if (DR && tr.thresh)
+                        v = tip_drop_hash_k(dk3, (grow0 + TAIL0 + 4 * r + hlg) * D + hcol) >= tr.thresh ? v * tr.scale : 0.f;
                     X[(TAIL0 + 4 * r + lg) * LDX + col] = xt[n][r] + v;
                 }
             }
@@ -1290,6 +1309,29 @@ hipError_t launch_fused_train_h(const Dims& d, const float* fused_w, const float
     hipLaunchKernelGGL((fused_encoder_h_kernel<false, true>), dim3(grid), dim3(fz::THREADS), fz::LDS_BYTES, s, fused_w, x_imu, x_s,
                        keep_mask, keep_scale, (float*)nullptr, ih_out, reinterpret_cast<unsigned*>(hall_sentinel), B, T, d.n_imu_total,
                        d.S, d.L, (int)(fused_packed_floats(d) * 4), (int)(fused_ih_off(d) * 4), tr);
+    return hipGetLastError();
+}
+
+// the deployed forward (tip_forward_live): dropout sites and keep mask live, nothing stashed, inference outputs
+hipError_t launch_fused_live_h(const Dims& d, const float* fused_w, const float* x_imu, const float* x_s, const float* keep_mask,
+                               float keep_scale, float* xout, float* ih_out, float* hall_sentinel, const FusedTrain& tr,
+                               const LiveArgs& lv, int B, int T, int num_cus, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    if (!fused_supported(d, T) || !fused_has_rnn_ih(d)) return hipErrorInvalidValue;
+    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_encoder_h_kernel<false, false, true>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, fz::LDS_BYTES);
+        if (e != hipSuccess) return e;
+        attr_set = true;
+    }
+    const int grid = B < num_cus ? B : num_cus;
+    LiveTrain lt;
+    static_cast<FusedTrain&>(lt) = tr;
+    lt.lv = lv;
+    hipLaunchKernelGGL((fused_encoder_h_kernel<false, false, true>), dim3(grid), dim3(fz::THREADS), fz::LDS_BYTES, s, fused_w, x_imu, x_s,
+                       keep_mask, keep_scale, xout, ih_out, reinterpret_cast<unsigned*>(hall_sentinel), B, T, d.n_imu_total, d.S, d.L,
+                       (int)(fused_packed_floats(d) * 4), (int)(fused_ih_off(d) * 4), lt);
     return hipGetLastError();
 }
 

@@ -55,6 +55,13 @@ __host__ __device__ __forceinline__ unsigned tip_drop_key(unsigned long long see
     z ^= z >> 31;
     return (unsigned)(z >> 32);
 }
+// the successor of a seed under tip_seeds_next (include/tip_hip.h): one splitmix64 step
+__host__ __device__ __forceinline__ unsigned long long tip_seed_successor(unsigned long long s) {
+    unsigned long long z = s + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
 // kernels compute the key ONCE (wave-uniform, forced into an SGPR) and hash elements with tip_drop_hash_k
 __device__ __forceinline__ unsigned tip_drop_key_s(unsigned long long seed, unsigned site) {
     return (unsigned)__builtin_amdgcn_readfirstlane((int)tip_drop_key(seed, site));
@@ -84,6 +91,23 @@ struct FusedTrain {
     unsigned thresh;   // 0 = dropout off
     float scale;
 };
+
+// What the hybrid encoder's LIVE mode (tip_forward_live: dropout sites and keep mask live, nothing stashed) needs beyond FusedTrain's
+// seed / thresh / scale: the past-state keep mask's draw, and where the two seeds live when they are device values.
+struct LiveArgs {
+    const unsigned long long* seeds = nullptr;   // DEVICE {seed, state_seed}: read instead of FusedTrain::seed / state_seed below
+    unsigned long long state_seed = 0;
+    unsigned mthresh = 0;                        // keep-mask threshold (state_mask_params); 0 = no mask drawn in the kernel
+};
+// The hybrid kernel's last argument: FusedTrain for the inference and training instantiations (their kernel-argument block, and with it
+// their code, is what it was before the live mode existed), FusedTrain + LiveArgs for the live one.
+struct LiveTrain : FusedTrain {
+    LiveArgs lv;
+};
+template <bool LIVE>
+using FusedEncArgs = std::conditional_t<LIVE, LiveTrain, FusedTrain>;
+__host__ __device__ __forceinline__ LiveArgs live_args_of(const FusedTrain&) { return LiveArgs{}; }
+__host__ __device__ __forceinline__ LiveArgs live_args_of(const LiveTrain& t) { return t.lv; }
 
 constexpr int kGemmBM = 128;   // general GEMM block tile (rows)
 constexpr int kGemmBN = 128;   // general GEMM block tile (cols); packed weights are padded to this
@@ -449,6 +473,11 @@ hipError_t launch_fused_train(const Dims& d, const float* fused_w, const float* 
 hipError_t launch_fused_train_h(const Dims& d, const float* fused_w, const float* x_imu, const float* x_s, const float* keep_mask,
                                 float keep_scale, float* ih_out, float* hall_sentinel, const FusedTrain& tr, int B, int T,
                                 int num_cus, hipStream_t s);
+// the hybrid kernel's LIVE mode (tip_forward_live): tr carries seed / thresh / scale only (no stash: tr.sv is not read); xout / ih_out
+// as launch_fused_encoder_h.  hipErrorInvalidValue where launch_fused_train_h would answer it.
+hipError_t launch_fused_live_h(const Dims& d, const float* fused_w, const float* x_imu, const float* x_s, const float* keep_mask,
+                               float keep_scale, float* xout, float* ih_out, float* hall_sentinel, const FusedTrain& tr,
+                               const LiveArgs& lv, int B, int T, int num_cus, hipStream_t s);
 // true when launch_rnn(cluster) will run the sentinel-polling resident kernel (HALL must be pre-filled with all-ones;
 // the fused encoder can do that for its own rows, otherwise launch_rnn memsets)
 bool rnn_uses_sentinel(const Dims& d, int B, int T, int cluster);
@@ -474,12 +503,16 @@ struct TrainDropout {
     unsigned thresh;
     float scale;
     unsigned mkey = 0, mthresh = 0;   // past-state keep mask drawn in the kernel (mthresh 0: not): see tip_draw_keep_mask
+    // tip_forward_live: DEVICE {seed, state_seed}, read by the kernels instead of `seed` and of the host's `mkey` (null: the fields above)
+    const unsigned long long* seeds_dev = nullptr;
+    unsigned long long state_seed = 0;   // (the hybrid live mode derives its own mask key)
 };
 TrainDropout make_train_dropout(float p, unsigned long long seed);
 constexpr unsigned kStateMaskSite = 0xFFFFFFF0u;   // hash site of the past-state keep mask (encoder sites are 4 * layer + k)
 // (key, thresh) of a keep mask with drop probability p under `seed`; false for p outside [0, 1)
 bool state_mask_params(float p, unsigned long long seed, unsigned* key, unsigned* thresh);
 hipError_t launch_keep_mask(float* mask, size_t n, unsigned key, unsigned thresh, hipStream_t s);
+hipError_t launch_seeds_next(unsigned long long* seeds, hipStream_t s);
 // What the ONE-launch form of the plan (lat_flow_kernel, few windows: stages, recurrence and output projection as roles of one
 // launch) needs beyond the chain's arguments; null = launch chain.  *done says whether the projection ran inside (then the caller
 // launches no launch_latency_head).

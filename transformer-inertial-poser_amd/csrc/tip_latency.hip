@@ -55,7 +55,10 @@ struct LatDrop {
     unsigned thresh = 0;
     float scale = 1.f;
     unsigned site = 0;      // 4 * layer + {0: attention probabilities, 1: out-projection output, 2: hidden after ReLU, 3: linear2 output}
+    const unsigned long long* sdev = nullptr;   // tip_forward_live: DEVICE {seed, state_seed}; word 0 is read instead of `seed`
 };
+// the site's key, once per kernel on the scalar unit — from the device seed where there is one
+__device__ __forceinline__ unsigned lat_drop_key(const LatDrop& dr) { return tip_drop_key_s(dr.sdev ? dr.sdev[0] : dr.seed, dr.site); }
 
 // ---- dataflow form (lat_flow_kernel below): the stages of a forward as ROLES of one launch ------------------------------------
 // A stage body is written once, for both forms.  FLOW = false: a kernel of its own (the launch chain: stream order is the
@@ -237,7 +240,12 @@ struct LatInArgs {
     float* xpre; int T, NI, S, in_w_off_b, in_b_off;
     unsigned long long* gran; unsigned* xcc_words; unsigned mkey, mthresh;
     const float* ubuf;       // one-launch form: the window rows [T][224] as the prologue role left them (:63-78 applied); null: gather here
+    const unsigned long long* sdev = nullptr;   // tip_forward_live: DEVICE {seed, state_seed}; the mask key comes from word 1, not from `mkey`
 };
+// (once per kernel, wave-uniform; only where a mask is drawn at all)
+__device__ __forceinline__ void lat_resolve_mkey(LatInArgs& a) {
+    if (a.mthresh && a.sdev) a.mkey = tip_drop_key_s(a.sdev[1], kStateMaskSite);
+}
 // The value the prologue (:63-78) puts at column c of row `row` of window `win`: x_imu | NaN-scrubbed, kept, scaled x_s | zero pad.
 // ONE expression for the launch chain's gather (lat_in_body) and the one-launch form's prologue role: same bits.
 __device__ __forceinline__ float lat_prologue_value(const LatInArgs& a, int win, int row, int c, bool skip_hash) {
@@ -358,6 +366,7 @@ __device__ __forceinline__ void lat_in_body(const LatInArgs& a, int nb, int win,
 }
 __global__ __launch_bounds__(256) void lat_in_kernel(LatInArgs a) {
     __shared__ __attribute__((aligned(16))) float smem[kLatInSmem];
+    lat_resolve_mkey(a);
     lat_in_body<false>(a, blockIdx.x, blockIdx.y, smem, nullptr);
 }
 
@@ -397,7 +406,7 @@ __device__ __forceinline__ void lat_ln_gemm_body(const LatLnArgs& a, int nb0, in
                              (a.stats && nb0 == 0) ? a.stats + (size_t)win * RP * 2 : nullptr, act);
     __syncthreads();
     const LatDrop dr = a.dr;
-    const unsigned dkey = DROP ? tip_drop_key_s(dr.seed, dr.site) : 0u;
+    const unsigned dkey = DROP ? lat_drop_key(dr) : 0u;
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
         const int nb = nb0 * NCB + cb;
@@ -489,7 +498,7 @@ __device__ __forceinline__ void lat_qkv_attn_body(const LatQkvArgs& a, int head,
     // of the stage's 6.8).  A wave reads its own Q rows and the K / V rows at or below them and writes O over its own Q rows only.
     {
         const LatDrop dr = a.dr;
-        const unsigned dk = DROP ? tip_drop_key_s(dr.seed, dr.site) : 0u;
+        const unsigned dk = DROP ? lat_drop_key(dr) : 0u;
         const unsigned long long bh = (unsigned long long)win * 16 + head;
         if (wave == 0) attention_head_mfma<DH + 4, RP + 4, DROP, 0, 1>(Qs, Ks, Vts, 0, lane, 48, dk, dr.thresh, dr.scale, bh, T);
         else if (wave == 1) attention_head_mfma<DH + 4, RP + 4, DROP, 1, 2>(Qs, Ks, Vts, 0, lane, 48, dk, dr.thresh, dr.scale, bh, T);
@@ -590,7 +599,7 @@ __device__ __forceinline__ void lat_res_gemm_body(const LatResArgs& a, int nb, i
         for (int wv = 0; wv < NW * PARTS; ++wv) s += *reinterpret_cast<const f32x4*>(red + ((wv * 3 + wave) * 64 + lane) * 4);
     }
     const LatDrop dr = a.dr;
-    const unsigned dkey = DROP ? tip_drop_key_s(dr.seed, dr.site) : 0u;
+    const unsigned dkey = DROP ? lat_drop_key(dr) : 0u;
     if (wave < RB) {
         float* o = a.out + (size_t)win * T * D;
 #pragma unroll
@@ -971,6 +980,7 @@ struct LatFlowArgs {
     const int* rows;                       // tip_forward_rows (null: last_only decides): row rows[win] of each window
     int B, T, NI, S, L;
     unsigned mkey, mthresh;
+    const unsigned long long* sdev;        // tip_forward_live: DEVICE {seed, state_seed} (null: dr.seed / mkey)
     LatDrop dr;
     Guard gd;
     int trace;                             // measurement (TIP_FLOW_TRACE=1): stamp g_flow_trace
@@ -1021,7 +1031,8 @@ __global__ __launch_bounds__(256) void lat_flow_kernel(LatFlowArgs a) {
     constexpr size_t G1 = W2_B + D, BE1 = G1 + D, G2 = BE1 + D, BE2 = G2 + D, LAYER_FLOATS = BE2 + D;
     if (stage <= 1) {
         LatInArgs ia{a.wts, a.wbytes, a.x_imu, a.x_s, a.keep_mask, a.keep_scale, a.xa, T, a.NI, a.S, (int)(IN_W * 4), (int)IN_B,
-                     a.gran, a.xccw, a.mkey, a.mthresh, a.ubuf};
+                     a.gran, a.xccw, a.mkey, a.mthresh, a.ubuf, a.sdev};
+        lat_resolve_mkey(ia);
         if (stage == 0) {                                 // prologue (:63-78): the window's rows, once
             FLOW_STAMP(1);
             lat_pre_role(ia, a.ubuf, nb, win);
@@ -1166,8 +1177,9 @@ hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float*
         fa.rows = head->rows;
         fa.B = B; fa.T = T; fa.NI = d.n_imu_total; fa.S = d.S; fa.L = d.L;
         fa.mkey = td ? td->mkey : 0u; fa.mthresh = td && !keep_mask ? td->mthresh : 0u;
+        fa.sdev = td ? td->seeds_dev : nullptr;
         fa.dr = LatDrop{};
-        if (td) { fa.dr.seed = td->seed; fa.dr.thresh = td->thresh; fa.dr.scale = td->scale; }
+        if (td) { fa.dr.seed = td->seed; fa.dr.thresh = td->thresh; fa.dr.scale = td->scale; fa.dr.sdev = td->seeds_dev; }
         fa.gd = gd;
         static const int trace_on = (tip_env("TIP_FLOW_TRACE") && tip_env("TIP_FLOW_TRACE")[0] == '1') ? 1 : 0;
         fa.trace = trace_on;
@@ -1180,7 +1192,7 @@ hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float*
     } else {
         hipLaunchKernelGGL(lat_in_kernel, dim3(16, B), dim3(256), 0, s,
                            LatInArgs{fused_w, wbytes, x_imu, x_s, keep_mask, keep_scale, xa, T, d.n_imu_total, d.S, (int)(IN_W * 4), (int)IN_B,
-                                     gran, xccw, td ? td->mkey : 0u, td && !keep_mask ? td->mthresh : 0u, nullptr});
+                                     gran, xccw, td ? td->mkey : 0u, td && !keep_mask ? td->mthresh : 0u, nullptr, td ? td->seeds_dev : nullptr});
         const float* pg = nullptr;   // LayerNorm pending on the residual stream (norm2 of the previous layer)
         const float* pb = nullptr;
         for (int l = 0; l < d.L; ++l) {
@@ -1188,7 +1200,7 @@ hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float*
             const float* LW = fused_w + lo;
             // xa = pre-norm input of the layer; st0 = its row statistics (when pg != null)
             LatDrop dr;
-            if (td) { dr.seed = td->seed; dr.thresh = td->thresh; dr.scale = td->scale; }
+            if (td) { dr.seed = td->seed; dr.thresh = td->thresh; dr.scale = td->scale; dr.sdev = td->seeds_dev; }
             auto site = [&](unsigned k) { LatDrop x = dr; x.site = (unsigned)l * 4u + k; return x; };
             const LatQkvArgs qa{fused_w, wbytes, xa, pg, pb, (int)((lo + QKV_W) * 4), (int)(lo + QKV_B), o, st0, T, site(0)};
             const LatResArgs oa{fused_w, wbytes, o, D, xa, st0, pg, pb, (int)((lo + WO_W) * 4), (int)(lo + WO_B), xb, T, site(1)};
@@ -1235,6 +1247,14 @@ hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float*
 __global__ void keep_mask_kernel(float* __restrict__ mask, size_t n, unsigned key, unsigned thresh) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
         mask[i] = tip_drop_hash_k(key, (unsigned)i) >= thresh ? 1.f : 0.f;
+}
+// tip_seeds_next: each of the two words <- its splitmix64 successor (include/tip_hip.h has the formula); one lane per word, plain stores
+__global__ void seeds_next_kernel(unsigned long long* __restrict__ seeds) {
+    if (threadIdx.x < 2) seeds[threadIdx.x] = tip_seed_successor(seeds[threadIdx.x]);
+}
+hipError_t launch_seeds_next(unsigned long long* seeds, hipStream_t s) {
+    hipLaunchKernelGGL(seeds_next_kernel, dim3(1), dim3(64), 0, s, seeds);
+    return hipGetLastError();
 }
 hipError_t launch_keep_mask(float* mask, size_t n, unsigned key, unsigned thresh, hipStream_t s) {
     if (!n) return hipSuccess;

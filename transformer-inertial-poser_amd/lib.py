@@ -40,6 +40,7 @@ EXPORTS = (
     "tip_reuse_cache_bytes", "tip_reuse_reset", "tip_forward_reuse", "tip_stream_frame_counter_offset", "tip_stream_ingest_newest",
     "tip_forward_rows", "tip_stream_attach", "tip_stream_detach", "tip_stream_ingest_staggered", "tip_stream_consume_staggered",
     "tip_stream_ingest_mapped", "tip_stream_consume_mapped", "tip_stream_reset_shaped", "tip_stream_history_override",
+    "tip_forward_live", "tip_seeds_next",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
     "tip_train_bytes_f64", "tip_train_forward_f64", "tip_train_backward_f64",
     "tip_combine_frames", "tip_combine_scratch_bytes", "tip_combine_sequence", "tip_gather_windows",
@@ -154,6 +155,9 @@ def load() -> ctypes.CDLL:
     lib.tip_forward_reuse.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, sz, i32, vp, vp, sz, vp]
     lib.tip_stream_frame_counter_offset.argtypes = [ctypes.POINTER(sz)]
     lib.tip_forward_rows.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, ctypes.c_float, vp, sz, vp]
+    lib.tip_forward_live.argtypes = [vp, vp, vp, vp, i32, i32, vp, i32, vp, ctypes.c_float, ctypes.c_float, ctypes.c_uint64, ctypes.c_float,
+                                     ctypes.c_uint64, vp, vp, sz, vp]
+    lib.tip_seeds_next.argtypes = [vp, vp]
     lib.tip_stream_attach.argtypes = [vp, i32, vp, vp, i32, vp]
     lib.tip_stream_detach.argtypes = [vp, i32, vp, i32, vp]
     lib.tip_stream_ingest_staggered.argtypes = [vp, vp, i32, vp, vp, vp, vp]
@@ -306,6 +310,14 @@ class Handle:
         self._check(self.lib.tip_forward_dropout(self._h, x_imu, x_s, y, B, T, flags, keep_mask, keep_scale, p_state, state_seed, p_drop,
                                                  seed, workspace, workspace_bytes, stream))
 
+    def forward_live(self, x_imu: int, x_s: int, y: int, B: int, T: int, rows: Optional[int], flags: int, keep_mask: Optional[int],
+                     keep_scale: float, p_state: float, state_seed: int, p_drop: float, seed: int, seeds_dev: Optional[int],
+                     workspace: int, workspace_bytes: int, stream: int):
+        """tip_forward_live: the deployed forward (encoder dropout and past-state keep mask live, no stash) at any batch; seeds_dev: device
+        uint64 [2] = {seed, state_seed} read by the kernels instead of the two arguments."""
+        self._check(self.lib.tip_forward_live(self._h, x_imu, x_s, y, B, T, rows, flags, keep_mask, keep_scale, p_state, state_seed, p_drop,
+                                              seed, seeds_dev, workspace, workspace_bytes, stream))
+
     # -- training step (train_model.py:171-196) -------------------------------------------------------
     def train_bytes(self, B: int, T: int, fp64: bool = False) -> Tuple[int, int]:
         """(saved_bytes, scratch_bytes); raises TipStatusError(-2: unsupported config) when the HIP training path
@@ -380,6 +392,24 @@ class Handle:
 def draw_keep_mask(p_state: float, state_seed: int, mask_ptr: int, n: int, stream: int):
     """tip_draw_keep_mask: the past-state keep decisions of (p_state, state_seed) as n floats (0 / 1) at device pointer mask_ptr."""
     st = load().tip_draw_keep_mask(p_state, state_seed, mask_ptr, n, stream)
+    if st < 0:
+        raise TipStatusError(st, load().tip_strerror(st).decode())
+
+
+_M64 = (1 << 64) - 1
+
+
+def seed_successor(s: int) -> int:
+    """What tip_seeds_next puts in place of the seed word `s`: one splitmix64 step (include/tip_hip.h has the formula)."""
+    z = (s + 0x9E3779B97F4A7C15) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def seeds_next(seeds_ptr: int, stream: int):
+    """tip_seeds_next: both words of the device uint64 [2] at seeds_ptr <- their successors (seed_successor), one tiny launch."""
+    st = load().tip_seeds_next(seeds_ptr, stream)
     if st < 0:
         raise TipStatusError(st, load().tip_strerror(st).decode())
 

@@ -213,6 +213,105 @@ class TF_RNN_Past_State(nn.Module):
             raise RuntimeError("tip_amd: rows must be an int32 CUDA tensor [B] on the inputs' device")
         return self._forward_hip(x_imu, x_s, True, workspace=workspace, out=out, rows=rows.contiguous())
 
+    def forward_live(self, x_imu, x_s, *, rows=None, last_row_only=True, seeds=None, seeds_dev=None, workspace=None, out=None):
+        """The forward as the reference DEPLOYS the model (every shipped loader builds it with past_state_dropout = 0.8 and never calls
+        .eval()), at any batch, on kernels of its own (include/tip_hip.h: tip_forward_live): the past-state keep mask (:77) is drawn
+        inside the first kernel — no mask tensor, no torch.rand_like — and, in .train() mode, the encoder's four dropout sites per layer
+        are live at ENCODER_DROPOUT (in .eval() only the keep mask is); no activation stash is written and nothing is recorded for
+        autograd (torch.no_grad()).  fp32 CUDA tensors only; in_dropout > 0 raises (no shipped loader sets it).
+        Output: [B, size_s] — row T-1 of every window (last_row_only, the default) or row rows[b] of window b (rows: int32 CUDA tensor
+        [B]; an index outside [0, T) gives an all-NaN row) — or the full [B, T, size_s] with last_row_only=False and no rows.
+        seeds: (encoder seed, state seed); default: _draw_seeds(), so torch.manual_seed governs the masks.  The keep decisions are the
+        training step's for the same seeds (same hash, same element indices; state mask = lib.draw_keep_mask).  seeds_dev: an int64
+        CUDA tensor [2] holding the same two values instead — read by the kernels at launch time, so that a captured HIP graph of
+        "lib.seeds_next(seeds_dev), forward_live(..., seeds_dev=...)" draws fresh masks at every replay.
+        Batches above chunk_batch(T) run in chunks of that size: chunk k uses BOTH seeds advanced k times by the tip_seeds_next rule
+        (lib.seed_successor), so no two chunks share decisions — the element indices restart at 0 in every chunk.  (seeds_dev,
+        workspace= and out= serve a single launch sequence and raise beyond it.)  workspace / out as forward_last's."""
+        if self.in_dropout > 0.0:
+            raise RuntimeError("tip_amd: forward_live does not serve in_dropout > 0 (no shipped loader of the reference sets it)")
+        if not (x_imu.is_cuda and x_s.is_cuda) or x_imu.dtype != torch.float32 or x_s.dtype != torch.float32 or \
+                self.in_linear.weight.dtype != torch.float32:
+            raise RuntimeError("tip_amd: forward_live serves fp32 windows and parameters on the GPU")
+        if x_imu.dim() != 3 or x_s.dim() != 3 or x_imu.shape[:2] != x_s.shape[:2]:
+            raise RuntimeError("expected x_imu [B,T,n_imu] and x_s [B,T,size_s]")
+        B, T = int(x_imu.shape[0]), int(x_imu.shape[1])
+        n_imu = self.input_size_imu + (18 if self.with_acc_sum else 0)
+        if x_imu.shape[2] != n_imu or x_s.shape[2] != self.size_s:
+            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied: got feature widths "
+                               f"{x_imu.shape[2]}+{x_s.shape[2]}, in_linear expects {n_imu}+{self.size_s}")
+        dev = x_imu.device
+        if rows is not None:
+            if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_cuda or
+                    rows.shape[0] != B or rows.device != dev):
+                raise RuntimeError("tip_amd: rows must be an int32 CUDA tensor [B] on the inputs' device")
+            rows = rows.contiguous()
+            last_row_only = True
+        if seeds_dev is not None:
+            if seeds is not None:
+                raise RuntimeError("tip_amd: forward_live takes seeds= or seeds_dev=, not both")
+            if (not isinstance(seeds_dev, torch.Tensor) or seeds_dev.dtype != torch.int64 or seeds_dev.numel() != 2 or
+                    seeds_dev.device != dev or not seeds_dev.is_contiguous()):
+                raise RuntimeError("tip_amd: seeds_dev must be a contiguous int64 CUDA tensor [2] on the inputs' device")
+            seeds = (0, 0)
+        elif seeds is None:
+            seeds = self._draw_seeds()
+        seeds = (int(seeds[0]) & _lib._M64, int(seeds[1]) & _lib._M64)
+        h = self._ensure_handle()
+        max_b = self.chunk_batch(T)
+        if B > max_b:
+            if workspace is not None or out is not None or seeds_dev is not None:
+                raise RuntimeError("tip_amd: workspace= / out= / seeds_dev= serve a single launch sequence (batch within tip_max_batch)")
+            parts = []
+            for lo in range(0, B, max_b):
+                hi = min(B, lo + max_b)
+                parts.append(self.forward_live(x_imu[lo:hi], x_s[lo:hi], rows=None if rows is None else rows[lo:hi],
+                                               last_row_only=last_row_only, seeds=seeds))
+                seeds = (_lib.seed_successor(seeds[0]), _lib.seed_successor(seeds[1]))
+            return torch.cat(parts, dim=0)
+        p_state = float(self.past_state_dropout)
+        if not 0.0 <= p_state < 1.0:
+            raise RuntimeError("tip_amd: forward_live needs 0 <= past_state_dropout < 1")
+        p_drop = float(self.ENCODER_DROPOUT) if self.training else 0.0
+        scale = 1.0 / (1.0 - p_state) if p_state > 0.0 else 1.0
+        flags = _lib.TIP_FWD_LAST_ROW_ONLY if last_row_only else 0
+        shape = (B, self.size_s) if last_row_only else (B, T, self.size_s)
+        with torch.no_grad(), (torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _NO_CTX):
+            if self._packed_dev is None or self._packed_dev.device != dev or (not self._frozen and self._packed_key != self._param_key(dev)):
+                self.refresh_packed(dev)
+            xi, xs = x_imu.contiguous(), x_s.contiguous()
+            if out is not None:
+                if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+                    raise RuntimeError(f"tip_amd: out= must be a contiguous float32 tensor of shape {shape} on {dev}")
+                y = out
+            else:
+                y = torch.empty(shape, dtype=torch.float32, device=dev)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            need = self._ws_bytes_cache.get((B, T))
+            if need is None:
+                need = self._ws_bytes_cache[(B, T)] = h.workspace_bytes(B, T)
+            if workspace is not None:
+                if workspace.dtype != torch.uint8 or workspace.device != dev or workspace.numel() < need or workspace.data_ptr() % 256:
+                    raise RuntimeError(f"tip_amd: workspace= must be a 256-byte aligned uint8 tensor of >= {need} bytes on {dev}")
+                ws = workspace
+            else:
+                ws = self._stream_buffer(self._workspace, dev, stream, need)
+
+            def launch():
+                h.forward_live(xi.data_ptr(), xs.data_ptr(), y.data_ptr(), B, T, None if rows is None else rows.data_ptr(), flags, None, scale,
+                               p_state, seeds[1], p_drop, seeds[0], None if seeds_dev is None else seeds_dev.data_ptr(), ws.data_ptr(),
+                               ws.numel(), stream)
+            try:
+                launch()
+            except _lib.TipHandoffError:
+                # an EARLIER launch lost a hand-off: the host's answer is _forward_hip's (one-launch form off, or the handle demoted —
+                # tip_forward_live serves a demoted handle on the hybrid encoder's live mode), then THIS call runs
+                if self._answer_handoff(h) is None:
+                    raise
+                self._fast_state = None
+                launch()
+        return y
+
     def reuse_cache(self, n_streams: int) -> torch.Tensor:
         """A cleared ring for forward_last_reuse: 40 slots x 4 KiB per stream (in_linear row + layer-0 q | k | v row of each of the
         last 40 frames) behind a 256-byte header of frame tags."""

@@ -177,8 +177,11 @@ class _StreamBase:
     its own in _allocate() (once, before the first reset()), says what a lost hand-off does to it (_reprime, _REPRIMED) and supplies
     the forward that warms a capture up (_warm_forward) and the frame that is captured (_captured_frame)."""
 
-    def __init__(self, model, s_init: torch.Tensor, use_graph: bool):
+    def __init__(self, model, s_init: torch.Tensor, use_graph: bool, live_dropout: bool = False):
         self.model = model
+        # live_dropout: every frame's forward is model.forward_live (the model as the reference deploys it: past-state keep mask drawn
+        # in the first kernel, encoder dropout live in .train() mode, no stash) under the engine's own device seeds
+        self.live_dropout = bool(live_dropout)
         self.n_sbps, self.with_acc_sum = stream_shape(model)
         self.nx, self.ns, self.nc = 72 + (18 if self.with_acc_sum else 0), int(model.size_s), 4 * self.n_sbps
         self.use_graph = bool(use_graph)
@@ -190,7 +193,7 @@ class _StreamBase:
         self.device = next(model.parameters()).device
         if self.device.type != "cuda":
             raise RuntimeError("tip_amd.StreamingEngine runs on an MI355X: move the model to the GPU first")
-        if model.training:
+        if model.training and not self.live_dropout:
             import warnings
             warnings.warn("tip_amd.StreamingEngine: the model is in .train() mode — like the reference's runner without "
                           ".eval() (offline_testing_simple.py:98) every frame then draws the encoder's dropout, here through "
@@ -205,6 +208,9 @@ class _StreamBase:
         self.s_rest = torch.empty((self.n, 111), dtype=torch.float32, device=self.device)
         self.c_t = torch.empty((self.n, self.nc), dtype=torch.float32, device=self.device)
         self.raw = torch.empty((self.n, 72), dtype=torch.float32, device=self.device)    # static input of the captured graph
+        # live_dropout: {encoder seed, state seed} on the device, filled from model._draw_seeds() (torch.manual_seed governs it) at every
+        # reset and advanced by tip_seeds_next in front of every frame's forward — a frame is reproduced from the values read before it
+        self.seeds = torch.zeros(2, dtype=torch.int64, device=self.device) if self.live_dropout else None
         # captured frames by key (None: the one frame of a lock-step or plain staggered engine; a compact pool: one per bucket), each
         # (graph, workspace, packed weight image, y_last): the graph and what its kernels point at
         self._graphs, self.captures = {}, 0
@@ -228,6 +234,16 @@ class _StreamBase:
         with torch.cuda.device(self.device):
             self._check(self.lib.tip_stream_reset_shaped(self.state.data_ptr(), s_init.data_ptr(), self.n, self.n_sbps,
                                                          1 if self.with_acc_sum else 0, self._stream()))
+            if self.live_dropout:
+                self.seeds.copy_(torch.tensor(self.model._draw_seeds(), dtype=torch.int64))
+
+    def _live_forward(self, x_imu, x_s, rows, ws, out, advance=True):
+        """live_dropout: tip_seeds_next, then forward_live under the device seeds — the same two calls launch by launch and inside a
+        capture, so a replay draws what the launch-by-launch frame would have drawn.  advance=False: a capture's warm-up (its result is
+        dropped and must not cost a draw)."""
+        if advance:
+            _lib.seeds_next(self.seeds.data_ptr(), self._stream())
+        return self.model.forward_live(x_imu, x_s, rows=rows, seeds_dev=self.seeds, workspace=ws, out=out)
 
     def _forget(self):
         """Frame counter back to 0, every captured frame dropped."""
@@ -327,9 +343,16 @@ class _StreamBase:
 class StreamingEngine(_StreamBase):
     _REPRIMED = "the engine was reset (re-prime it)"
 
-    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False):
-        self.reuse = reuse          # True / False / "auto" (resolved in _allocate, once the stream count is known)
-        super().__init__(model, s_init, use_graph)
+    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False, live_dropout: bool = False):
+        """live_dropout=True: serve the model as the reference deploys it — .train() or .eval() (then only the past-state keep mask is
+        live), every frame ingest -> tip_seeds_next -> model.forward_live(seeds_dev=engine.seeds) -> consume, launch by launch and
+        captured alike: use_graph=True replays from the usual frame on with a .train() model too and reproduces launch mode bit for
+        bit.  reuse=True is refused and "auto" is off (rows differ from window to window)."""
+        if live_dropout and reuse is True:
+            raise RuntimeError("tip_amd.StreamingEngine(live_dropout=True): reuse=True is not supported — with dropout live a frame's rows "
+                               "differ from window to window")
+        self.reuse = False if live_dropout else reuse          # True / False / "auto" (resolved in _allocate, once the stream count is known)
+        super().__init__(model, s_init, use_graph, live_dropout)
 
     def _allocate(self):
         model = self.model
@@ -387,6 +410,8 @@ class StreamingEngine(_StreamBase):
                 y_last = self.model.forward_last_reuse(x_imu, x_s, self._ring, f_fwd, frame_ctr_ptr=ctr, workspace=ws, out=out)
             except _lib.TipHandoffError as e:
                 self._lost_handoff(e)
+        elif self.live_dropout:
+            y_last = self._live_forward(x_imu, x_s, None, ws, out)
         else:
             y_last = self.model.forward_last(x_imu, x_s, workspace=ws, out=out)
         if self._demotions() != mark:
@@ -396,6 +421,9 @@ class StreamingEngine(_StreamBase):
         return y_last
 
     def _warm_forward(self, key):
+        if self.live_dropout:
+            self._live_forward(self.x_imu, self.x_s, None, self._graph_ws, self._graph_y, advance=False)
+            return
         self.model.forward_last(self.x_imu, self.x_s, workspace=self._graph_ws, out=self._graph_y)   # (never touches the ring)
 
     def _captured_frame(self, key):
@@ -404,7 +432,7 @@ class StreamingEngine(_StreamBase):
     @torch.no_grad()
     def step(self, raw_imu: torch.Tensor) -> Optional[dict]:
         f = self.frame
-        if self.use_graph and f >= 44 and not self.model.training:
+        if self.use_graph and f >= 44 and (self.live_dropout or not self.model.training):
             # steady state (T = 40): one copy + one graph launch per frame
             self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
             with torch.cuda.device(self.device):
@@ -453,14 +481,17 @@ class StaggeredStreamingEngine(_StreamBase):
 
     _REPRIMED = "every attached slot was re-attached"
 
-    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False, compact: bool = False):
+    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False, compact: bool = False,
+                 live_dropout: bool = False):
+        """live_dropout=True (StreamingEngine's): a .train() model is accepted, and every frame's forward is tip_seeds_next ->
+        model.forward_live(rows=..., seeds_dev=engine.seeds) in place of forward_rows, plain and compact, launch by launch and captured."""
         if reuse:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine: reuse= is not supported (the reuse ring assumes lock-step frames)")
-        if model.training:
+        if model.training and not live_dropout:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine needs model.eval() (the inference kernels: forward_rows)")
         self.reuse, self._ring = False, None          # (lock-step only)
         self.compact = bool(compact)
-        super().__init__(model, s_init, use_graph)
+        super().__init__(model, s_init, use_graph, live_dropout)
         self.s_rest.zero_()          # (rows of slots that have not produced a row yet: defined, and unchanged until they do)
         self.c_t.zero_()
 
@@ -566,6 +597,11 @@ class StaggeredStreamingEngine(_StreamBase):
         """compact=True: the slot at each window position 0 .. k-1."""
         return list(self._positions.slot_at)
 
+    def _rows_forward(self, x_imu, x_s, rows, ws, out, advance=True):
+        if self.live_dropout:
+            return self._live_forward(x_imu, x_s, rows, ws, out, advance)
+        return self.model.forward_rows(x_imu, x_s, rows, workspace=ws, out=out)
+
     def bucket(self, k: int) -> int:
         """compact=True: the batch the forward runs on with k attached slots."""
         return pool_bucket(k, self.ladder)
@@ -577,7 +613,7 @@ class StaggeredStreamingEngine(_StreamBase):
         self._check(self.lib.tip_stream_ingest_staggered(self.state.data_ptr(), self.raw.data_ptr(), self.n, self.x_imu.data_ptr(),
                                                          self.x_s.data_ptr(), self.rows.data_ptr(), st))
         mark = self._demotions()
-        y_last = self.model.forward_rows(self.x_imu, self.x_s, self.rows, workspace=ws, out=out)
+        y_last = self._rows_forward(self.x_imu, self.x_s, self.rows, ws, out)
         if self._demotions() != mark:
             self._lost_handoff()
         self._check(self.lib.tip_stream_consume_staggered(self.state.data_ptr(), y_last.data_ptr(), self.rows.data_ptr(), self.n,
@@ -591,7 +627,7 @@ class StaggeredStreamingEngine(_StreamBase):
         self._check(self.lib.tip_stream_ingest_mapped(self.state.data_ptr(), self.raw.data_ptr(), self.n, self.slot_at.data_ptr(), B,
                                                       self.x_imu.data_ptr(), self.x_s.data_ptr(), self.rows.data_ptr(), st))
         mark = self._demotions()
-        y = self.model.forward_rows(self.x_imu[:B], self.x_s[:B], self.rows[:B], workspace=ws, out=out)
+        y = self._rows_forward(self.x_imu[:B], self.x_s[:B], self.rows[:B], ws, out)
         if self._demotions() != mark:
             self._lost_handoff()
         self._check(self.lib.tip_stream_consume_mapped(self.state.data_ptr(), y.data_ptr(), self.rows.data_ptr(), self.slot_at.data_ptr(),
@@ -621,7 +657,7 @@ class StaggeredStreamingEngine(_StreamBase):
 
     def _warm_forward(self, B):
         B = self.n if B is None else B          # (the plain engine: all n windows)
-        self.model.forward_rows(self.x_imu[:B], self.x_s[:B], self.rows[:B], workspace=self._graph_ws, out=self._graph_y[:B])
+        self._rows_forward(self.x_imu[:B], self.x_s[:B], self.rows[:B], self._graph_ws, self._graph_y[:B], advance=False)
 
     def _captured_frame(self, B):
         ws, y = self._graph_ws, self._graph_y
@@ -661,7 +697,7 @@ class StaggeredStreamingEngine(_StreamBase):
 
     @torch.no_grad()
     def step(self, raw_imu: torch.Tensor) -> dict:
-        if self.model.training:
+        if self.model.training and not self.live_dropout:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine needs model.eval() (the inference kernels: forward_rows)")
         if self.compact:
             return self._step_compact(raw_imu)
