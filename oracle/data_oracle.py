@@ -29,6 +29,13 @@ N_DOFS = 57                 # constants.py:24
 TRIM = 4                    # preprocess_and_combine_syn_amass.py:73
 
 
+def two_axis(rotvec: np.ndarray) -> np.ndarray:
+    """Axis-angles [L,54] fp64 -> the first two columns of the 18 rotation matrices, row-major 3x2 blocks [L,108], fp64 (before
+    the float32 store): data_utils.py:182-187 with scipy standing in for fairmotion's A2R."""
+    L = len(rotvec)
+    return Rotation.from_rotvec(rotvec.reshape(-1, 3)).as_matrix()[:, :, :2].reshape(L, -1)
+
+
 def combine_sequence(imu: np.ndarray, s: np.ndarray, c: np.ndarray, bias: np.ndarray, nan_root_vel: bool = False):
     """imu [L,72], s [L,114] (nimble_qdq), c [L,20] fp64 -> (IMU [L',72], SUM [L',18], S [L',131]) float32, L' = m-8."""
     s = s.copy()
@@ -48,7 +55,7 @@ def combine_sequence(imu: np.ndarray, s: np.ndarray, c: np.ndarray, bias: np.nda
     b = np.cumsum(loc[:, 54:72], axis=0)                                # :90-93
     b[ACC_SUM_WIN_LEN:] = b[ACC_SUM_WIN_LEN:] - b[:-ACC_SUM_WIN_LEN]
     batch_s = s[:, 3:N_DOFS + 3]                                        # :96: 54 axis-angles + 3 root velocity
-    r = Rotation.from_rotvec(batch_s[:, :N_DOFS - 3].reshape(-1, 3)).as_matrix()[:, :, :2].reshape(L, -1)
+    r = two_axis(batch_s[:, :N_DOFS - 3])
     s_all = np.concatenate([r, batch_s[:, -3:], c], axis=1)             # :127-128
     return np.single(loc), np.single(b / ACC_SUM_DOWN_SCALE), np.single(s_all)
 
