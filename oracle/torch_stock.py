@@ -5,6 +5,11 @@ Only tests/ and bench.py's cpu_baseline leg may import this; the product path ne
 
 Attribute names equal the reference's, so a state dict in the reference's layout (synth.make_weights) loads directly.
 Pinned against the golden vectors captured from the reference in tests/test_host_cpu.py.
+
+One difference from the reference, for non-finite data only: the root-velocity history columns 108-110 are OVERWRITTEN with zeros
+here (`zeros_like`), where the reference multiplies them by 0.0 (:75).  A +-Inf there stays out of this module's output and is NaN in
+the reference's (0 * Inf), in the C oracle's and on the HIP path (tests/test_nonfinite_oracle.py pins both).  For finite and NaN
+entries (NaN is scrubbed first, :65) the two are the same function.
 """
 from __future__ import annotations
 

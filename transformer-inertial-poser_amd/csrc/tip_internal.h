@@ -518,7 +518,8 @@ hipError_t launch_seeds_next(unsigned long long* seeds, hipStream_t s);
 // launches no launch_latency_head).
 struct LatencyHead {
     const float* wfrag; const float* bias; float* y; int ldy; int N; bool last_only;
-    unsigned long long nonce;   // the handle's stamp base (tip_handle::flow_epoch)
+    unsigned long long nonce;   // the handle's share of the stamp base (tip_handle::flow_epoch); launch_latency_plan adds a hash of
+                                // `flags`' address, so stamps written through one flag area never count in another
     bool* done;
     unsigned long long* flags;  // the workspace's flag / launch-counter area (Workspace::flow; latency_flow_flag_floats() floats)
     const int* rows = nullptr;  // tip_forward_rows: row rows[b] of window b (last_only set too: one output row per window)

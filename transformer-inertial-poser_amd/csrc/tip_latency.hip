@@ -961,6 +961,7 @@ __device__ __forceinline__ void rnn_flow_role(const float* __restrict__ ih, cons
 constexpr int kFlowSmem = kLatQkvSmem;   // the largest role (floats)
 static_assert(kLatInSmem <= kFlowSmem && kLatLnSmem <= kFlowSmem && 8 * 3 * 256 <= kFlowSmem && 2 * 8 * 68 <= kFlowSmem, "role LDS");
 constexpr int kFlowMaxStages = 2 + 4 * 8;
+static_assert(kFlowMaxStages == 34, "tests/test_nonfinite_isolation_gpu.py restates the flag layout ([34 stages][64] u64 per window): change both");
 // The flags and launch counters of the one-launch form, [64 windows][34][64] u64 = 1.06 MiB, live at the very FRONT of the caller's
 // workspace (tip_abi.hip carve_workspace), at offsets that depend on nothing — not on B, not on T.  A counter must only ever be
 // advanced by its own window's launches: behind the activations (where round 6 first put them) the words moved with every (B, T), a
@@ -1171,7 +1172,15 @@ hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float*
         fa.xa = xa; fa.xb = xb; fa.o = o; fa.hid = hid; fa.ihb = ihb; fa.st0 = st0; fa.st1 = st1;
         fa.ubuf = xb + bt * 256;                                 // the [B][T][768] slot nobody else uses: [B][T][224] prologue rows
         fa.gran = gran; fa.xccw = xccw; fa.flags = flags;
-        fa.nonce = head->nonce;
+        // The stamp base is the handle's nonce PLUS a hash of where the flags live.  A host that moves its workspace through recycled
+        // memory (the module's per-stream buffer grows with T: a new address every frame while a stream warms up) puts the new flag
+        // area on top of an older one at a shifted offset; a fresh area counts from 0 like the old one did, so with the handle's nonce
+        // alone window w found window w + k's stamps of the same epoch — from another XCD ("foreign": NaN rows, the one-launch form
+        // switched off; a 5-stream engine at frame 21), or, k a multiple of 8, "done" before its producers ran.
+        u64 where = reinterpret_cast<uintptr_t>(flags);
+        where = (where ^ (where >> 30)) * 0xbf58476d1ce4e5b9ull;
+        where = (where ^ (where >> 27)) * 0x94d049bb133111ebull;
+        fa.nonce = head->nonce + (where ^ (where >> 31));
         fa.whh_frag = whh_frag; fa.hall = hall;
         fa.out_frag = head->wfrag; fa.out_bias = head->bias; fa.y = head->y; fa.ldy = head->ldy; fa.N = head->N; fa.last_only = head->last_only ? 1 : 0;
         fa.rows = head->rows;
