@@ -33,7 +33,8 @@ extern "C" {
                                 (tip_stream_attach, tip_stream_detach, tip_stream_ingest_staggered, tip_stream_consume_staggered,
                                 tip_stream_ingest_mapped, tip_stream_consume_mapped); the model shapes of the streaming entry points
                                 (tip_stream_reset_shaped) and the host override of the fed-back pose (tip_stream_history_override); the deployed forward at any
-                                batch and its device seeds (tip_forward_live, tip_seeds_next) */
+                                batch and its device seeds (tip_forward_live, tip_seeds_next); the streaming entry points at any window
+                                length (the tip_stream_*_w family) */
 
 /* The library is built with -fvisibility=hidden: the functions declared here (and the measurement hooks of
  * tip_hip_debug.h) are its whole dynamic symbol table (tests/test_host_cpu.py compares `nm -D` with the two headers). */
@@ -391,6 +392,47 @@ TIP_API int tip_stream_ingest_mapped(void* state, const float* raw_imu, int n_st
                              float* x_s, int* rows, tip_stream_t stream);
 TIP_API int tip_stream_consume_mapped(void* state, const float* y, const int* rows, const int* slot_at, int B, int n_streams,
                               float* s_rest, float* c_t, float* y_slot, int* rows_slot, tip_stream_t stream);
+
+/* ---- any window length: the reference's RTRunnerMin(char, model, max_input_l, ...) / RTRunner take the window length W as an
+ *      argument (real_time_runner_minimal.py:24,54,131,139; real_time_runner.py:29,413,421); the entry points above are W = 40.  The
+ *      _w family is the same calls with `window` = W in [1, 128] in front of `stream` (anything else: TIP_ERR_INVALID_ARG); the host
+ *      cannot read the device buffer, so every call is told.  What W changes, and nothing else:
+ *        - the call for frame f has T = tip_stream_window_len_w(f, W) = min(max(f - 4, 0), W) rows: x_imu [n,T,72|90], x_s [n,T,119|131];
+ *          the staggered and mapped windows sit in W-row slots ([n|B, W, *], rows T_i .. W-1 zero);
+ *        - the local-frame, acc-sum and history rings are W deep; the raw ring (11) and the output filter (6) are not.  A block is
+ *          11*72 + W*(72 + 18 + 131) + 6*131 + 54 + 3 floats rounded up to 64 (tip_stream_state_bytes_w; 10496 floats at W = 40);
+ *        - the acc-sum feature still spans ACC_SUM_WIN_LEN = 40 rows (:136-141): the newest min(T, 40) rows of the window;
+ *        - TIP_STREAM_FRAME_AUTO means full windows (T = W): valid once frame W + 3 has been ingested.
+ *      window = 40 IS the call above: same kernels, same layout, same bits (and no layout check).  Every other W runs kernels that take
+ *      W as a value, on a layout of its own: the three control words lead the block, and the shape word records W above the two
+ *      shape bits (0 there — what tip_stream_reset(_shaped) writes — means 40).  A buffer is used with ONE W from tip_stream_reset_w
+ *      to the next reset.  A _w call whose window (other than 40) is not the one the buffer's reset recorded never produces another
+ *      layout's numbers and touches no state: tip_stream_ingest_w writes NaN window rows, the staggered and mapped ingest a NaN window
+ *      and rows = -1; consume, attach, detach and override skip the block.  (The windows are filled at the buffer's shape; a buffer no
+ *      _w reset ever wrote has no known shape, and the NaNs go to windows of the narrowest one, 119 / 72 columns.  block 0's words
+ *      are read at the head of the buffer: it must hold at least one block, which every n_streams >= 1 gives.)
+ *      tip_stream_ingest_newest, tip_stream_frame_counter_offset and tip_forward_reuse's ring stay at 40 only. */
+TIP_API int tip_stream_state_bytes_w(int n_streams, int window, size_t* bytes);
+TIP_API int tip_stream_window_len_w(int frame_idx, int window); /* T, or TIP_ERR_INVALID_ARG (< 0) for a window outside [1, 128] */
+TIP_API int tip_stream_reset_w(void* state, const float* s_init /* [n,114] device */, int n_streams, int n_sbps, int with_acc_sum,
+                       int window, tip_stream_t stream);
+TIP_API int tip_stream_ingest_w(void* state, const float* raw_imu, int n_streams, int frame_idx, float* x_imu, float* x_s, int window,
+                        tip_stream_t stream);
+TIP_API int tip_stream_consume_w(void* state, const float* y_last, int n_streams, int call_idx, float* s_rest, float* c_t, int window,
+                         tip_stream_t stream);
+TIP_API int tip_stream_attach_w(void* state, int n_streams, const int* slots, const float* s_init /* [count,114] */, int count,
+                        int window, tip_stream_t stream);
+TIP_API int tip_stream_detach_w(void* state, int n_streams, const int* slots, int count, int window, tip_stream_t stream);
+TIP_API int tip_stream_ingest_staggered_w(void* state, const float* raw_imu, int n_streams, float* x_imu, float* x_s, int* rows,
+                                  int window, tip_stream_t stream);
+TIP_API int tip_stream_consume_staggered_w(void* state, const float* y_last, const int* rows, int n_streams, float* s_rest, float* c_t,
+                                   int window, tip_stream_t stream);
+TIP_API int tip_stream_ingest_mapped_w(void* state, const float* raw_imu, int n_streams, const int* slot_at, int B, float* x_imu,
+                               float* x_s, int* rows, int window, tip_stream_t stream);
+TIP_API int tip_stream_consume_mapped_w(void* state, const float* y, const int* rows, const int* slot_at, int B, int n_streams,
+                                float* s_rest, float* c_t, float* y_slot, int* rows_slot, int window, tip_stream_t stream);
+TIP_API int tip_stream_history_override_w(void* state, int n_streams, const int* slots /* [count] */, const float* q_aa /* [count,54] */,
+                                  int count, int window, tip_stream_t stream);
 
 /* ---- exact streaming reuse: tip_forward for lock-stepped streams whose windows slide by one frame per call.
  *      In the runner a frame's model inputs never change once recorded (real_time_runner_minimal.py:74,85,137: raw_imu_buffer,

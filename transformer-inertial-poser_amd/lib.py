@@ -41,6 +41,9 @@ EXPORTS = (
     "tip_forward_rows", "tip_stream_attach", "tip_stream_detach", "tip_stream_ingest_staggered", "tip_stream_consume_staggered",
     "tip_stream_ingest_mapped", "tip_stream_consume_mapped", "tip_stream_reset_shaped", "tip_stream_history_override",
     "tip_forward_live", "tip_seeds_next",
+    "tip_stream_state_bytes_w", "tip_stream_window_len_w", "tip_stream_reset_w", "tip_stream_ingest_w", "tip_stream_consume_w",
+    "tip_stream_attach_w", "tip_stream_detach_w", "tip_stream_ingest_staggered_w", "tip_stream_consume_staggered_w",
+    "tip_stream_ingest_mapped_w", "tip_stream_consume_mapped_w", "tip_stream_history_override_w",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
     "tip_train_bytes_f64", "tip_train_forward_f64", "tip_train_backward_f64",
     "tip_combine_frames", "tip_combine_scratch_bytes", "tip_combine_sequence", "tip_gather_windows",
@@ -164,6 +167,13 @@ def load() -> ctypes.CDLL:
     lib.tip_stream_consume_staggered.argtypes = [vp, vp, vp, i32, vp, vp, vp]
     lib.tip_stream_ingest_mapped.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp]
     lib.tip_stream_consume_mapped.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
+    # the _w family (any window length): the same arguments with `window` in front of the stream
+    lib.tip_stream_state_bytes_w.argtypes = [i32, i32, ctypes.POINTER(sz)]
+    lib.tip_stream_window_len_w.argtypes = [i32, i32]
+    for name in ("reset_shaped", "ingest", "consume", "attach", "detach", "ingest_staggered", "consume_staggered", "ingest_mapped",
+                 "consume_mapped", "history_override"):
+        at = getattr(lib, "tip_stream_" + name).argtypes
+        getattr(lib, "tip_stream_" + name.replace("_shaped", "") + "_w").argtypes = at[:-1] + [i32, vp]
     u64 = ctypes.c_ulonglong
     f32 = ctypes.c_float
     lib.tip_train_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz)]

@@ -43,6 +43,12 @@ StaggeredStreamingEngine(..., compact=True) makes that cost follow the load inst
 positions 0 .. k-1 (include/tip_hip.h: tip_stream_ingest_mapped) and the forward runs on the top of the step of AUTO's cost staircase
 that holds them (POOL_LADDER below).
 
+Window length (window=W, both engines; default 40, the paper's — what "40" stands for everywhere above): the reference's runners take
+it as max_input_l (real_time_runner_minimal.py:24; real_time_runner.py:29), and train_model.py --seq_len trains at any length.  W in
+1 .. 128: rings, buffers and the forward's T follow it (T = min(max(f - 4, 0), W); graph capture from frame W + 4 on); the acc-sum
+feature keeps its 40-frame span (the newest min(T, 40) rows).  40 runs the kernels with compile-time trip counts through the same
+entry points as ever; any other length the tip_stream_*_w family (include/tip_hip.h), which takes W as a value.  reuse needs 40.
+
 Model shapes (stream_shape below): the engines serve the four models the reference's runners accept — with or without the acc-sum
 feature (x_imu 90 / 72 columns) times five or two stationary body points (size_s 131 / 119, c_t 20 / 8 columns) — and take the
 shape from the model.  override_history(q, slots): RTRunner with multi_sbp_terrain_and_correction feeds back a pose its host-side
@@ -92,6 +98,16 @@ def pool_bucket(k: int, ladder) -> int:
 
 
 SHAPES = ((72, 119), (72, 131), (90, 119), (90, 131))     # (x_imu columns, size_s) the streaming kernels serve
+WINDOW_MAX = 128          # window lengths 1 .. 128 (include/tip_hip.h: the tip_stream_*_w family; the training step's T limit)
+LIVE_WINDOW_MAX = 40      # live_dropout=True: what tip_forward_live serves (csrc/tip_fused.hip: fused_supported, T <= fz::TMAX = 40)
+
+
+def check_window(window, who: str) -> int:
+    """`window` as an int in [1, WINDOW_MAX]; anything else is a ValueError in `who`'s name (no device needed)."""
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= int(window) <= WINDOW_MAX:
+        raise ValueError(f"tip_amd.{who}: window is the window length in frames, an int in [1, {WINDOW_MAX}] (the reference runners' "
+                         f"max_input_l); got {window!r}")
+    return int(window)
 
 
 def stream_shape(model):
@@ -177,8 +193,14 @@ class _StreamBase:
     its own in _allocate() (once, before the first reset()), says what a lost hand-off does to it (_reprime, _REPRIMED) and supplies
     the forward that warms a capture up (_warm_forward) and the frame that is captured (_captured_frame)."""
 
-    def __init__(self, model, s_init: torch.Tensor, use_graph: bool, live_dropout: bool = False):
+    def __init__(self, model, s_init: torch.Tensor, use_graph: bool, live_dropout: bool = False, window: int = 40):
         self.model = model
+        # window: the reference runners' max_input_l — rings, buffers and the forward's T.  40 runs the 40-row entry points (today's
+        # kernels, bit for bit); any other length the tip_stream_*_w family (_call)
+        self.window = check_window(window, type(self).__name__)
+        if live_dropout and self.window > LIVE_WINDOW_MAX:
+            raise ValueError(f"tip_amd.{type(self).__name__}(live_dropout=True): the live forward (tip_forward_live) serves windows of at "
+                             f"most {LIVE_WINDOW_MAX} frames; got window={self.window}")
         # live_dropout: every frame's forward is model.forward_live (the model as the reference deploys it: past-state keep mask drawn
         # in the first kernel, encoder dropout live in .train() mode, no stash) under the engine's own device seeds
         self.live_dropout = bool(live_dropout)
@@ -200,11 +222,11 @@ class _StreamBase:
                           "the HIP TRAINING kernels (all rows, activation stash); call model.eval() for the inference plans")
         self.n = int(s_init.shape[0])
         nbytes = ctypes.c_size_t()
-        self._check(self.lib.tip_stream_state_bytes(self.n, ctypes.byref(nbytes)))
+        self._check(self.lib.tip_stream_state_bytes_w(self.n, self.window, ctypes.byref(nbytes)))
         self.state = torch.empty(max(nbytes.value, 4), dtype=torch.uint8, device=self.device)
         self.s_init = s_init.to(self.device).contiguous()
-        self.x_imu = torch.empty((self.n, 40, self.nx), dtype=torch.float32, device=self.device)
-        self.x_s = torch.empty((self.n, 40, self.ns), dtype=torch.float32, device=self.device)
+        self.x_imu = torch.empty((self.n, self.window, self.nx), dtype=torch.float32, device=self.device)
+        self.x_s = torch.empty((self.n, self.window, self.ns), dtype=torch.float32, device=self.device)
         self.s_rest = torch.empty((self.n, 111), dtype=torch.float32, device=self.device)
         self.c_t = torch.empty((self.n, self.nc), dtype=torch.float32, device=self.device)
         self.raw = torch.empty((self.n, 72), dtype=torch.float32, device=self.device)    # static input of the captured graph
@@ -225,6 +247,14 @@ class _StreamBase:
     def _stream(self):
         return torch.cuda.current_stream(self.device).cuda_stream
 
+    def _call(self, name: str, *args):
+        """tip_stream_<name>(*args, stream) on the current stream at window 40 — the 40-row entry points, as ever — and
+        tip_stream_<name>_w(*args, window, stream) at any other length."""
+        if self.window == 40:
+            self._check(getattr(self.lib, "tip_stream_" + name)(*args, self._stream()))
+        else:
+            self._check(getattr(self.lib, "tip_stream_" + name.replace("_shaped", "") + "_w")(*args, self.window, self._stream()))
+
     def _to_dev(self, t):
         """Host -> device without a synchronising copy from pageable memory (an attach between two frames must not drain the queue)."""
         return t.to(self.device, non_blocking=True) if t.is_cuda else t.pin_memory().to(self.device, non_blocking=True)
@@ -232,8 +262,7 @@ class _StreamBase:
     def _reset_state(self, s_init):
         """tip_stream_reset_shaped: every block rebuilt from its s_init row, the buffer's shape recorded for the kernels."""
         with torch.cuda.device(self.device):
-            self._check(self.lib.tip_stream_reset_shaped(self.state.data_ptr(), s_init.data_ptr(), self.n, self.n_sbps,
-                                                         1 if self.with_acc_sum else 0, self._stream()))
+            self._call("reset_shaped", self.state.data_ptr(), s_init.data_ptr(), self.n, self.n_sbps, 1 if self.with_acc_sum else 0)
             if self.live_dropout:
                 self.seeds.copy_(torch.tensor(self.model._draw_seeds(), dtype=torch.int64))
 
@@ -280,8 +309,7 @@ class _StreamBase:
         with torch.cuda.device(self.device):
             q = self._to_dev(q.contiguous()).contiguous()
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
-            self._check(self.lib.tip_stream_history_override(self.state.data_ptr(), self.n, sl.data_ptr(), q.data_ptr(), len(idx),
-                                                             self._stream()))
+            self._call("history_override", self.state.data_ptr(), self.n, sl.data_ptr(), q.data_ptr(), len(idx))
 
     # ---- the hand-off contract ------------------------------------------------------------------------------------------------------
     def _demotions(self):
@@ -315,7 +343,7 @@ class _StreamBase:
         if self._graph_ws is None:
             # what the captured kernels will point at: allocated OUTSIDE the capture, held by the engine, one for every key and sized for
             # n (the one-launch form keeps its counters at offset 0 for any batch: include/tip_hip.h, tip_workspace_bytes; replays are serial)
-            self._graph_ws = torch.empty(self.model.workspace_bytes(self.n, 40), dtype=torch.uint8, device=self.device)
+            self._graph_ws = torch.empty(self.model.workspace_bytes(self.n, self.window), dtype=torch.uint8, device=self.device)
             self._graph_y = torch.empty((self.n, self.model.size_s), dtype=torch.float32, device=self.device)
         # packs / attaches outside the capture.  The device RNG is put back afterwards: with past_state_dropout or in_dropout live
         # this warm-up would otherwise draw once more than the launch-by-launch loop does
@@ -343,16 +371,27 @@ class _StreamBase:
 class StreamingEngine(_StreamBase):
     _REPRIMED = "the engine was reset (re-prime it)"
 
-    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False, live_dropout: bool = False):
-        """live_dropout=True: serve the model as the reference deploys it — .train() or .eval() (then only the past-state keep mask is
+    def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False, live_dropout: bool = False,
+                 window: int = 40):
+        """window: the window length W in frames, 1 .. 128 — RTRunnerMin's max_input_l (real_time_runner_minimal.py:24,54,131,139):
+        the call for frame f has T = min(max(f - 4, 0), W) rows, the rings are W deep, forward_last runs at T = W once the window is
+        full and use_graph=True captures from frame W + 4 on; the acc-sum feature still spans the newest min(T, 40) rows.  40 is
+        the paper's, on kernels with compile-time trip counts; any other length takes W as a value.  reuse=True needs window=40 (the
+        reuse ring is 40 slots: ValueError otherwise; "auto" is then off), live_dropout=True a window the live forward serves
+        (at most 40: ValueError otherwise, at construction).
+        live_dropout=True: serve the model as the reference deploys it — .train() or .eval() (then only the past-state keep mask is
         live), every frame ingest -> tip_seeds_next -> model.forward_live(seeds_dev=engine.seeds) -> consume, launch by launch and
         captured alike: use_graph=True replays from the usual frame on with a .train() model too and reproduces launch mode bit for
         bit.  reuse=True is refused and "auto" is off (rows differ from window to window)."""
         if live_dropout and reuse is True:
             raise RuntimeError("tip_amd.StreamingEngine(live_dropout=True): reuse=True is not supported — with dropout live a frame's rows "
                                "differ from window to window")
-        self.reuse = False if live_dropout else reuse          # True / False / "auto" (resolved in _allocate, once the stream count is known)
-        super().__init__(model, s_init, use_graph, live_dropout)
+        window = check_window(window, "StreamingEngine")
+        if reuse is True and window != 40:
+            raise ValueError(f"tip_amd.StreamingEngine(reuse=True): the reuse ring holds 40-frame windows; got window={window}")
+        # True / False / "auto" (resolved in _allocate, once the stream count is known)
+        self.reuse = False if (live_dropout or window != 40) else reuse
+        super().__init__(model, s_init, use_graph, live_dropout, window)
 
     def _allocate(self):
         model = self.model
@@ -392,15 +431,16 @@ class StreamingEngine(_StreamBase):
 
     def _frame(self, raw, f, f_consume, T, ws, out):
         """ingest -> forward_last -> consume on windows of T rows; None while the smoother primes (T = 0).  Launch by launch: frame
-        indices f and f - 5, the module's own buffers (ws = out = None).  Captured: TIP_STREAM_FRAME_AUTO twice, T = 40, the engine's."""
-        st = self._stream()
-        # (full windows: the reuse forward reads only the newest row of x_imu / x_s — the 35-KB window gather per stream is skipped)
-        ingest = self.lib.tip_stream_ingest_newest if (self.reuse and T == 40) else self.lib.tip_stream_ingest
-        self._check(ingest(self.state.data_ptr(), raw.data_ptr(), self.n, f, self.x_imu.data_ptr(), self.x_s.data_ptr(), st))
+        indices f and f - 5, the module's own buffers (ws = out = None).  Captured: TIP_STREAM_FRAME_AUTO twice, T = window, the
+        engine's."""
+        # (full windows: the reuse forward reads only the newest row of x_imu / x_s — the 35-KB window gather per stream is skipped;
+        # reuse implies window 40)
+        self._call("ingest_newest" if (self.reuse and T == 40) else "ingest", self.state.data_ptr(), raw.data_ptr(), self.n, f,
+                   self.x_imu.data_ptr(), self.x_s.data_ptr())
         if T == 0:
             return None
         x_imu, x_s = self.x_imu, self.x_s
-        if T < 40:      # windows are written densely as [n, T, *] at the head of the preallocated buffers
+        if T < self.window:      # windows are written densely as [n, T, *] at the head of the preallocated buffers
             x_imu = x_imu.view(-1)[: self.n * T * self.nx].view(self.n, T, self.nx)
             x_s = x_s.view(-1)[: self.n * T * self.ns].view(self.n, T, self.ns)
         mark = self._demotions()
@@ -416,8 +456,7 @@ class StreamingEngine(_StreamBase):
             y_last = self.model.forward_last(x_imu, x_s, workspace=ws, out=out)
         if self._demotions() != mark:
             self._lost_handoff()
-        self._check(self.lib.tip_stream_consume(self.state.data_ptr(), y_last.data_ptr(), self.n, f_consume,
-                                                self.s_rest.data_ptr(), self.c_t.data_ptr(), st))
+        self._call("consume", self.state.data_ptr(), y_last.data_ptr(), self.n, f_consume, self.s_rest.data_ptr(), self.c_t.data_ptr())
         return y_last
 
     def _warm_forward(self, key):
@@ -427,20 +466,20 @@ class StreamingEngine(_StreamBase):
         self.model.forward_last(self.x_imu, self.x_s, workspace=self._graph_ws, out=self._graph_y)   # (never touches the ring)
 
     def _captured_frame(self, key):
-        return self._frame(self.raw, _lib.TIP_STREAM_FRAME_AUTO, _lib.TIP_STREAM_FRAME_AUTO, 40, self._graph_ws, self._graph_y)
+        return self._frame(self.raw, _lib.TIP_STREAM_FRAME_AUTO, _lib.TIP_STREAM_FRAME_AUTO, self.window, self._graph_ws, self._graph_y)
 
     @torch.no_grad()
     def step(self, raw_imu: torch.Tensor) -> Optional[dict]:
         f = self.frame
-        if self.use_graph and f >= 44 and (self.live_dropout or not self.model.training):
-            # steady state (T = 40): one copy + one graph launch per frame
+        if self.use_graph and f >= self.window + 4 and (self.live_dropout or not self.model.training):
+            # steady state (T = window): one copy + one graph launch per frame
             self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
             with torch.cuda.device(self.device):
                 self._replay(None)
             self.frame = f + 1
-            return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": self._y_last, "T": 40}
+            return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": self._y_last, "T": self.window}
         raw = torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72).to(self.device, non_blocking=True).contiguous()
-        T = int(self.lib.tip_stream_window_len(f))
+        T = int(self.lib.tip_stream_window_len_w(f, self.window))
         self.frame = f + 1          # (the frame is ingested whatever its forward does; a lost hand-off resets the counter)
         with torch.cuda.device(self.device):
             y_last = self._frame(raw, f, f - 5, T, None, None)
@@ -482,16 +521,22 @@ class StaggeredStreamingEngine(_StreamBase):
     _REPRIMED = "every attached slot was re-attached"
 
     def __init__(self, model, s_init: torch.Tensor, use_graph: bool = False, reuse: bool = False, compact: bool = False,
-                 live_dropout: bool = False):
-        """live_dropout=True (StreamingEngine's): a .train() model is accepted, and every frame's forward is tip_seeds_next ->
+                 live_dropout: bool = False, window: int = 40):
+        """window (StreamingEngine's): windows sit in `window`-row slots and every slot costs a T = window forward, plain and compact.
+        The compact pool's ladder (POOL_LADDER) was calibrated at T = 40 and is kept for every window: it is unmeasured elsewhere, and
+        it decides cost only, never results.
+        live_dropout=True (StreamingEngine's): a .train() model is accepted, and every frame's forward is tip_seeds_next ->
         model.forward_live(rows=..., seeds_dev=engine.seeds) in place of forward_rows, plain and compact, launch by launch and captured."""
+        window = check_window(window, "StaggeredStreamingEngine")
+        if reuse is True and window != 40:
+            raise ValueError(f"tip_amd.StaggeredStreamingEngine(reuse=True): the reuse ring holds 40-frame windows; got window={window}")
         if reuse:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine: reuse= is not supported (the reuse ring assumes lock-step frames)")
         if model.training and not live_dropout:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine needs model.eval() (the inference kernels: forward_rows)")
         self.reuse, self._ring = False, None          # (lock-step only)
         self.compact = bool(compact)
-        super().__init__(model, s_init, use_graph, live_dropout)
+        super().__init__(model, s_init, use_graph, live_dropout, window)
         self.s_rest.zero_()          # (rows of slots that have not produced a row yet: defined, and unchanged until they do)
         self.c_t.zero_()
 
@@ -518,8 +563,7 @@ class StaggeredStreamingEngine(_StreamBase):
         with torch.cuda.device(self.device):
             slots = self._to_dev(torch.tensor(idx, dtype=torch.int32))
             rows = self.s_cur.index_select(0, slots.long()).contiguous()
-            self._check(self.lib.tip_stream_attach(self.state.data_ptr(), self.n, slots.data_ptr(), rows.data_ptr(), len(idx),
-                                                   self._stream()))
+            self._call("attach", self.state.data_ptr(), self.n, slots.data_ptr(), rows.data_ptr(), len(idx))
 
     def reset(self):
         """Re-prime: every attached slot restarts at its frame 0 from the s_init it was last attached with; detached slots stay
@@ -578,7 +622,7 @@ class StaggeredStreamingEngine(_StreamBase):
             return
         with torch.cuda.device(self.device):
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
-            self._check(self.lib.tip_stream_detach(self.state.data_ptr(), self.n, sl.data_ptr(), len(idx), self._stream()))
+            self._call("detach", self.state.data_ptr(), self.n, sl.data_ptr(), len(idx))
 
     def _override_ready(self, idx):
         for i in idx:
@@ -609,30 +653,27 @@ class StaggeredStreamingEngine(_StreamBase):
     def _frame_staggered(self, ws, out):
         """ingest_staggered -> forward_rows -> consume_staggered: no frame index anywhere (capturable from the first frame on).
         Launch by launch on the module's own workspace and output (ws = out = None), captured on the engine's."""
-        st = self._stream()
-        self._check(self.lib.tip_stream_ingest_staggered(self.state.data_ptr(), self.raw.data_ptr(), self.n, self.x_imu.data_ptr(),
-                                                         self.x_s.data_ptr(), self.rows.data_ptr(), st))
+        self._call("ingest_staggered", self.state.data_ptr(), self.raw.data_ptr(), self.n, self.x_imu.data_ptr(), self.x_s.data_ptr(),
+                   self.rows.data_ptr())
         mark = self._demotions()
         y_last = self._rows_forward(self.x_imu, self.x_s, self.rows, ws, out)
         if self._demotions() != mark:
             self._lost_handoff()
-        self._check(self.lib.tip_stream_consume_staggered(self.state.data_ptr(), y_last.data_ptr(), self.rows.data_ptr(), self.n,
-                                                          self.s_rest.data_ptr(), self.c_t.data_ptr(), st))
+        self._call("consume_staggered", self.state.data_ptr(), y_last.data_ptr(), self.rows.data_ptr(), self.n, self.s_rest.data_ptr(),
+                   self.c_t.data_ptr())
         return y_last
 
     # ---- compact pools ----------------------------------------------------------------------------------------------------------
     def _frame_mapped(self, B, ws, out):
         """ingest_mapped -> forward_rows on B windows -> consume_mapped (what a bucket's graph holds); ws / out as _frame_staggered's."""
-        st = self._stream()
-        self._check(self.lib.tip_stream_ingest_mapped(self.state.data_ptr(), self.raw.data_ptr(), self.n, self.slot_at.data_ptr(), B,
-                                                      self.x_imu.data_ptr(), self.x_s.data_ptr(), self.rows.data_ptr(), st))
+        self._call("ingest_mapped", self.state.data_ptr(), self.raw.data_ptr(), self.n, self.slot_at.data_ptr(), B, self.x_imu.data_ptr(),
+                   self.x_s.data_ptr(), self.rows.data_ptr())
         mark = self._demotions()
         y = self._rows_forward(self.x_imu[:B], self.x_s[:B], self.rows[:B], ws, out)
         if self._demotions() != mark:
             self._lost_handoff()
-        self._check(self.lib.tip_stream_consume_mapped(self.state.data_ptr(), y.data_ptr(), self.rows.data_ptr(), self.slot_at.data_ptr(),
-                                                       B, self.n, self.s_rest.data_ptr(), self.c_t.data_ptr(), self.y_slot.data_ptr(),
-                                                       self.rows_slot.data_ptr(), st))
+        self._call("consume_mapped", self.state.data_ptr(), y.data_ptr(), self.rows.data_ptr(), self.slot_at.data_ptr(), B, self.n,
+                   self.s_rest.data_ptr(), self.c_t.data_ptr(), self.y_slot.data_ptr(), self.rows_slot.data_ptr())
         return y
 
     def _flush(self):
@@ -646,8 +687,7 @@ class StaggeredStreamingEngine(_StreamBase):
         self._stage[: h.size].copy_(torch.from_numpy(h).pin_memory(), non_blocking=True)
         base = self._stage.data_ptr()
         if att:
-            self._check(self.lib.tip_stream_attach(self.state.data_ptr(), self.n, base + 4 * o_att, base + 4 * o_rows, len(att),
-                                                   self._stream()))
+            self._call("attach", self.state.data_ptr(), self.n, base + 4 * o_att, base + 4 * o_rows, len(att))
         if det:
             sl = self._stage[o_det: o_rows].view(torch.int64)
             self.y_slot.index_fill_(0, sl, float("nan"))
