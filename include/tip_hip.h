@@ -34,7 +34,7 @@ extern "C" {
                                 tip_stream_ingest_mapped, tip_stream_consume_mapped); the model shapes of the streaming entry points
                                 (tip_stream_reset_shaped) and the host override of the fed-back pose (tip_stream_history_override); the deployed forward at any
                                 batch and its device seeds (tip_forward_live, tip_seeds_next); the streaming entry points at any window
-                                length (the tip_stream_*_w family) */
+                                length (the tip_stream_*_w family); device-fed replay of recordings (tip_replay_feed, tip_replay_collect) */
 
 /* The library is built with -fvisibility=hidden: the functions declared here (and the measurement hooks of
  * tip_hip_debug.h) are its whole dynamic symbol table (tests/test_host_cpu.py compares `nm -D` with the two headers). */
@@ -433,6 +433,33 @@ TIP_API int tip_stream_consume_mapped_w(void* state, const float* y, const int* 
                                 float* s_rest, float* c_t, float* y_slot, int* rows_slot, int window, tip_stream_t stream);
 TIP_API int tip_stream_history_override_w(void* state, int n_streams, const int* slots /* [count] */, const float* q_aa /* [count,54] */,
                                   int count, int window, tip_stream_t stream);
+
+/* ---- device-fed replay: recorded IMU files through a compact pool with no per-frame host traffic (tip_amd.replay.ReplayPool; the
+ *      reference replays a file by stepping its runner once per frame: offline_testing_simple.py:109-155).  The corpus — the frames of
+ *      every recording back to back, corpus[n_rows,72] fp32 — and the corpus-shaped outputs s_out[n_rows,111], c_out[n_rows,8|20],
+ *      y_out[n_rows,119|131] (nullable), valid[n_rows] (bytes) are DEVICE arrays that live for the whole run.  cur / end are DEVICE
+ *      long long [n_slots] tables: cur[s] is the corpus row slot s is fed next (< 0: the slot is idle), end[s] the row after the last
+ *      one it is fed.  A frame is, on one stream,
+ *          tip_replay_feed(corpus, n_rows, cur, n, raw[n,72], stream);
+ *              raw[s] = corpus[cur[s]]; an idle slot, or a cursor outside [0, n_rows): zeros (finite padding, as tip_forward_rows' empty windows)
+ *          tip_stream_ingest_mapped(state, raw, ...) -> tip_forward_rows / tip_forward_live -> tip_stream_consume_mapped(..., y_slot, rows_slot, ...);
+ *          tip_replay_collect(cur, end, n, n_rows, s_rest[n,111], c_t[n,8|20], y_slot[n,119|131], rows_slot[n], size_s, s_out, c_out, y_out, valid, stream);
+ *              slot s with c = cur[s] >= 0 writes output row c + 1 — the step on frame t of a recording fills its row t + 1, as the
+ *              reference's loop does (offline_testing_simple.py:123-134).  rows_slot[s] >= 0 (the slot produced a row this frame):
+ *              s_out / c_out / y_out row c + 1 = s_rest[s] / c_t[s] / y_slot[s], valid = 1.  rows_slot[s] < 0 (the slot's smoother primes:
+ *              its first five frames): s_out row c + 1 = s_out row c, c_out row = 0, y_out row = NaN, valid = 0 — the HOST writes
+ *              row 0 of every recording (its start state) before the run, so every priming row is the start state, which is what the
+ *              runner returns while it primes (real_time_runner_minimal.py:125-128).  Then cur[s] = c + 1, or -1 once c + 1 = end[s].
+ *              A cursor with c + 1 >= n_rows writes nothing and goes idle; idle slots are not touched.
+ *      Neither call takes a frame index or any argument that changes from frame to frame: the three steps are captured once (HIP
+ *      graph) and replayed; the host rewrites cur / end entries between two replays when a slot takes its next recording.  One wave
+ *      per slot, one writer per slot and per output row (the host keeps the recordings of different slots disjoint).  corpus, raw,
+ *      c_t and c_out must be 16-byte aligned, cur / end 8-byte; size_s is 119 or 131; y_slot may be null only with y_out;
+ *      anything else: TIP_ERR_INVALID_ARG. */
+TIP_API int tip_replay_feed(const float* corpus, long long n_rows, const long long* cur, int n_slots, float* raw, tip_stream_t stream);
+TIP_API int tip_replay_collect(long long* cur, const long long* end, int n_slots, long long n_rows, const float* s_rest, const float* c_t,
+                       const float* y_slot, const int* rows_slot, int size_s, float* s_out, float* c_out, float* y_out,
+                       unsigned char* valid, tip_stream_t stream);
 
 /* ---- exact streaming reuse: tip_forward for lock-stepped streams whose windows slide by one frame per call.
  *      In the runner a frame's model inputs never change once recorded (real_time_runner_minimal.py:74,85,137: raw_imu_buffer,

@@ -44,6 +44,7 @@ EXPORTS = (
     "tip_stream_state_bytes_w", "tip_stream_window_len_w", "tip_stream_reset_w", "tip_stream_ingest_w", "tip_stream_consume_w",
     "tip_stream_attach_w", "tip_stream_detach_w", "tip_stream_ingest_staggered_w", "tip_stream_consume_staggered_w",
     "tip_stream_ingest_mapped_w", "tip_stream_consume_mapped_w", "tip_stream_history_override_w",
+    "tip_replay_feed", "tip_replay_collect",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
     "tip_train_bytes_f64", "tip_train_forward_f64", "tip_train_backward_f64",
     "tip_combine_frames", "tip_combine_scratch_bytes", "tip_combine_sequence", "tip_gather_windows",
@@ -174,6 +175,8 @@ def load() -> ctypes.CDLL:
                  "consume_mapped", "history_override"):
         at = getattr(lib, "tip_stream_" + name).argtypes
         getattr(lib, "tip_stream_" + name.replace("_shaped", "") + "_w").argtypes = at[:-1] + [i32, vp]
+    lib.tip_replay_feed.argtypes = [vp, ctypes.c_longlong, vp, i32, vp, vp]
+    lib.tip_replay_collect.argtypes = [vp, vp, i32, ctypes.c_longlong, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     u64 = ctypes.c_ulonglong
     f32 = ctypes.c_float
     lib.tip_train_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz)]

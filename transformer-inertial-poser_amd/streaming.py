@@ -556,6 +556,7 @@ class StaggeredStreamingEngine(_StreamBase):
             self._pending_attach, self._pending_detach = {}, {}
             self.y_slot = torch.full((self.n, self.model.size_s), float("nan"), dtype=torch.float32, device=self.device)
             self.rows_slot = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
+            self._fed, self.fed_frames = None, 0          # device-fed frames (_step_fed): the feeder's two launches, frames launched
 
     def _attach_dev(self, idx):
         if not idx:
@@ -696,12 +697,56 @@ class StaggeredStreamingEngine(_StreamBase):
         self._pending_attach, self._pending_detach = {}, {}
 
     def _warm_forward(self, B):
+        if isinstance(B, tuple):                # (a device-fed frame, ("fed", B): the same forward)
+            B = B[1]
         B = self.n if B is None else B          # (the plain engine: all n windows)
         self._rows_forward(self.x_imu[:B], self.x_s[:B], self.rows[:B], self._graph_ws, self._graph_y[:B], advance=False)
 
     def _captured_frame(self, B):
         ws, y = self._graph_ws, self._graph_y
+        if isinstance(B, tuple):
+            return self._frame_fed(B[1], ws, y[:B[1]])
         return self._frame_staggered(ws, y) if B is None else self._frame_mapped(B, ws, y[:B])
+
+    # ---- device-fed frames (tip_amd.replay) -----------------------------------------------------------------------------------------
+    def _frame_fed(self, B, ws, out):
+        """feed -> _frame_mapped -> collect: `raw` is filled on the device by the feeder's first launch and the slots' rows are taken
+        away by its second (self._fed: two callables that launch on the current stream with no argument that changes from frame to
+        frame).  What a device-fed bucket's graph holds, under the key ("fed", B)."""
+        feed, collect = self._fed
+        feed()
+        y = self._frame_mapped(B, ws, out)
+        collect()
+        return y
+
+    @torch.no_grad()
+    def _step_fed(self):
+        """_step_compact for a frame whose `raw` the device fills itself (set_feeder): the same flush, the same capture and replay — one
+        captured frame per bucket, feed and collect inside it — and the same hand-off poll, but no host frame, no copy into `raw` and no
+        per-frame result (the feeder's collect launch owns the outputs; nothing is launched for T / valid).  Returns (k, B);
+        fed_frames counts the frames that launched."""
+        if self.model.training and not self.live_dropout:
+            raise RuntimeError("tip_amd.StaggeredStreamingEngine needs model.eval() (the inference kernels: forward_rows)")
+        k = len(self._positions)
+        B = self.bucket(k)
+        with torch.cuda.device(self.device):
+            self._flush()
+            if k:
+                if self.use_graph:
+                    self._replay(("fed", B))
+                else:
+                    self._frame_fed(B, None, None)
+                self.fed_frames += 1
+        self.frame += 1
+        return k, B
+
+    def set_feeder(self, feed, collect):
+        """Install the two launches _step_fed puts around the engine's frame; captured device-fed frames are dropped (they hold the
+        previous feeder's pointers).  compact=True only."""
+        if not self.compact:
+            raise RuntimeError("tip_amd.StaggeredStreamingEngine.set_feeder: compact=True only")
+        self._fed = (feed, collect)
+        self._graphs = {key: e for key, e in self._graphs.items() if not isinstance(key, tuple)}
 
     @torch.no_grad()
     def prewarm(self, buckets=None):

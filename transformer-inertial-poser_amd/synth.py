@@ -201,6 +201,15 @@ def make_keep_mask(cfg: dict, B: int, T: int, p: float, seed: int = 7) -> np.nda
     return (uniform01(seed, "mask", B * T * S) >= p).astype(np.float32).reshape(B, T, S)
 
 
+def make_recording(L: int, seed: int = 0):
+    """A recorded IMU file in the runner's frame format, for replay tests and benchmarks: (imu [L, 72] float32 — six fixed sensor
+    rotations, row-major, then 18 gaussian accelerations per frame — and a start state s_init [114] float32)."""
+    imu = np.empty((L, 72), dtype=np.float32)
+    imu[:, :54] = _random_rotations(seed, "rec/rot", 6).reshape(54)
+    imu[:, 54:] = (normal(seed, "rec/acc", L * 18) * 0.5).reshape(L, 18)
+    return imu, (normal(seed, "rec/s_init", 114) * 0.2).astype(np.float32)
+
+
 def flops_per_window(cfg: dict, T: int) -> float:
     """Algorithmic FLOPs of one window forward."""
     In = cfg["input_size_imu"] + cfg["size_s"] + (18 if cfg.get("with_acc_sum") else 0)
