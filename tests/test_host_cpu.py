@@ -202,6 +202,69 @@ def test_new_entry_points_check_their_arguments_without_a_gpu():
     assert [lib.tip_stream_window_len(f) for f in (0, 4, 5, 43, 44, 45, 1000)] == [0, 0, 1, 39, 40, 40, 40]
 
 
+def test_stream_entry_points_and_their_w_twins_refuse_the_same_calls():
+    """Every streaming operation has a 40-row entry point and a _w twin; both go through one argument check.  A refused call returns
+    the same negative status from both (at window = 40), the _w call at a window outside [1, 128] is TIP_ERR_INVALID_ARG, and a call
+    over no streams / slots / positions is TIP_OK.  Nothing here launches: every call is refused or empty (the pointers are fakes)."""
+    import ctypes
+    lib = tlib.load()
+    P, INVALID = ctypes.c_void_p(8), -1
+    # name -> (an empty call, refused calls); arguments without (window,) stream
+    ops = {
+        "reset_shaped": ((P, P, 0, 5, 1), [(None, P, 0, 5, 1), (P, None, 0, 5, 1), (P, P, -1, 5, 1), (P, P, 0, 3, 1), (P, P, 1, 3, 1)]),
+        "history_override": ((P, 4, P, P, 0), [(None, 4, P, P, 0), (P, -1, P, P, 0), (P, 4, P, P, -1), (P, 4, None, P, 1),
+                                               (P, 4, P, None, 1)]),
+        "ingest": ((P, P, 0, 7, P, P), [(None, P, 0, 7, P, P), (P, None, 0, 7, P, P), (P, P, -1, 7, P, P), (P, P, 0, -2, P, P),
+                                        (P, P, 1, -2, P, P), (P, P, 0, 7, None, P), (P, P, 0, -1, P, None)]),
+        "consume": ((P, P, 0, 7, P, P), [(None, P, 0, 7, P, P), (P, None, 0, 7, P, P), (P, P, -1, 7, P, P), (P, P, 0, -2, P, P),
+                                         (P, P, 1, -2, P, P), (P, P, 0, 7, None, P), (P, P, 0, 7, P, None)]),
+        "attach": ((P, 4, P, P, 0), [(None, 4, P, P, 0), (P, -1, P, P, 0), (P, 4, P, P, -1), (P, 4, None, P, 1), (P, 4, P, None, 1)]),
+        "detach": ((P, 4, P, 0), [(None, 4, P, 0), (P, -1, P, 0), (P, 4, P, -1), (P, 4, None, 1)]),
+        "ingest_staggered": ((P, P, 0, P, P, P), [(None, P, 0, P, P, P), (P, None, 0, P, P, P), (P, P, -1, P, P, P),
+                                                  (P, P, 0, None, P, P), (P, P, 0, P, None, P), (P, P, 0, P, P, None)]),
+        "consume_staggered": ((P, P, P, 0, P, P), [(None, P, P, 0, P, P), (P, None, P, 0, P, P), (P, P, None, 0, P, P),
+                                                   (P, P, P, -1, P, P), (P, P, P, 0, None, P), (P, P, P, 0, P, None)]),
+        "ingest_mapped": ((P, P, 4, P, 0, P, P, P), [(None, P, 4, P, 0, P, P, P), (P, None, 4, P, 0, P, P, P), (P, P, -1, P, 0, P, P, P),
+                                                     (P, P, 4, None, 0, P, P, P), (P, P, 4, P, -1, P, P, P), (P, P, 4, P, 5, P, P, P),
+                                                     (P, P, 0, P, 1, P, P, P), (P, P, 4, P, 0, None, P, P), (P, P, 4, P, 0, P, None, P),
+                                                     (P, P, 4, P, 0, P, P, None)]),
+        "consume_mapped": ((P, P, P, P, 0, 4, P, P, None, None),
+                           [(None, P, P, P, 0, 4, P, P, None, None), (P, None, P, P, 0, 4, P, P, None, None),
+                            (P, P, None, P, 0, 4, P, P, None, None), (P, P, P, None, 0, 4, P, P, None, None),
+                            (P, P, P, P, -1, 4, P, P, None, None), (P, P, P, P, 5, 4, P, P, None, None),
+                            (P, P, P, P, 1, 0, P, P, None, None), (P, P, P, P, 0, -1, P, P, None, None),
+                            (P, P, P, P, 0, 4, None, P, None, None), (P, P, P, P, 0, 4, P, None, None, None)]),
+    }
+    for name, (empty, refused) in ops.items():
+        f40, fw = getattr(lib, "tip_stream_" + name), getattr(lib, "tip_stream_" + name.replace("_shaped", "") + "_w")
+        assert f40(*empty, None) == 0 and fw(*empty, 40, None) == 0 and fw(*empty, 7, None) == 0, name
+        for args in [empty] + refused:
+            assert fw(*args, 0, None) == INVALID and fw(*args, 129, None) == INVALID, (name, args)
+        for args in refused:
+            s40 = f40(*args, None)
+            assert s40 == INVALID and fw(*args, 40, None) == s40 and fw(*args, 7, None) == s40, (name, args)
+    # zero-size calls of the operations that count twice: no slots listed among n streams, or listed slots of no streams
+    for name, args in (("history_override", (P, 0, P, P, 3)), ("attach", (P, 0, P, P, 3)), ("detach", (P, 0, P, 3))):
+        for W in (40, 7):
+            assert getattr(lib, f"tip_stream_{name}_w")(*args, W, None) == 0, (name, W)
+        assert getattr(lib, "tip_stream_" + name)(*args, None) == 0, name
+    # reset (tip_stream_reset: the paper's shape) is the shaped call too
+    assert lib.tip_stream_reset(P, P, 0, None) == 0 and lib.tip_stream_reset(None, P, 0, None) == INVALID
+    assert lib.tip_stream_reset(P, P, -1, None) == INVALID
+    assert lib.tip_stream_ingest_newest(P, P, 0, 7, P, P, None) == 0 and lib.tip_stream_ingest_newest(P, P, 0, -2, P, P, None) == INVALID
+    for f in range(51):
+        assert lib.tip_stream_window_len_w(f, 40) == lib.tip_stream_window_len(f) == min(max(f - 4, 0), 40), f
+    sz = ctypes.c_size_t
+    for n in (0, 1, 3, 256, 4096):
+        b40, bw = sz(), sz()
+        assert lib.tip_stream_state_bytes(n, ctypes.byref(b40)) == 0 and lib.tip_stream_state_bytes_w(n, 40, ctypes.byref(bw)) == 0
+        assert b40.value == bw.value == n * 10496 * 4, n
+    for args in ((-1, ctypes.byref(sz())), (1, None)):
+        assert lib.tip_stream_state_bytes(*args) == INVALID and lib.tip_stream_state_bytes_w(args[0], 40, args[1]) == INVALID
+    for W in (0, 129):
+        assert lib.tip_stream_state_bytes_w(1, W, ctypes.byref(sz())) == INVALID and lib.tip_stream_window_len_w(10, W) == INVALID
+
+
 def _unpack_linear(img, off_w, off_b, N, K, Npad, Kpad):
     W = img[off_w: off_w + Npad * Kpad].reshape(Npad, Kpad)
     return W[:N, :K], img[off_b: off_b + N], W

@@ -2,9 +2,11 @@
 """Output bits of the streaming engines as one line, for comparing two trees' host code (or two library builds, TIP_LIB=<path>.so) on
 one machine: sha256 prefixes over every frame's s_rest, c_t, y_last (and T / valid where the engine returns them).
 
-    python tools/stream_digest.py [--tree DIR] [--frames 100] [--streams 1,256,1024]     -> DIGEST {...}   (sorted keys; compare with cmp)
-
+    python tools/stream_digest.py [--tree DIR] [--frames 100] [--streams 1,256,1024] [--window 40]   -> DIGEST {...}   (sorted keys;
+                                                                                                        compare with cmp)
   --tree DIR   the directory whose tip_amd.py is imported (default: this file's own tree)
+  --window W   the window length of every engine (default 40, the 40-row kernels; any other length runs the _w kernels and leaves
+               the reuse engine out, whose ring holds 40-frame windows)
 
 Per model shape — the paper's (90, 131) and (72, 119) — and per source — the committed runner trace (tests/golden/tip_runner_golden.npz:
 2 streams, 70 frames) and a random closed loop of --frames frames at each stream count: lock-step launch / graph / reuse, staggered
@@ -77,7 +79,9 @@ def main():
     ap.add_argument("--tree", default=HERE)
     ap.add_argument("--frames", type=int, default=100)
     ap.add_argument("--streams", default="1,256,1024")
+    ap.add_argument("--window", type=int, default=40)
     a = ap.parse_args()
+    W = a.window
     tree = os.path.abspath(a.tree)
     sys.path.insert(0, tree)
     import tip_amd
@@ -86,12 +90,16 @@ def main():
     loops = {"trace": runner_trace(tree)}
     for n in (int(s) for s in a.streams.split(",")):
         loops[f"n{n}"] = random_loop(n, a.frames)
-    engines = {"lock_launch": lambda m, s: S.StreamingEngine(m, s), "lock_graph": lambda m, s: S.StreamingEngine(m, s, use_graph=True),
+    kw = {} if W == 40 else {"window": W}          # (a --tree from before the window keyword still runs at 40)
+    engines = {"lock_launch": lambda m, s: S.StreamingEngine(m, s, **kw),
+               "lock_graph": lambda m, s: S.StreamingEngine(m, s, use_graph=True, **kw),
                "lock_reuse": lambda m, s: S.StreamingEngine(m, s, reuse=True),
-               "stag_launch": lambda m, s: S.StaggeredStreamingEngine(m, s),
-               "stag_graph": lambda m, s: S.StaggeredStreamingEngine(m, s, use_graph=True),
-               "pool_launch": lambda m, s: S.StaggeredStreamingEngine(m, s, compact=True),
-               "pool_graph": lambda m, s: S.StaggeredStreamingEngine(m, s, use_graph=True, compact=True)}
+               "stag_launch": lambda m, s: S.StaggeredStreamingEngine(m, s, **kw),
+               "stag_graph": lambda m, s: S.StaggeredStreamingEngine(m, s, use_graph=True, **kw),
+               "pool_launch": lambda m, s: S.StaggeredStreamingEngine(m, s, compact=True, **kw),
+               "pool_graph": lambda m, s: S.StaggeredStreamingEngine(m, s, use_graph=True, compact=True, **kw)}
+    if W != 40:
+        del engines["lock_reuse"]                  # the reuse ring holds 40-frame windows
     digest = {}
     for shape, cfg in (("90x131", paper), ("72x119", dict(paper, size_s=119, with_acc_sum=False))):
         m = model_for(tip_amd, synth, cfg)
