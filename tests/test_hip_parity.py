@@ -585,12 +585,17 @@ def test_general_plan_configuration_sweep(D, H, F, L, R, with_rnn, acc, B, T):
     assert np.array_equal(yl, y[:, -1])
 
 
-@pytest.mark.parametrize("cfgname", ["paper", "tiny", "scaled2", "no_rnn"])
+@pytest.mark.parametrize("cfgname", ["paper", "tiny", "scaled2", "no_rnn", "no_acc_sum", "size_s_119", "train_default"])
 def test_device_packer_builds_the_same_image_as_the_host_packer(cfgname):
-    """tip_pack_weights_device (descriptor-driven kernel) vs tip_pack_weights (host loops): two independent
-    implementations of the packed layout and its folds must agree bit for bit."""
+    """tip_pack_weights_device (pack_ops_kernel) vs tip_pack_weights (a host loop): both read ONE description of the packed
+    layout and its folds — the PackOp list of csrc/tip_pack.hip — and share the function that gives an element's value
+    (pack_row + pack_value); the kernel decodes the storage order from the element index, the host walks rows.  They must
+    agree bit for bit.  What the description itself says is pinned on the CPU: test_packed_image_matches_the_pinned_digests
+    (tests/test_host_cpu.py) holds the host's bytes, for these seven configurations and seed, to the digests of the
+    hand-written host packer that preceded it.  So: device == host == that packer."""
     cfg = {"paper": synth.PAPER, "tiny": synth.TINY, "scaled2": dict(synth.SCALED, tf_layers=2),
-           "no_rnn": dict(synth.PAPER, with_rnn=False)}[cfgname]
+           "no_rnn": dict(synth.PAPER, with_rnn=False), "no_acc_sum": dict(synth.PAPER, with_acc_sum=False),
+           "size_s_119": dict(synth.PAPER, size_s=119), "train_default": synth.TRAIN_DEFAULT}[cfgname]
     m, _ = _gpu_model(cfg, 3)
     host = m.pack_host()
     dev = m.pack_device().cpu()

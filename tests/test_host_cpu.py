@@ -4,6 +4,7 @@ import ctypes
 import io
 import os
 import re
+import sys
 
 import numpy as np
 import pytest
@@ -13,6 +14,9 @@ import tip_amd
 from tip_amd import synth
 from tip_amd import lib as tlib
 from conftest import ROOT, cfg_for_tag, seed_for_tag
+
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import make_packed_digest   # noqa: E402  (the digests' configurations and how an image is digested)
 
 
 def make_model(cfg, p_state=0.0, dropout=0.0):
@@ -307,6 +311,23 @@ def test_packed_image_folds():
     blk = flat[off + (nb * 32 + kb) * 256: off + (nb * 32 + kb + 1) * 256].reshape(64, 4)
     exp = np.array([[whh[nb * 16 + (l & 15), kb * 16 + 4 * (l >> 4) + s] for s in range(4)] for l in range(64)])
     assert np.array_equal(blk, exp)
+
+
+@pytest.mark.parametrize("name", ["paper", "no_acc_sum", "size_s_119", "no_rnn", "tiny", "train_default", "scaled2"])
+def test_packed_image_matches_the_pinned_digests(name):
+    """The image tip_pack_weights builds — the host loop over the one PackOp description of csrc/tip_pack.hip — has, byte for
+    byte, the length and SHA-256 that the hand-written host packer before it produced (tests/golden/tip_packed_digest.json
+    names the commit).  The GPU test test_device_packer_builds_the_same_image_as_the_host_packer ties the kernel to the same
+    bytes."""
+    import json
+    mk = make_packed_digest
+    with open(mk.PATH) as f:
+        pinned = json.load(f)["images"]
+    assert sorted(pinned) == sorted(mk.configs())
+    nbytes, sha = mk.image_digest(mk.configs()[name])
+    print(name, nbytes, sha)
+    assert nbytes == pinned[name]["bytes"]
+    assert sha == pinned[name]["sha256"]
 
 
 def test_zero_edit_drop_in_import_path():

@@ -1,5 +1,5 @@
-// tip_abi.hip — the C-ABI of libtip_hip.so (include/tip_hip.h): handle, packed weight image, workspace
-// carve-up and the forward orchestration.  No torch types, no exceptions across the boundary.
+// tip_abi.hip — the C-ABI of libtip_hip.so (include/tip_hip.h): handle, workspace carve-up and the forward's launch
+// sequences (the packed weight image is tip_pack.hip's).  No torch types, no exceptions across the boundary.
 #include <math.h>
 #include <string.h>
 
@@ -27,63 +27,6 @@ const char* kStatusText[] = {
 };
 
 size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
-// packed image builder: offsets are in floats, every section 64-float (256 B) aligned
-struct Carver {
-    size_t off = 0;
-    size_t take(size_t n) {
-        size_t o = off;
-        off = align_up(off + n, 64);
-        return o;
-    }
-};
-
-PackedLinear carve_linear(Carver& c, int N, int K) {
-    PackedLinear p;
-    p.N = N;
-    p.K = K;
-    p.Npad = round_up(N, kGemmBN);
-    p.Kpad = round_up(K, kGemmBK);
-    p.w_off = c.take((size_t)p.Npad * p.Kpad);
-    p.b_off = c.take((size_t)p.Npad);
-    return p;
-}
-
-void build_layout(tip_handle* h) {
-    const Dims& d = h->d;
-    Carver c;
-    PackedLayout& L = h->lay;
-    L.in_lin = carve_linear(c, d.D, d.In);
-    L.layers.assign(d.L, PackedLayer{});
-    for (int l = 0; l < d.L; ++l) {
-        PackedLayer& pl = L.layers[l];
-        pl.qkv = carve_linear(c, 3 * d.D, d.D);
-        pl.out = carve_linear(c, d.D, d.D);
-        pl.ff1 = carve_linear(c, d.F, d.D);
-        pl.ff2 = carve_linear(c, d.D, d.F);
-        pl.g1_off = c.take(d.D);
-        pl.be1_off = c.take(d.D);
-        pl.g2_off = c.take(d.D);
-        pl.be2_off = c.take(d.D);
-        // big linears also in MFMA fragment order for the panel GEMM (tip_fused2.hip, launch_pgemm)
-        for (PackedLinear* p : {&pl.qkv, &pl.out, &pl.ff1, &pl.ff2})
-            if (pgemm_shape_ok(1 << 20, p->N, p->K)) p->f_off = c.take((size_t)p->N * p->K);
-    }
-    if (d.with_rnn) {
-        L.rnn_ih = carve_linear(c, d.R, d.D);
-        L.whh_frag_off = c.take((size_t)d.R * d.R);
-        L.out_lin = carve_linear(c, d.S, d.R);
-        L.out_frag_off = c.take((size_t)round_up(d.S, 16) * d.R);
-    } else {
-        L.rnn_ih = PackedLinear{};
-        L.whh_frag_off = 0;
-        L.out_lin = carve_linear(c, d.S, d.D);
-        L.out_frag_off = c.take((size_t)round_up(d.S, 16) * d.D);
-    }
-    L.fused_floats = fused_packed_floats(d);
-    L.fused_off = c.take(L.fused_floats);
-    L.total_floats = c.off;
-}
 
 void build_tensor_table(tip_handle* h) {
     const Dims& d = h->d;
@@ -118,15 +61,6 @@ void build_tensor_table(tip_handle* h) {
         add("linear.weight", d.S, d.D);
     }
     add("linear.bias", d.S, 0);
-}
-
-void pack_linear(float* img, const PackedLinear& p, const float* W, const float* b) {
-    float* w = img + p.w_off;
-    memset(w, 0, sizeof(float) * (size_t)p.Npad * p.Kpad);
-    for (int n = 0; n < p.N; ++n) memcpy(w + (size_t)n * p.Kpad, W + (size_t)n * p.K, sizeof(float) * p.K);
-    float* bb = img + p.b_off;
-    memset(bb, 0, sizeof(float) * p.Npad);
-    if (b) memcpy(bb, b, sizeof(float) * p.N);
 }
 
 }  // namespace
@@ -443,175 +377,14 @@ int tip_packed_bytes(const tip_handle* h, size_t* bytes) {
     return TIP_OK;
 }
 
+// The packed image from host tensors into host memory, and from device tensors into device memory (`packed_dev` is then ready for
+// tip_attach_packed): one description of the image, two interpreters of it (tip_pack.hip)
 int tip_pack_weights(const tip_handle* h, const float* const* t, int n, void* packed_host_out, size_t bytes) {
-    if (!h || !t || !packed_host_out) return TIP_ERR_INVALID_ARG;
-    if (n != (int)h->tensor_names.size()) return TIP_ERR_INVALID_ARG;
-    if (bytes < h->lay.total_floats * sizeof(float)) return TIP_ERR_INVALID_ARG;
-    for (int i = 0; i < n; ++i)
-        if (!t[i]) return TIP_ERR_INVALID_ARG;
-    const Dims& d = h->d;
-    const PackedLayout& L = h->lay;
-    float* img = static_cast<float*>(packed_host_out);
-    memset(img, 0, L.total_floats * sizeof(float));
-
-    // in_linear with the channel shuffle (:88-89) folded into its rows and the root-velocity zeroing (:75)
-    // folded into its columns: packed row a*H + b = reference row b*dh + a.
-    {
-        const PackedLinear& p = L.in_lin;
-        float* w = img + p.w_off;
-        float* b = img + p.b_off;
-        for (int a = 0; a < d.dh; ++a)
-            for (int hb = 0; hb < d.H; ++hb) {
-                const int nn = a * d.H + hb, old = hb * d.dh + a;
-                memcpy(w + (size_t)nn * p.Kpad, t[0] + (size_t)old * d.In, sizeof(float) * d.In);
-                for (int c = d.rootv0; c < d.rootv1; ++c) w[(size_t)nn * p.Kpad + d.n_imu_total + c] = 0.f;
-                b[nn] = t[1][old];
-            }
-    }
-    for (int l = 0; l < d.L; ++l) {
-        const float* const* lw = t + 2 + 12 * l;
-        const PackedLayer& pl = L.layers[l];
-        pack_linear(img, pl.qkv, lw[0], lw[1]);
-        if (d.fold_q_scale) {
-            const float sc = 1.0f / sqrtf((float)d.dh);  // power of two: exact
-            float* w = img + pl.qkv.w_off;
-            float* b = img + pl.qkv.b_off;
-            for (size_t i = 0; i < (size_t)d.D * pl.qkv.Kpad; ++i) w[i] *= sc;
-            for (int i = 0; i < d.D; ++i) b[i] *= sc;
-        }
-        pack_linear(img, pl.out, lw[2], lw[3]);
-        pack_linear(img, pl.ff1, lw[4], lw[5]);
-        pack_linear(img, pl.ff2, lw[6], lw[7]);
-        for (const PackedLinear* p : {&pl.qkv, &pl.out, &pl.ff1, &pl.ff2}) {
-            if (!p->f_off) continue;
-            // from the packed row-major copy (which already carries the folds) to [N/16][K/16][64 lanes][4]
-            const float* w = img + p->w_off;
-            float* f = img + p->f_off;
-            const int KBn = p->K / 16;
-            for (int nb = 0; nb < p->N / 16; ++nb)
-                for (int kb = 0; kb < KBn; ++kb)
-                    for (int lane = 0; lane < 64; ++lane)
-                        for (int s4 = 0; s4 < 4; ++s4)
-                            f[((size_t)(nb * KBn + kb) * 64 + lane) * 4 + s4] =
-                                w[(size_t)(nb * 16 + (lane & 15)) * p->Kpad + kb * 16 + 4 * (lane >> 4) + s4];
-        }
-        memcpy(img + pl.g1_off, lw[8], sizeof(float) * d.D);
-        memcpy(img + pl.be1_off, lw[9], sizeof(float) * d.D);
-        memcpy(img + pl.g2_off, lw[10], sizeof(float) * d.D);
-        memcpy(img + pl.be2_off, lw[11], sizeof(float) * d.D);
-    }
-    const float* const* tw = t + 2 + 12 * d.L;
-    if (d.with_rnn) {
-        pack_linear(img, L.rnn_ih, tw[0], tw[2]);
-        float* b = img + L.rnn_ih.b_off;
-        for (int i = 0; i < d.R; ++i) b[i] = tw[2][i] + tw[3][i];  // b_ih + b_hh
-        const int KB = d.R / 16;
-        float* f = img + L.whh_frag_off;
-        for (int nb = 0; nb < KB; ++nb)
-            for (int kb = 0; kb < KB; ++kb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int s = 0; s < 4; ++s)
-                        f[((size_t)(nb * KB + kb) * 64 + lane) * 4 + s] =
-                            tw[1][(size_t)(nb * 16 + (lane & 15)) * d.R + kb * 16 + 4 * (lane >> 4) + s];
-        pack_linear(img, L.out_lin, tw[4], tw[5]);
-    } else {
-        pack_linear(img, L.out_lin, tw[0], tw[1]);
-    }
-    {
-        // out-linear in fragment order for the skinny head GEMM
-        const int K = d.with_rnn ? d.R : d.D, KB = K / 16, NBo = round_up(d.S, 16) / 16;
-        const float* Wo = d.with_rnn ? tw[4] : tw[0];
-        float* f = img + L.out_frag_off;
-        for (int nb = 0; nb < NBo; ++nb)
-            for (int kb = 0; kb < KB; ++kb)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int s4 = 0; s4 < 4; ++s4) {
-                        const int n = nb * 16 + (lane & 15), k = kb * 16 + 4 * (lane >> 4) + s4;
-                        f[((size_t)(nb * KB + kb) * 64 + lane) * 4 + s4] = n < d.S ? Wo[(size_t)n * K + k] : 0.f;
-                    }
-    }
-    if (L.fused_floats) fused_pack(d, t, img + L.fused_off);
-    return TIP_OK;
+    return pack_weights_host(h, t, n, packed_host_out, bytes);
 }
 
-// The same image built on the GPU from device tensors (tip_pack.hip); `packed_dev` is then ready for tip_attach_packed.
 int tip_pack_weights_device(const tip_handle* h, const float* const* t, int n, void* packed_dev, size_t bytes, void* stream) {
-    if (!h || !t || !packed_dev) return TIP_ERR_INVALID_ARG;
-    if (n != (int)h->tensor_names.size()) return TIP_ERR_INVALID_ARG;
-    if (bytes < h->lay.total_floats * sizeof(float)) return TIP_ERR_INVALID_ARG;
-    for (int i = 0; i < n; ++i)
-        if (!t[i]) return TIP_ERR_INVALID_ARG;
-    const Dims& d = h->d;
-    const PackedLayout& L = h->lay;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    std::vector<PackOp> ops;
-    auto op = [](const float* src, size_t dst, int N, int K, int src_rows, int src_cols, int frag) {
-        PackOp o;
-        o.src = src; o.src2 = nullptr; o.dst_off = dst; o.N = N; o.K = K; o.src_rows = src_rows; o.src_cols = src_cols; o.frag = frag;
-        o.shuffle_h = 0; o.shuffle_dh = 0; o.z0 = 0; o.z1 = 0; o.scale_rows = 0; o.scale = 1.f; o.transpose = 0;
-        return o;
-    };
-    auto linear = [&](const PackedLinear& p, const float* W, const float* b) {
-        ops.push_back(op(W, p.w_off, p.Npad, p.Kpad, p.N, p.K, 0));
-        ops.push_back(op(b, p.b_off, p.Npad, 1, p.N, 1, 0));
-    };
-    {
-        PackOp w = op(t[0], L.in_lin.w_off, L.in_lin.Npad, L.in_lin.Kpad, d.D, d.In, 0);
-        w.shuffle_h = d.H; w.shuffle_dh = d.dh;
-        w.z0 = d.n_imu_total + d.rootv0; w.z1 = d.n_imu_total + d.rootv1;
-        ops.push_back(w);
-        PackOp b = op(t[1], L.in_lin.b_off, L.in_lin.Npad, 1, d.D, 1, 0);
-        b.shuffle_h = d.H; b.shuffle_dh = d.dh;
-        ops.push_back(b);
-    }
-    for (int l = 0; l < d.L; ++l) {
-        const float* const* lw = t + 2 + 12 * l;
-        const PackedLayer& pl = L.layers[l];
-        linear(pl.qkv, lw[0], lw[1]);
-        if (d.fold_q_scale) {
-            const float sc = 1.0f / sqrtf((float)d.dh);
-            ops[ops.size() - 2].scale = sc; ops[ops.size() - 2].scale_rows = d.D;
-            ops[ops.size() - 1].scale = sc; ops[ops.size() - 1].scale_rows = d.D;
-        }
-        linear(pl.out, lw[2], lw[3]);
-        linear(pl.ff1, lw[4], lw[5]);
-        linear(pl.ff2, lw[6], lw[7]);
-        {
-            const PackedLinear* pls[4] = {&pl.qkv, &pl.out, &pl.ff1, &pl.ff2};
-            const float* src[4] = {lw[0], lw[2], lw[4], lw[6]};
-            for (int i = 0; i < 4; ++i) {
-                if (!pls[i]->f_off) continue;
-                PackOp f = op(src[i], pls[i]->f_off, pls[i]->N, pls[i]->K, pls[i]->N, pls[i]->K, 1);
-                if (i == 0 && d.fold_q_scale) {
-                    f.scale = 1.0f / sqrtf((float)d.dh);
-                    f.scale_rows = d.D;
-                }
-                ops.push_back(f);
-            }
-        }
-        ops.push_back(op(lw[8], pl.g1_off, d.D, 1, d.D, 1, 0));
-        ops.push_back(op(lw[9], pl.be1_off, d.D, 1, d.D, 1, 0));
-        ops.push_back(op(lw[10], pl.g2_off, d.D, 1, d.D, 1, 0));
-        ops.push_back(op(lw[11], pl.be2_off, d.D, 1, d.D, 1, 0));
-    }
-    const float* const* tw = t + 2 + 12 * d.L;
-    const float* Wo;
-    int Ko;
-    if (d.with_rnn) {
-        linear(L.rnn_ih, tw[0], tw[2]);
-        ops.back().src2 = tw[3];                                           // b_ih + b_hh
-        ops.push_back(op(tw[1], L.whh_frag_off, d.R, d.R, d.R, d.R, 1));
-        linear(L.out_lin, tw[4], tw[5]);
-        Wo = tw[4]; Ko = d.R;
-    } else {
-        linear(L.out_lin, tw[0], tw[1]);
-        Wo = tw[0]; Ko = d.D;
-    }
-    ops.push_back(op(Wo, L.out_frag_off, round_up(d.S, 16), Ko, d.S, Ko, 1));
-    if (L.fused_floats) fused_pack_ops(d, t, L.fused_off, ops);
-    if (hipMemsetAsync(packed_dev, 0, L.total_floats * sizeof(float), s) != hipSuccess) return TIP_ERR_HIP;
-    if (run_pack_ops(ops, static_cast<float*>(packed_dev), s) != hipSuccess) return TIP_ERR_HIP;
-    return TIP_OK;
+    return pack_weights_device(h, t, n, packed_dev, bytes, static_cast<hipStream_t>(stream));
 }
 
 int tip_attach_packed(tip_handle* h, const void* packed_device, size_t bytes) {

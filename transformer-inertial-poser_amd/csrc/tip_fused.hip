@@ -73,103 +73,47 @@ size_t fused_packed_floats(const Dims& d) {
     return fused_ih_off(d) + (fused_has_rnn_ih(d) ? (size_t)fz::R * fz::D + fz::R : 0) + fz::TAIL_PAD;
 }
 
-// W [N][K] row-major (K <= Kpad) -> 16x16x4 B-fragment order [N/16][Kpad/16][64 lanes][4]:
-//   dst[((nb*KB + kb)*64 + lane)*4 + s] = W[nb*16 + (lane&15)][kb*16 + 4*(lane>>4) + s]
-static void pack_frag(float* dst, const float* W, int N, int K, int Kpad, const int* row_map, float scale_rows_lt,
-                      int scale_n) {
-    const int KB = Kpad / 16;
-    for (int nb = 0; nb < N / 16; ++nb)
-        for (int kb = 0; kb < KB; ++kb)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int s = 0; s < 4; ++s) {
-                    const int n = nb * 16 + (lane & 15), k = kb * 16 + 4 * (lane >> 4) + s;
-                    const int src = row_map ? row_map[n] : n;
-                    float v = k < K ? W[(size_t)src * K + k] : 0.f;
-                    if (n < scale_n) v *= scale_rows_lt;
-                    dst[((size_t)(nb * KB + kb) * 64 + lane) * 4 + s] = v;
-                }
-}
-
-void fused_pack(const Dims& d, const float* const* t, float* dst) {
-    using namespace fz;
-    // in_linear: channel shuffle (:88-89) folded into rows, root-velocity columns (:75) zeroed
-    std::vector<int> map(D);
-    for (int a = 0; a < DH; ++a)
-        for (int b = 0; b < H; ++b) map[a * H + b] = b * DH + a;
-    std::vector<float> win((size_t)D * d.In);
-    memcpy(win.data(), t[0], sizeof(float) * win.size());
-    for (int n = 0; n < D; ++n)
-        for (int c = d.rootv0; c < d.rootv1; ++c) win[(size_t)n * d.In + d.n_imu_total + c] = 0.f;
-    pack_frag(dst + IN_W, win.data(), D, d.In, KIN, map.data(), 1.f, 0);
-    for (int n = 0; n < D; ++n) dst[IN_B + n] = t[1][map[n]];
-    for (int l = 0; l < d.L; ++l) {
-        const float* const* lw = t + 2 + 12 * l;
-        float* L = dst + LAYER0 + (size_t)l * LAYER_FLOATS;
-        pack_frag(L + QKV_W, lw[0], 3 * D, D, D, nullptr, 0.25f, D);  // 1/sqrt(16) folded into W_q (exact)
-        for (int i = 0; i < 3 * D; ++i) L[QKV_B + i] = lw[1][i] * (i < D ? 0.25f : 1.f);
-        pack_frag(L + WO_W, lw[2], D, D, D, nullptr, 1.f, 0);
-        memcpy(L + WO_B, lw[3], sizeof(float) * D);
-        pack_frag(L + W1_W, lw[4], F, D, D, nullptr, 1.f, 0);
-        memcpy(L + W1_B, lw[5], sizeof(float) * F);
-        pack_frag(L + W2_W, lw[6], D, F, F, nullptr, 1.f, 0);
-        memcpy(L + W2_B, lw[7], sizeof(float) * D);
-        memcpy(L + G1, lw[8], sizeof(float) * D);
-        memcpy(L + BE1, lw[9], sizeof(float) * D);
-        memcpy(L + G2, lw[10], sizeof(float) * D);
-        memcpy(L + BE2, lw[11], sizeof(float) * D);
-    }
-    if (fused_has_rnn_ih(d)) {
-        const float* const* tw = t + 2 + 12 * d.L;
-        float* I = dst + fused_ih_off(d);
-        pack_frag(I, tw[0], R, D, D, nullptr, 1.f, 0);
-        for (int i = 0; i < R; ++i) I[(size_t)R * D + i] = tw[2][i] + tw[3][i];
-    }
-}
-
-static PackOp mk_op(const float* src, size_t dst, int N, int K, int src_rows, int src_cols, int frag) {
-    PackOp o;
-    o.src = src; o.src2 = nullptr; o.dst_off = dst; o.N = N; o.K = K; o.src_rows = src_rows; o.src_cols = src_cols; o.frag = frag;
-    o.shuffle_h = 0; o.shuffle_dh = 0; o.z0 = 0; o.z1 = 0; o.scale_rows = 0; o.scale = 1.f; o.transpose = 0;
-    return o;
-}
-
-// the same image as fused_pack() above, as descriptors for the on-device packer
+// The fused section of the image: weights in 16x16x4 B-fragment order [N/16][Kpad/16][64 lanes][4],
+//   dst[((nb*KB + kb)*64 + lane)*4 + s] = W[nb*16 + (lane&15)][kb*16 + 4*(lane>>4) + s],
+// with the folds: channel shuffle (:88-89) into in_linear's rows, root-velocity columns (:75) zeroed, 1/sqrt(16) into W_q (exact)
 void fused_pack_ops(const Dims& d, const float* const* t, size_t base, std::vector<PackOp>& ops) {
     using namespace fz;
+    auto frag = [](const float* W, size_t dst, int N, int K) { return frag_op(W, dst, N, K, N, K); };
+    auto vec = [](const float* v, size_t dst, int N) { return rows_op(v, dst, N, 1, N, 1); };
     {
-        PackOp o = mk_op(t[0], base + IN_W, D, KIN, D, d.In, 1);
+        PackOp o = frag_op(t[0], base + IN_W, D, KIN, D, d.In);
         o.shuffle_h = H; o.shuffle_dh = DH;
         o.z0 = d.n_imu_total + d.rootv0; o.z1 = d.n_imu_total + d.rootv1;
         ops.push_back(o);
-        PackOp b = mk_op(t[1], base + IN_B, D, 1, D, 1, 0);
+        PackOp b = vec(t[1], base + IN_B, D);
         b.shuffle_h = H; b.shuffle_dh = DH;
         ops.push_back(b);
     }
     for (int l = 0; l < d.L; ++l) {
         const float* const* lw = t + 2 + 12 * l;
         const size_t L = base + LAYER0 + (size_t)l * LAYER_FLOATS;
-        PackOp q = mk_op(lw[0], L + QKV_W, 3 * D, D, 3 * D, D, 1);
+        PackOp q = frag(lw[0], L + QKV_W, 3 * D, D);
         q.scale = 0.25f; q.scale_rows = D;
         ops.push_back(q);
-        PackOp qb = mk_op(lw[1], L + QKV_B, 3 * D, 1, 3 * D, 1, 0);
+        PackOp qb = vec(lw[1], L + QKV_B, 3 * D);
         qb.scale = 0.25f; qb.scale_rows = D;
         ops.push_back(qb);
-        ops.push_back(mk_op(lw[2], L + WO_W, D, D, D, D, 1));
-        ops.push_back(mk_op(lw[3], L + WO_B, D, 1, D, 1, 0));
-        ops.push_back(mk_op(lw[4], L + W1_W, F, D, F, D, 1));
-        ops.push_back(mk_op(lw[5], L + W1_B, F, 1, F, 1, 0));
-        ops.push_back(mk_op(lw[6], L + W2_W, D, F, D, F, 1));
-        ops.push_back(mk_op(lw[7], L + W2_B, D, 1, D, 1, 0));
-        ops.push_back(mk_op(lw[8], L + G1, D, 1, D, 1, 0));
-        ops.push_back(mk_op(lw[9], L + BE1, D, 1, D, 1, 0));
-        ops.push_back(mk_op(lw[10], L + G2, D, 1, D, 1, 0));
-        ops.push_back(mk_op(lw[11], L + BE2, D, 1, D, 1, 0));
+        ops.push_back(frag(lw[2], L + WO_W, D, D));
+        ops.push_back(vec(lw[3], L + WO_B, D));
+        ops.push_back(frag(lw[4], L + W1_W, F, D));
+        ops.push_back(vec(lw[5], L + W1_B, F));
+        ops.push_back(frag(lw[6], L + W2_W, D, F));
+        ops.push_back(vec(lw[7], L + W2_B, D));
+        ops.push_back(vec(lw[8], L + G1, D));
+        ops.push_back(vec(lw[9], L + BE1, D));
+        ops.push_back(vec(lw[10], L + G2, D));
+        ops.push_back(vec(lw[11], L + BE2, D));
     }
     if (fused_has_rnn_ih(d)) {
         const float* const* tw = t + 2 + 12 * d.L;
         const size_t I = base + fused_ih_off(d);
-        ops.push_back(mk_op(tw[0], I, R, D, R, D, 1));
-        PackOp b = mk_op(tw[2], I + (size_t)R * D, R, 1, R, 1, 0);
+        ops.push_back(frag(tw[0], I, R, D));
+        PackOp b = vec(tw[2], I + (size_t)R * D, R);
         b.src2 = tw[3];
         ops.push_back(b);
     }
@@ -1376,18 +1320,10 @@ void fused_bwd_pack_ops(const Dims& d, const float* const* t, size_t base, std::
     for (int l = 0; l < d.L; ++l) {
         const float* const* lw = t + 2 + 12 * l;
         const size_t L = base + (size_t)l * fb::LAYER_FLOATS2;
-        PackOp a = mk_op(lw[6], L + fb::W2T, F, D, F, D, 1);   // linear2.weight is [D][F]: logical W2^T [F][D]
-        a.transpose = 1;
-        ops.push_back(a);
-        PackOp b = mk_op(lw[4], L + fb::W1T, D, F, D, F, 1);   // linear1.weight is [F][D]: logical W1^T [D][F]
-        b.transpose = 1;
-        ops.push_back(b);
-        PackOp o = mk_op(lw[2], L + fb::WOT, D, D, D, D, 1);         // out_proj.weight [D][D]: logical Wo^T
-        o.transpose = 1;
-        ops.push_back(o);
-        PackOp q = mk_op(lw[0], L + fb::WQT, D, 3 * D, D, 3 * D, 1);  // in_proj_weight [3D][D]: logical Wqkv^T [D][3D]
-        q.transpose = 1;
-        ops.push_back(q);
+        ops.push_back(frag_op(lw[6], L + fb::W2T, F, D, F, D, 1));          // linear2.weight is [D][F]: logical W2^T [F][D]
+        ops.push_back(frag_op(lw[4], L + fb::W1T, D, F, D, F, 1));          // linear1.weight is [F][D]: logical W1^T [D][F]
+        ops.push_back(frag_op(lw[2], L + fb::WOT, D, D, D, D, 1));          // out_proj.weight [D][D]: logical Wo^T
+        ops.push_back(frag_op(lw[0], L + fb::WQT, D, 3 * D, D, 3 * D, 1));  // in_proj_weight [3D][D]: logical Wqkv^T [D][3D]
     }
 }
 

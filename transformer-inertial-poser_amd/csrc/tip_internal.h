@@ -156,22 +156,57 @@ struct PackedLayout {
     size_t total_floats;
 };
 
-// One destination array of the packed image, as a function of one (or the sum of two) source tensors: used by the on-device
-// packer (tip_pack.hip).  dst element (n, k), n < N, k < K:  src[map(n)][k] (+ src2) for n < src_rows, k < src_cols and k
-// outside [z0, z1), times `scale` for n < scale_rows, else 0; stored row-major or in 16x16x4 B-fragment order.
+// One destination array of the packed image, as a function of one (or the sum of two) source tensors: THE description of the
+// image, read by the packing kernel and by the host loop alike (tip_pack.hip).  dst element (n, k), n < N, k < K:
+// src[map(n)][k] (+ src2) for n < src_rows, k < src_cols and k outside [z0, z1), times `scale` for n < scale_rows, else 0;
+// stored row-major or in 16x16x4 B-fragment order.  (A kernel argument inside PackBatch: fields, types and order are fixed.)
 struct PackOp {
-    const float* src;
-    const float* src2;
-    unsigned long long dst_off;   // float offset into the image
-    int N, K;
-    int src_rows, src_cols;
-    int frag;                     // 0: [N][K] row-major, 1: [N/16][K/16][64 lanes][4]
-    int shuffle_h, shuffle_dh;    // 0 = identity, else dst row a*H + b <- src row b*dh + a (channel shuffle :88-89)
-    int z0, z1;
-    int scale_rows;
-    float scale;
-    int transpose;                // 1: the source is stored [K][N] (src_rows = N, src_cols = K describe the LOGICAL matrix)
+    const float* src = nullptr;
+    const float* src2 = nullptr;
+    unsigned long long dst_off = 0;   // float offset into the image
+    int N = 0, K = 0;
+    int src_rows = 0, src_cols = 0;
+    int frag = 0;                     // 0: [N][K] row-major, 1: [N/16][K/16][64 lanes][4]
+    int shuffle_h = 0, shuffle_dh = 0;   // 0 = identity, else dst row a*H + b <- src row b*dh + a (channel shuffle :88-89)
+    int z0 = 0, z1 = 0;
+    int scale_rows = 0;
+    float scale = 1.f;
+    int transpose = 0;                // 1: the source is stored [K][N] (src_rows = N, src_cols = K describe the LOGICAL matrix)
 };
+// dst [N][K] row-major / in fragment order <- the logical source matrix [src_rows][src_cols], zero padded; folds are set on the result
+inline PackOp rows_op(const float* src, size_t dst, int N, int K, int src_rows, int src_cols, int transpose = 0) {
+    PackOp o;
+    o.src = src; o.dst_off = dst; o.N = N; o.K = K; o.src_rows = src_rows; o.src_cols = src_cols; o.transpose = transpose;
+    return o;
+}
+inline PackOp frag_op(const float* src, size_t dst, int N, int K, int src_rows, int src_cols, int transpose = 0) {
+    PackOp o = rows_op(src, dst, N, K, src_rows, src_cols, transpose);
+    o.frag = 1;
+    return o;
+}
+// What the two interpreters of a PackOp share (tip_pack.hip: pack_ops_kernel, run_pack_ops_host): the value of element (n, k) of
+// op's destination array, as the part that depends on the row alone and the part that depends on k.
+struct PackRow {
+    int src_row;   // the source row destination row n reads; < 0: none, the row is zero padding
+    bool scaled;   // `scale` applies to the row
+};
+__host__ __device__ __forceinline__ PackRow pack_row(const PackOp& op, int n) {
+    PackRow r;
+    r.src_row = n >= op.src_rows ? -1 : op.shuffle_h ? (n % op.shuffle_h) * op.shuffle_dh + n / op.shuffle_h : n;   // dst row a*H + b <- src row b*dh + a
+    r.scaled = n < op.scale_rows;
+    return r;
+}
+__host__ __device__ __forceinline__ float pack_value(const PackOp& op, const PackRow& r, int k) {
+    float v = 0.f;
+    if (r.src_row >= 0 && k < op.src_cols && !(k >= op.z0 && k < op.z1)) {
+        // [src_rows][src_cols] row-major, or stored transposed: a row part (constant along a row) and a k part
+        const size_t si = (size_t)r.src_row * (op.transpose ? 1 : op.src_cols) + (size_t)k * (op.transpose ? op.src_rows : 1);
+        v = op.src[si];
+        if (op.src2) v += op.src2[si];
+        if (r.scaled) v *= op.scale;
+    }
+    return v;
+}
 constexpr int kPackBatch = 32;
 struct PackBatch {
     PackOp ops[kPackBatch];
@@ -387,15 +422,19 @@ hipError_t launch_pgemm(const float* A, int lda, const float* wfrag, size_t wfra
 // launches (tip_train.hip lin_launch) call this
 void count_pgemm_launch();
 
-// ---- on-device packing (tip_pack.hip) ----
-hipError_t run_pack_ops(const std::vector<PackOp>& ops, float* img, hipStream_t s);
+// ---- the packed weight image (tip_pack.hip): its layout, its list of PackOps, and the two interpreters of that list ----
+void build_layout(tip_handle* h);
+hipError_t run_pack_ops(const std::vector<PackOp>& ops, float* img, hipStream_t s);   // img: device
+void run_pack_ops_host(const std::vector<PackOp>& ops, float* img);                   // img and every op's sources: host
+// bodies of tip_pack_weights / tip_pack_weights_device (t: host / device pointers)
+int pack_weights_host(const tip_handle* h, const float* const* t, int n, void* packed_host_out, size_t bytes);
+int pack_weights_device(const tip_handle* h, const float* const* t, int n, void* packed_dev, size_t bytes, hipStream_t s);
 
 // ---- fused plan (tip_fused.hip) ----
-// descriptors of the fused section for the on-device packer (t = 56 device pointers, base = float offset of the section)
+// the fused section of the image (t = the 56 tensors, base = float offset of the section)
 void fused_pack_ops(const Dims& d, const float* const* t, size_t base, std::vector<PackOp>& ops);
 bool fused_supported(const Dims& d, int T);
 size_t fused_packed_floats(const Dims& d);
-void fused_pack(const Dims& d, const float* const* tensors, float* dst);
 bool fused_has_rnn_ih(const Dims& d);
 // xout [B,T,D] and/or ih_out [B,T,R] (RNN input projection incl. b_ih+b_hh); either may be null
 hipError_t launch_fused_encoder(const Dims& d, const float* fused_w, const float* x_imu, const float* x_s,

@@ -1638,20 +1638,14 @@ int tip_train_forward(tip_handle* h, const float* const* params, int n_params, c
         std::vector<PackOp> ops;
         fused_pack_ops(d, params, L.fused_img, ops);
         if (fused_prep) {
-            auto op = [&](const float* src, size_t dst, int N, int K, int src_rows, int src_cols, int frag, int transpose) {
-                PackOp o;
-                o.src = src; o.src2 = nullptr; o.dst_off = dst; o.N = N; o.K = K; o.src_rows = src_rows; o.src_cols = src_cols; o.frag = frag;
-                o.shuffle_h = 0; o.shuffle_dh = 0; o.z0 = 0; o.z1 = 0; o.scale_rows = 0; o.scale = 1.f; o.transpose = transpose;
-                ops.push_back(o);
-            };
-            op(rp[PR_WHH], L.whh_f, d.R, d.R, d.R, d.R, 1, 0);                              // W_hh fragments (forward recurrence)
-            op(rp[PR_WHH], L.whh_b, d.R, d.R, d.R, d.R, 1, 1);                              // W_hh^T fragments (backward recurrence)
-            op(rp[PR_LIN_W], L.wout_t, d.R, round_up(d.S, 16), d.R, d.S, 0, 1);             // W_out^T [R][S padded to 16] (dH = dy W_out)
-            op(rp[PR_WIH], L.wih_t, d.D, d.R, d.D, d.R, 0, 1);                              // W_ih^T [D][R] (d_enc = delta W_ih)
+            ops.push_back(frag_op(rp[PR_WHH], L.whh_f, d.R, d.R, d.R, d.R));                           // W_hh fragments (forward recurrence)
+            ops.push_back(frag_op(rp[PR_WHH], L.whh_b, d.R, d.R, d.R, d.R, 1));                        // W_hh^T fragments (backward recurrence)
+            ops.push_back(rows_op(rp[PR_LIN_W], L.wout_t, d.R, round_up(d.S, 16), d.R, d.S, 1));       // W_out^T [R][S padded to 16] (dH = dy W_out)
+            ops.push_back(rows_op(rp[PR_WIH], L.wih_t, d.D, d.R, d.D, d.R, 1));                        // W_ih^T [D][R] (d_enc = delta W_ih)
             if (L.wout_f) {
-                op(rp[PR_WIH], L.wih_tf, d.D, d.R, d.D, d.R, 1, 1);                         // ... and in fragment order (win_gemm_kernel)
-                op(rp[PR_LIN_W], L.wout_tf, d.R, 160, d.R, d.S, 1, 1);                      // W_out^T fragments [R][160], zero padded (dH)
-                op(rp[PR_LIN_W], L.wout_f, 144, d.R, d.S, d.R, 1, 0);                       // W_out fragments [144][R] (forward projection)
+                ops.push_back(frag_op(rp[PR_WIH], L.wih_tf, d.D, d.R, d.D, d.R, 1));                   // ... and in fragment order (win_gemm_kernel)
+                ops.push_back(frag_op(rp[PR_LIN_W], L.wout_tf, d.R, 160, d.R, d.S, 1));                // W_out^T fragments [R][160], zero padded (dH)
+                ops.push_back(frag_op(rp[PR_LIN_W], L.wout_f, 144, d.R, d.S, d.R));                    // W_out fragments [144][R] (forward projection)
             }
         }
         TT(hipMemsetAsync(W + L.fused_img, 0, fused_packed_floats(d) * sizeof(float), s), "train_fused_pack");
@@ -1678,10 +1672,7 @@ int tip_train_forward(tip_handle* h, const float* const* params, int n_params, c
         std::vector<PackOp> ops;
         auto frag = [&](const float* src, size_t dst, int N, int K, bool tr) {
             if (!dst) return;
-            PackOp o;
-            o.src = src; o.src2 = nullptr; o.dst_off = dst; o.N = N; o.K = K; o.src_rows = N; o.src_cols = K; o.frag = 1;
-            o.shuffle_h = 0; o.shuffle_dh = 0; o.z0 = 0; o.z1 = 0; o.scale_rows = 0; o.scale = 1.f; o.transpose = tr ? 1 : 0;
-            ops.push_back(o);
+            ops.push_back(frag_op(src, dst, N, K, N, K, tr ? 1 : 0));
         };
         if (d.with_rnn) {
             frag(rp[PR_WIH], L.wih_f, d.R, d.D, false);

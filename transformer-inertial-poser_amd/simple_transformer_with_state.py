@@ -703,7 +703,8 @@ class TF_RNN_Past_State(nn.Module):
         return (str(device), list(map(_data_ptr, plist)), list(map(_version, plist)))
 
     def pack_host(self) -> torch.Tensor:
-        """Build the packed weight image (uint8 CPU tensor) from the current parameters."""
+        """Build the packed weight image (uint8 CPU tensor) from the current parameters (tip_pack_weights: the host loop over
+        the image's one description, csrc/tip_pack.hip)."""
         h = self._ensure_handle()
         host = [p.detach().to("cpu", torch.float32).contiguous() for p in self.state_dict().values()]
         out = torch.empty(h.packed_bytes(), dtype=torch.uint8)
@@ -720,8 +721,8 @@ class TF_RNN_Past_State(nn.Module):
         self._pack_epoch += 1
 
     def pack_device(self, device=None) -> torch.Tensor:
-        """Build the packed weight image ON the GPU from the live parameters (tip_pack_weights_device): same bytes as
-        pack_host(), no host round trip."""
+        """Build the packed weight image ON the GPU from the live parameters (tip_pack_weights_device: a kernel over the same
+        description pack_host() reads, hence the same bytes), no host round trip."""
         h = self._ensure_handle()
         device = torch.device(device) if device is not None else next(self.parameters()).device
         tensors = [p.detach().to(device, torch.float32).contiguous() for p in self.state_dict().values()]
