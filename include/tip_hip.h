@@ -461,6 +461,53 @@ TIP_API int tip_replay_collect(long long* cur, const long long* end, int n_slots
                        const float* y_slot, const int* rows_slot, int size_s, float* s_out, float* c_out, float* y_out,
                        unsigned char* valid, tip_stream_t stream);
 
+/* ---- sensor front end: raw IMU packets and the per-slot calibration, in front of the `raw_imu` every ingest above takes — the
+ *      arithmetic the reference's live demo does on the host between its socket reader and RTRunner.step (live_demo_new.py:97-112
+ *      packet -> readings, :150-158 / :221-226 heading reset, :243-248 / :52-62 T-pose, :161-175 the per-frame transform).
+ *      A packet is packets[n,42] fp32, row-major: per sensor q0 q1 q2 q3 ax ay az, the quaternion read as (x, y, z, w) and normalised
+ *      — what the demo hands to fairmotion's Q2R, i.e. scipy's Rotation.from_quat(q).as_matrix() — and the acceleration in the
+ *      sensor's frame.  `cal` is a caller-owned device buffer of tip_sensor_state_bytes() (8-byte aligned), one block per slot: the
+ *      126-float TABLE R_Gn_Gp[6][9] | acc_offset[6][3] | R_B0_S0[6][9] (fp32), fp64 sums [72], a sample count, a phase word, and
+ *      the fp64 form of R_Gn_Gp.  Phases: 0 uncalibrated, 1 accumulating heading, 2 heading done, 3 accumulating T-pose, 4 live.
+ *      tip_sensor_reset: every block to phase 0 (required once: fresh memory holds garbage phases).
+ *      tip_sensor_begin: for each j < count, slot slots[j] starts a hold: sums and count to zero, and with TIP_SENSOR_HEADING phase
+ *        0 | 2 | 4 -> 1, with TIP_SENSOR_TPOSE phase 2 -> 3 (also how a T-pose is taken again after a finished heading).  A begin
+ *        this rule does not allow leaves the block untouched.
+ *      tip_sensor_accumulate: every slot in phase 1 or 3 adds its packet's six Q2R matrices (fp64, from the fp32 quaternion) and six
+ *        raw accelerations to its sums and bumps its count; slots in any other phase are not written at all.
+ *      tip_sensor_finish: a listed slot in phase 1: R_Gn_Gp = the mean matrices AS THEY ARE (the demo does not re-orthonormalise),
+ *        acc_offset = the mean accelerations, phase 2.  In phase 3: R_B0_S0 = R_Gp_B0^T (R_Gn_Gp^T mean) in fp64, rounded once to
+ *        fp32, phase 4.  R_Gp_B0: DEVICE double [6][9] (8-byte aligned), or null for the demo's aligned T-pose
+ *        [[0,0,1],[1,0,0],[0,1,0]] for all six sensors.  A finish with count 0 writes NaN tables; a listed slot in any other phase
+ *        is untouched.
+ *      tip_sensor_set / tip_sensor_get: tables[count,126] into / out of the listed slots' blocks.  A set makes the slot live (phase
+ *        4): a saved calibration is put back without the two holds.  A get does not look at the phase.
+ *      tip_sensor_transform: the per-frame launch.  raw_out[n,72] by slot — a streaming engine's raw_imu — from packets[n,42], fp32:
+ *        R_Gp_St = R_Gn_Gp^T Q2R(q), columns 9k .. 9k+8 = R_Gp_St R_B0_S0^T, columns 54+3k .. 54+3k+2 = clip(R_Gp_St acc -
+ *        acc_offset, +-max_acc) (the demo's MAX_ACC is 10; max_acc < 0 or NaN: TIP_ERR_INVALID_ARG).  The clip is np.clip's: a NaN
+ *        stays a NaN.  A zero or non-finite quaternion (scipy raises there) gives that sensor's nine rotation and three
+ *        acceleration columns NaN and touches nothing else; a slot whose phase is not 4 gets a row of 72 NaN, never a finite row
+ *        from an unfinished calibration.  One thread per (slot, sensor), no argument that changes from frame to frame.
+ *      slots / tables / R_Gp_B0 are DEVICE arrays.  A listed slot outside [0, n_slots) is skipped (a get leaves its output row as it
+ *      was); a slot listed twice is written twice with the same values.  Null buffers, a negative n_slots or count:
+ *      TIP_ERR_INVALID_ARG; count = 0 or n_slots = 0 launches nothing.  Everything runs on `stream`, in order with the engine's frame:
+ *      tip_sensor_transform(cal, packets, n, 10.f, raw, stream); tip_stream_ingest(state, raw, ...); a hold of one slot runs between
+ *      the frames of the others (tip_amd.sensors.SensorFrontEnd; the engines' step_packets). */
+#define TIP_SENSOR_HEADING 1
+#define TIP_SENSOR_TPOSE   2
+TIP_API int tip_sensor_state_bytes(int n_slots, size_t* bytes);
+TIP_API int tip_sensor_reset(void* cal, int n_slots, tip_stream_t stream);
+TIP_API int tip_sensor_begin(void* cal, int n_slots, const int* slots, int count, int which, tip_stream_t stream);
+TIP_API int tip_sensor_accumulate(void* cal, const float* packets /* [n,42] */, int n_slots, tip_stream_t stream);
+TIP_API int tip_sensor_finish(void* cal, int n_slots, const int* slots, int count, const double* R_Gp_B0 /* [6,9] or null */,
+                      tip_stream_t stream);
+TIP_API int tip_sensor_set(void* cal, int n_slots, const int* slots, int count, const float* tables /* [count,126] */,
+                   tip_stream_t stream);
+TIP_API int tip_sensor_get(const void* cal, int n_slots, const int* slots, int count, float* tables_out /* [count,126] */,
+                   tip_stream_t stream);
+TIP_API int tip_sensor_transform(const void* cal, const float* packets /* [n,42] */, int n_slots, float max_acc,
+                         float* raw_out /* [n,72] */, tip_stream_t stream);
+
 /* ---- exact streaming reuse: tip_forward for lock-stepped streams whose windows slide by one frame per call.
  *      In the runner a frame's model inputs never change once recorded (real_time_runner_minimal.py:74,85,137: raw_imu_buffer,
  *      s_and_c_in_buffer and imu_acc_sum_buffer are append-only), so with the stochastic parts off — past_state_dropout = 0, in_dropout = 0,

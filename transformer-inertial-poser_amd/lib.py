@@ -30,6 +30,7 @@ TIP_RNN_CLUSTER_ROWS4 = 0x44   # TIP_OPT_RNN_CLUSTER value: 4-window tiles on 4-
 TIP_ERR_HANDOFF = -8
 TIP_ERR_UNSUPPORTED_CONFIG = -2
 TIP_LOSS_Q, TIP_LOSS_C, TIP_LOSS_J, TIP_LOSS_STATS = 1, 2, 4, 16
+TIP_SENSOR_HEADING, TIP_SENSOR_TPOSE = 1, 2   # tip_sensor_begin: which hold starts
 
 # every symbol include/tip_hip.h declares (tests check that the .so exports exactly these + the hooks of tip_hip_debug.h)
 EXPORTS = (
@@ -45,6 +46,8 @@ EXPORTS = (
     "tip_stream_attach_w", "tip_stream_detach_w", "tip_stream_ingest_staggered_w", "tip_stream_consume_staggered_w",
     "tip_stream_ingest_mapped_w", "tip_stream_consume_mapped_w", "tip_stream_history_override_w",
     "tip_replay_feed", "tip_replay_collect",
+    "tip_sensor_state_bytes", "tip_sensor_reset", "tip_sensor_begin", "tip_sensor_accumulate", "tip_sensor_finish", "tip_sensor_set",
+    "tip_sensor_get", "tip_sensor_transform",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
     "tip_train_bytes_f64", "tip_train_forward_f64", "tip_train_backward_f64",
     "tip_combine_frames", "tip_combine_scratch_bytes", "tip_combine_sequence", "tip_gather_windows",
@@ -177,6 +180,15 @@ def load() -> ctypes.CDLL:
         getattr(lib, "tip_stream_" + name.replace("_shaped", "") + "_w").argtypes = at[:-1] + [i32, vp]
     lib.tip_replay_feed.argtypes = [vp, ctypes.c_longlong, vp, i32, vp, vp]
     lib.tip_replay_collect.argtypes = [vp, vp, i32, ctypes.c_longlong, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    # sensor front end (csrc/tip_sensor.hip): cal, then what the header lists, then the stream
+    lib.tip_sensor_state_bytes.argtypes = [i32, ctypes.POINTER(sz)]
+    lib.tip_sensor_reset.argtypes = [vp, i32, vp]
+    lib.tip_sensor_begin.argtypes = [vp, i32, vp, i32, i32, vp]
+    lib.tip_sensor_accumulate.argtypes = [vp, vp, i32, vp]
+    lib.tip_sensor_finish.argtypes = [vp, i32, vp, i32, vp, vp]
+    lib.tip_sensor_set.argtypes = [vp, i32, vp, i32, vp, vp]
+    lib.tip_sensor_get.argtypes = [vp, i32, vp, i32, vp, vp]
+    lib.tip_sensor_transform.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
     u64 = ctypes.c_ulonglong
     f32 = ctypes.c_float
     lib.tip_train_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz)]

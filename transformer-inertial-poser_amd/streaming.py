@@ -53,6 +53,10 @@ Model shapes (stream_shape below): the engines serve the four models the referen
 feature (x_imu 90 / 72 columns) times five or two stationary body points (size_s 131 / 119, c_t 20 / 8 columns) — and take the
 shape from the model.  override_history(q, slots): RTRunner with multi_sbp_terrain_and_correction feeds back a pose its host-side
 IK corrected, not the pose it returns (real_time_runner.py:483-495); the host hands that pose back between two frames.
+
+step_packets(front, packets), both engines: the frame from RAW sensor packets [n, 42] instead of the calibrated frame — `front` is a
+tip_amd.sensors.SensorFrontEnd (the live demo's calibration and per-frame transform, live_demo_new.py:161-175, on the device), whose
+one launch fills the engine's `raw`; everything behind "raw is filled" is step()'s (_step_filled), bit for bit.
 """
 from __future__ import annotations
 
@@ -311,6 +315,24 @@ class _StreamBase:
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
             self._call("history_override", self.state.data_ptr(), self.n, sl.data_ptr(), q.data_ptr(), len(idx))
 
+    # ---- raw IMU packets (tip_amd.sensors) ------------------------------------------------------------------------------------------
+    def _packets_to_raw(self, front, packets, slots, launch=True):
+        """The front half of step_packets: `front` (a sensors.SensorFrontEnd of this engine's n and device) takes the packets [n, 42]
+        into its buffer and ONE tip_sensor_transform launch writes the calibrated frame straight into self.raw — no intermediate
+        tensor, no device-to-device copy.  Every slot of `slots` must be live (the front end's host mirror): a refusal raises before
+        anything is copied or launched.  launch=False: checks only (a compact pool with nothing attached)."""
+        who = f"{type(self).__name__}.step_packets"
+        if getattr(front, "n", None) != self.n or getattr(front, "device", None) != self.device:
+            raise ValueError(f"tip_amd.{who}: the front end serves {getattr(front, 'n', None)} slots on {getattr(front, 'device', None)}, "
+                             f"the engine {self.n} on {self.device}")
+        for i in slots:
+            if not front.mirror.phase[i] == 4:
+                raise RuntimeError(f"tip_amd.{who}: slot {i} is not calibrated (phase {front.mirror.phase[i]}: finish its heading and "
+                                   "T-pose holds, or load() its tables, before it streams)")
+        if launch:
+            front._fill(packets, who)
+            front._transform_into(self.raw)
+
     # ---- the hand-off contract ------------------------------------------------------------------------------------------------------
     def _demotions(self):
         """Read by a frame body before and after its forward: a change says that the model answered a lost hand-off in between."""
@@ -468,17 +490,35 @@ class StreamingEngine(_StreamBase):
     def _captured_frame(self, key):
         return self._frame(self.raw, _lib.TIP_STREAM_FRAME_AUTO, _lib.TIP_STREAM_FRAME_AUTO, self.window, self._graph_ws, self._graph_y)
 
+    def _replays(self):
+        """This frame is a replay of the captured one (steady state, T = window): its input is self.raw."""
+        return self.use_graph and self.frame >= self.window + 4 and (self.live_dropout or not self.model.training)
+
     @torch.no_grad()
     def step(self, raw_imu: torch.Tensor) -> Optional[dict]:
-        f = self.frame
-        if self.use_graph and f >= self.window + 4 and (self.live_dropout or not self.model.training):
+        if self._replays():
             # steady state (T = window): one copy + one graph launch per frame
             self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
+            return self._step_filled(self.raw)
+        raw = torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72).to(self.device, non_blocking=True).contiguous()
+        return self._step_filled(raw)
+
+    @torch.no_grad()
+    def step_packets(self, front, packets) -> Optional[dict]:
+        """step() from raw IMU packets [n, 42] (tip_amd.sensors.SensorFrontEnd: layout, calibration): one tip_sensor_transform launch
+        fills the engine's `raw` on the device, then the frame runs as step() runs it.  Lock-step has no detached slots: every slot
+        of `front` must be live.  With use_graph=True the launch sits between two replays; nothing is re-captured."""
+        self._packets_to_raw(front, packets, range(self.n))
+        return self._step_filled(self.raw)
+
+    def _step_filled(self, raw) -> Optional[dict]:
+        """The frame behind "raw is filled" (raw: [n, 72] on the device; self.raw when the frame replays)."""
+        f = self.frame
+        if self._replays():
             with torch.cuda.device(self.device):
                 self._replay(None)
             self.frame = f + 1
             return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": self._y_last, "T": self.window}
-        raw = torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72).to(self.device, non_blocking=True).contiguous()
         T = int(self.lib.tip_stream_window_len_w(f, self.window))
         self.frame = f + 1          # (the frame is ingested whatever its forward does; a lost hand-off resets the counter)
         with torch.cuda.device(self.device):
@@ -764,11 +804,9 @@ class StaggeredStreamingEngine(_StreamBase):
                 if B not in self._graphs:
                     self._capture(B)
 
-    def _step_compact(self, raw_imu):
+    def _step_compact(self):
         k = len(self._positions)
         B = self.bucket(k)
-        if k:
-            self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
         with torch.cuda.device(self.device):
             self._flush()
             if k:
@@ -780,13 +818,32 @@ class StaggeredStreamingEngine(_StreamBase):
         self.frame += 1
         return {"s_rest": self.s_rest, "c_t": self.c_t, "y_last": self.y_slot, "T": T, "valid": T > 0, "active": k, "batch": B}
 
-    @torch.no_grad()
-    def step(self, raw_imu: torch.Tensor) -> dict:
+    def _needs_eval(self):
         if self.model.training and not self.live_dropout:
             raise RuntimeError("tip_amd.StaggeredStreamingEngine needs model.eval() (the inference kernels: forward_rows)")
+
+    @torch.no_grad()
+    def step(self, raw_imu: torch.Tensor) -> dict:
+        self._needs_eval()
+        if not self.compact or len(self._positions):          # (a compact pool with nothing attached launches nothing)
+            self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
+        return self._step_filled()
+
+    @torch.no_grad()
+    def step_packets(self, front, packets) -> dict:
+        """step() from raw IMU packets [n, 42] (tip_amd.sensors.SensorFrontEnd): one tip_sensor_transform launch fills the engine's
+        `raw` on the device, then the frame runs as step() runs it, plain and compact, launch by launch and replayed.  Every ATTACHED
+        slot must be live in `front` (its host mirror; RuntimeError otherwise, nothing launched); a detached slot may be anywhere in
+        its calibration — its holds run between the frames of the others (front.accumulate) — and its NaN row is never ingested."""
+        self._needs_eval()
+        self._packets_to_raw(front, packets, [i for i in range(self.n) if self._attached[i]],
+                             launch=not self.compact or len(self._positions) > 0)
+        return self._step_filled()
+
+    def _step_filled(self) -> dict:
+        """The frame behind "self.raw is filled"."""
         if self.compact:
-            return self._step_compact(raw_imu)
-        self.raw.copy_(torch.as_tensor(raw_imu, dtype=torch.float32).reshape(self.n, 72), non_blocking=True)
+            return self._step_compact()
         with torch.cuda.device(self.device):
             if self.use_graph:
                 self._replay(None)
