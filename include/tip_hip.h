@@ -291,7 +291,8 @@ TIP_API int tip_check(tip_handle* h, int clear);
  *          if (T > 0) { tip_forward(..., TIP_FWD_LAST_ROW_ONLY) -> y_last[n,131];
  *                       tip_stream_consume(state, y_last, n, f - 5, s_rest[n,111] (= s_t[3:114]), c_t[n,20], stream); }
  *      (widths of the paper's model; x_imu [.., 72|90], x_s / y_last [.., 119|131], c_t [.., 8|20] by the buffer's shape: "model shapes" below)
- *      PyBullet FK and the SBP root-translation correction (:169-194) stay with the host.
+ *      FK and the SBP root-translation correction (:169-194) are not part of the frame: tip_kin_track ("kinematics" below) consumes
+ *      s_rest / c_t beside it.  RTRunner's terrain map and IK stay with the host.
  *      HIP graphs: kernel arguments are frozen at capture, so once the window is full (frame_idx >= 43 has been ingested, T = 40
  *      from then on) both calls accept TIP_STREAM_FRAME_AUTO for frame_idx / call_idx — "the frame after the last one ingested",
  *      read from a counter the ingest kernel keeps in `state`.  The triple ingest(AUTO) -> tip_forward -> consume(AUTO) can then be
@@ -507,6 +508,53 @@ TIP_API int tip_sensor_get(const void* cal, int n_slots, const int* slots, int c
                    tip_stream_t stream);
 TIP_API int tip_sensor_transform(const void* cal, const float* packets /* [n,42] */, int n_slots, float max_acc,
                          float* raw_out /* [n,72] */, tip_stream_t stream);
+
+/* ---- kinematics: forward kinematics of the character, the root track with its SBP correction, and the evaluation script's seven
+ *      metrics — what the reference does through PyBullet behind RTRunnerMin.step (real_time_runner_minimal.py:159-194;
+ *      data_utils.py:262-306, 397-412, 473-548) and in offline_testing_simple.py --compare_gt (:422-453; data_utils.py:314-391).
+ *      None of it feeds back into the model, so none of it is inside a streaming frame: these entries CONSUME s_rest / c_t, as a
+ *      post-pass over whole recordings or as one more launch per live frame (tip_amd.kinematics).
+ *      `skel` is a caller-owned device buffer of tip_kin_skel_bytes() that the host fills (4-byte words):
+ *          int n_links (<= 32); int sbp[5] (body indices of lankle, rankle, lwrist, rwrist, root); int pad[2];
+ *          per link i < 32: int parent (body index: 0 the root, j + 1 link j, always below i + 1); int state_col (column of the
+ *          57-wide q where the link's axis-angle starts, -1 for a fixed joint); float joint_xyz[3], joint_q[4] (x, y, z, w: the joint
+ *          origin in the parent's link frame); float com_xyz[3] (the inertial origin in the link frame).
+ *      A pose is 7 floats, xyz + (x, y, z, w); a pose table is [rows, n_links + 1, 7], the root first, then the links in table order.
+ *      tip_kin_fk: q[n, ldq >= 57] (root xyz, root axis-angle, joint axis-angles) -> pq_g (COM poses: getLinkState fields 0-1) and,
+ *        when not null, pq_jf (link frames: fields 4-5).  Base at q[:3] with A2Q(q[3:6]); child frame = parent frame x joint origin x
+ *        A2Q(axis-angle), the identity for a fixed joint.  A2Q is scipy's from_rotvec().as_quat(): exact at angle 0, a series below
+ *        1e-3 rad.  fp32, one lane per pose.
+ *      `carry` is a caller-owned device buffer of tip_kin_carry_bytes() (8-byte aligned), one block per sequence: the corrected root
+ *        (fp64), the corrected pq_g of the last valid frame with positions about that root, and that frame's s_rest[54:57].
+ *      tip_kin_track_reset: for each j < count, block slots[j] (null: j) <- root = s_init[j, :3], pq_prev = FK(s_init[j]) (:47-50).
+ *      tip_kin_track: one kernel.  Sequence j < count uses block slots[j] (null: j) and rows begin[j] .. end[j] - 1 of s_rest[n_rows,111],
+ *        c_t[n_rows,nc] (nc 8 | 20), valid[n_rows] (bytes; null: every row valid), in order, and leaves the block ready for the next
+ *        chunk: a whole recording per call is the replay post-pass, one row per call the live frame, and any chunking gives the same
+ *        bits.  A row that is not valid: root_out = the carry's root, viz_out = 100, carry unchanged.  A valid row: the runner's
+ *        :159-194 — root_pre = root + v DT, FK, the residues of the active feet against pq_prev, nanmean, clip at +-0.5, the
+ *        flat-ground z rule with its norm test taken literally, then root, the five locations and the poses shifted by -vel_res DT.
+ *        v is the velocity :159 integrates, from BEFORE the pose averaging of :165-166, which s_rest[54:57] has been through:
+ *        v = 2 s_rest[54:57] - (the previous valid row's), and s_rest[54:57] itself on a block's first valid row.
+ *        FK is fp32 with the root at the origin; the scan and the root accumulator are fp64; the outputs root_out[n_rows,3] and
+ *        viz_out[n_rows,5,3] are fp32.  A non-finite row makes its own sequence's root NaN from there on and touches no other.
+ *      tip_kin_metrics: out[count,7] fp64 = angle, j_pos, root_2s, root_5s, root_10s, jerk, root_jerk of file j over rows
+ *        offsets[j] + start .. offsets[j + 1] - end - 1 of pred_qdq / gt_qdq [.., 114] and of their pose tables pq_pred / pq_gt (tip_kin_fk
+ *        of the same rows); i2, i5, i10 are the script's int(t / DT) - 1, clamped here to the rows in range.  A file with fewer than 4
+ *        rows in range gets NaN.  One workgroup per file, fp64 sums in a fixed order.
+ *      Null pointers and negative counts return TIP_ERR_INVALID_ARG; a zero count returns TIP_OK without a launch. */
+TIP_API int tip_kin_skel_bytes(size_t* bytes);
+TIP_API int tip_kin_carry_bytes(int n_slots, size_t* bytes);
+TIP_API int tip_kin_fk(const void* skel, const float* q /* [n,ldq] */, int ldq, long long n, float* pq_g /* [n,L+1,7] */,
+               float* pq_jf /* [n,L+1,7] or null */, tip_stream_t stream);
+TIP_API int tip_kin_track_reset(const void* skel, void* carry, int n_slots, const int* slots /* [count] or null */, int count,
+                        const float* s_init /* [count,114] */, tip_stream_t stream);
+TIP_API int tip_kin_track(const void* skel, void* carry, int n_slots, const int* slots /* [count] or null */, const long long* begin,
+                  const long long* end, int count, long long n_rows, const float* s_rest /* [n_rows,111] */,
+                  const float* c_t /* [n_rows,nc] */, int nc, const unsigned char* valid /* [n_rows] or null */,
+                  float* root_out /* [n_rows,3] */, float* viz_out /* [n_rows,5,3] */, tip_stream_t stream);
+TIP_API int tip_kin_metrics(const void* skel, const float* pred_qdq, const float* gt_qdq, const float* pq_pred, const float* pq_gt,
+                    const long long* offsets /* [count+1] */, int count, int start, int end, int i2, int i5, int i10,
+                    double* out /* [count,7] */, tip_stream_t stream);
 
 /* ---- exact streaming reuse: tip_forward for lock-stepped streams whose windows slide by one frame per call.
  *      In the runner a frame's model inputs never change once recorded (real_time_runner_minimal.py:74,85,137: raw_imu_buffer,

@@ -48,6 +48,7 @@ EXPORTS = (
     "tip_replay_feed", "tip_replay_collect",
     "tip_sensor_state_bytes", "tip_sensor_reset", "tip_sensor_begin", "tip_sensor_accumulate", "tip_sensor_finish", "tip_sensor_set",
     "tip_sensor_get", "tip_sensor_transform",
+    "tip_kin_skel_bytes", "tip_kin_carry_bytes", "tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_kin_metrics",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
     "tip_train_bytes_f64", "tip_train_forward_f64", "tip_train_backward_f64",
     "tip_combine_frames", "tip_combine_scratch_bytes", "tip_combine_sequence", "tip_gather_windows",
@@ -189,6 +190,13 @@ def load() -> ctypes.CDLL:
     lib.tip_sensor_set.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.tip_sensor_get.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.tip_sensor_transform.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
+    # kinematics (csrc/tip_kin.hip): the skeleton table, then what the header lists, then the stream
+    lib.tip_kin_skel_bytes.argtypes = [ctypes.POINTER(sz)]
+    lib.tip_kin_carry_bytes.argtypes = [i32, ctypes.POINTER(sz)]
+    lib.tip_kin_fk.argtypes = [vp, vp, i32, ctypes.c_longlong, vp, vp, vp]
+    lib.tip_kin_track_reset.argtypes = [vp, vp, i32, vp, i32, vp, vp]
+    lib.tip_kin_track.argtypes = [vp, vp, i32, vp, vp, vp, i32, ctypes.c_longlong, vp, vp, i32, vp, vp, vp, vp]
+    lib.tip_kin_metrics.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
     u64 = ctypes.c_ulonglong
     f32 = ctypes.c_float
     lib.tip_train_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz)]

@@ -17,8 +17,10 @@ Row conventions — those of test_run_ours_gpt_v4_with_c_rt_minimal (:123-134):
   - the five priming steps (t < 5) give s_init's rest, zero c_t, NaN y_last and valid False — what the runner returns while its
     smoother primes (real_time_runner_minimal.py:125-128);
   - so a recording with L_i <= 6 has no valid row, L_i = 1 runs nothing, and L_i = 0 is a ValueError.
-s_rest is s_t[3:114] of the runner (54 axis-angles, root velocity, zeros): root translation, PyBullet FK and the SBP root
-correction (real_time_runner_minimal.py:169-194) stay on the host, and s_rest[:, 54:57] is the root velocity a host integrates.
+s_rest is s_t[3:114] of the runner (54 axis-angles, root velocity, zeros).  Root translation, FK and the SBP root correction
+(real_time_runner_minimal.py:159-194) are a post-pass over this result, also on the device: tip_amd.kinematics.track_replay gives the
+script's s_traj_pred rows and viz_locs, kinematics.evaluate its seven metrics; neither touches the pool.  s_rest[:, 54:57] is the root
+velocity after the runner's pose averaging (:165-166), not the one :159 integrates: the tracker takes the averaging back out.
 trim_like_reference applies the script's shift by IMU_n_smooth + 2 rows (:148-151) to pose rows.
 
 Device side (csrc/tip_replay.hip; include/tip_hip.h: tip_replay_feed, tip_replay_collect): the corpus — every recording's frames

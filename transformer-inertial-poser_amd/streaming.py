@@ -8,8 +8,9 @@
 
 Everything between the raw IMU frame and the fed-back history row stays in HBM: ring buffers, smoothing, root-frame
 rotation, acc-sum feature, window gather, the forward pass (TIP_FWD_LAST_ROW_ONLY), output filter, SBP decode,
-6D <-> axis-angle and the pose averaging (csrc/tip_stream.hip).  PyBullet FK and the SBP root-translation correction
-(:169-194) remain the host's job (they never feed back into the model input).
+6D <-> axis-angle and the pose averaging (csrc/tip_stream.hip).  FK and the SBP root-translation correction
+(:169-194) never feed back into the model input, so they are not part of the frame: tip_amd.kinematics.RootTracker consumes
+out["s_rest"] / out["c_t"] in one more launch beside it.  RTRunner's terrain map and IK remain the host's job.
 
 reuse=True (include/tip_hip.h: tip_forward_reuse): a frame's model inputs never change once recorded
 (real_time_runner_minimal.py:74,85,137), so its in_linear row and its layer-0 Q / K / V rows are computed ONCE, when the frame enters,
