@@ -556,6 +556,49 @@ TIP_API int tip_kin_metrics(const void* skel, const float* pred_qdq, const float
                     const long long* offsets /* [count+1] */, int count, int start, int end, int i2, int i5, int i10,
                     double* out /* [count,7] */, tip_stream_t stream);
 
+/* ---- synthetic data: IMU readings and stationary-body-point (SBP) labels from pose sequences — the reference's offline generator
+ *      (data-gen-and-viz-bullet-new.py:44-218 over data_utils.py:27-100 get_rot_center_sample_based; bullet_agent.py for the scale),
+ *      for `count` ragged sequences held back to back: sequence j is rows offsets[j] .. offsets[j + 1] - 1 of every array, offsets
+ *      [count + 1] a DEVICE array from 0 up to n.  fp64 end to end; it produces what tip_combine_sequence consumes
+ *      (tip_amd.syndata.synthesize).  An offline producer beside the engines: no engine, graph or other kernel is involved.
+ *      `skel` is a caller-owned device buffer of tip_syn_skel_bytes(), 8-byte aligned, that the host fills — the fp64 form of the
+ *      kinematics table, with the IMU bodies:
+ *          int n_links (<= 32); int sbp[5] (body indices of lankle, rankle, lwrist, rwrist, root); int imu[6] (body indices of root,
+ *          lwrist, rwrist, lknee, rknee, upperneck; the first three are sbp[4], sbp[2], sbp[3]); int pad[4];
+ *          per link i < 32, 88 bytes: int parent; int state_col; double joint_xyz[3], joint_q[4], com_xyz[3] (as in "kinematics").
+ *      `grids` is a caller-owned device buffer of tip_syn_grid_bytes(), 8-byte aligned: the candidate points of the three body classes,
+ *      0 feet (SBP slots 0-1), 1 wrists (slots 2-3), 2 pelvis (slot 4), each
+ *          int n[3] (points per axis, <= 40); int pad; double axis[3][40] (the values of lp_x, lp_y, lp_z, built by the HOST with
+ *          the reference's np.arange expressions: the device never regenerates them);
+ *      point i of a class is (axis[0][ix], axis[1][iy], axis[2][iz]) with i = (iy n[0] + ix) n[2] + iz, the order of
+ *      np.meshgrid(lp_x, lp_y, lp_z) ravelled.  The launches serve 9 x 6 x 33, 5 x 5 x 5 and 31 x 25 x 8 points (1782 / 125 / 6200);
+ *      a class with more than 1792 / 128 / 6400 is cut there.
+ *      The tracked-pose block `poses` is [n, 8, 7] doubles, xyz + (x, y, z, w) per slot: slots 0-4 the SBP bodies in sbp order, slots
+ *      5-7 imu[3], imu[4], imu[5].  A slot whose body is the root (index 0) holds p + Q2R(Q) (0, 0.1, -0.1) with the root's Q — the
+ *      root IMU's and the pelvis SBP's point, the offset not scaled — and every other slot the body's COM pose.
+ *      tip_syn_poses: q[n, ldq >= 57] fp64 (as tip_kin_fk's) -> poses, FK in fp64 with every joint and COM offset and the root xyz of
+ *        sequence j multiplied by scale[j] (a DEVICE array [count]).  One lane per row.
+ *      tip_syn_imu: poses -> imu[n,72]: columns 0:54 six row-major Q2R matrices (scipy's as_matrix, the quaternion normalised first) of
+ *        slots 4, 2, 3, 5, 6, 7; columns 54:72 (p[t+4] + p[t-4] - 2 p[t]) / (4/60)^2 of the same slots with t clamped to rows 4 .. L - 5 of
+ *        the row's OWN sequence (rows 0-3 copy row 4, rows L-4 .. L-1 copy row L-5); NaN for a sequence of fewer than 9 rows.
+ *      tip_syn_sbp: poses -> constrs[n,20], five blocks of (flag, r).  `frames` is caller-owned scratch of n x 5 x 15 doubles, 8-byte
+ *        aligned: a first launch fills it with R, w, v per (row, slot) — what does not depend on the previous solution — and the chains
+ *        read it.  One workgroup per (sequence, slot), frames in order.  Rows 0, 1,
+ *        L-2, L-1 are zero.  Row t takes x1, q1 from row t-1 and x2, q2 from row t+1, dt = 2/60: v = (x2 - x1) / dt, w = (2 sub q2* / dt)[:3]
+ *        with sub = q2 - q1 if |q2 - q1| < |q2 + q1| else q2 + q1, R = Q2R(q2); the residue of point p is
+ *        |w x Rp + v| + 0.2 |Rp - (r_prev - v dt)| + 0.02 |Rp|, the middle term absent when row t-1 had no solution or t = 2.  The
+ *        solution is the first point of least residue in the order above; the flag is 1 and r = Rp iff that residue is < 0.15, else the
+ *        row is zero and the chain starts over.  A NaN residue never wins a comparison, so a non-finite row gives flag 0.
+ *      Null pointers, negative counts and misaligned buffers return TIP_ERR_INVALID_ARG; n = 0 returns TIP_OK without a launch. */
+TIP_API int tip_syn_skel_bytes(size_t* bytes);
+TIP_API int tip_syn_grid_bytes(size_t* bytes);
+TIP_API int tip_syn_poses(const void* skel, const double* q /* [n,ldq] */, int ldq, const long long* offsets /* [count+1] */, int count,
+                  const double* scale /* [count] */, long long n, double* poses /* [n,8,7] */, tip_stream_t stream);
+TIP_API int tip_syn_imu(const double* poses /* [n,8,7] */, const long long* offsets /* [count+1] */, int count, long long n,
+                double* imu /* [n,72] */, tip_stream_t stream);
+TIP_API int tip_syn_sbp(const void* grids, const double* poses /* [n,8,7] */, const long long* offsets /* [count+1] */, int count,
+                long long n, double* frames /* [n,5,15] scratch */, double* constrs /* [n,20] */, tip_stream_t stream);
+
 /* ---- exact streaming reuse: tip_forward for lock-stepped streams whose windows slide by one frame per call.
  *      In the runner a frame's model inputs never change once recorded (real_time_runner_minimal.py:74,85,137: raw_imu_buffer,
  *      s_and_c_in_buffer and imu_acc_sum_buffer are append-only), so with the stochastic parts off — past_state_dropout = 0, in_dropout = 0,

@@ -25,23 +25,12 @@
 // root as fp64; outputs are rounded to fp32 once.  The metrics are fp64 on the fp32 poses.
 //
 // Nothing waits on another workgroup; a carry block is written by the one wave whose sequence names it.
-#include "tip_internal.h"
+#include "tip_kin_fk.h"      // KinLinkT, a2q, qmul, qrot, fk_frames, fk_to_com: one body for fp32 (here) and fp64 (tip_syn.hip)
 
 namespace tip {
 
-namespace kn {
-constexpr int MAX_LINKS = 32, MAX_BODIES = 33, LANES = 64, COL = 65;      // COL: LDS column stride (odd: the transpose is conflict-free)
-constexpr int QDQ = 114, REST = 111, NQ = 57, SBPS = 5;
-constexpr double DT = 1.0 / 60;                                           // constants.py:7
-}  // namespace kn
-
 // The skeleton table as the device reads it (tip_amd.kinematics.Skeleton.pack writes it; include/tip_hip.h has the layout).
-struct KinLink {
-    int parent;                  // body index of the parent: 0 the root, i + 1 link i; always below this link's own body index
-    int state_col;               // column of the 57-wide q where the link's axis-angle starts, or -1 for a fixed joint
-    float jxyz[3], jq[4];        // joint origin in the parent's link frame
-    float com[3];                // inertial origin in the link frame
-};
+using KinLink = KinLinkT<float>;
 struct KinSkel {
     int n_links;
     int sbp[kn::SBPS];           // body indices of lankle, rankle, lwrist, rwrist, root
@@ -63,86 +52,13 @@ struct KinCarry {
 };
 static_assert(sizeof(KinCarry) == 1024, "KinCarry layout");
 
-template <typename F> __device__ __forceinline__ F kin_sqrt(F x) {
-    if constexpr (std::is_same<F, float>::value) return sqrtf(x);
-    else return sqrt(x);
-}
-
-// scipy's from_rotvec(a).as_quat(): exact at angle 0 (x = y = z = 0, w = cos 0 = 1), the series of sin(t / 2) / t below 1e-3 rad.
-template <typename F>
-__device__ __forceinline__ void a2q(F ax, F ay, F az, F* q) {
-    const F t2 = ax * ax + ay * ay + az * az;
-    const F t = kin_sqrt<F>(t2);
-    F s, w;
-    if (t <= F(1e-3)) {
-        s = F(0.5) - t2 / F(48) + t2 * t2 / F(3840);
-    } else {
-        if constexpr (std::is_same<F, float>::value) s = sinf(t * 0.5f) / t;
-        else s = sin(t * 0.5) / t;
-    }
-    if constexpr (std::is_same<F, float>::value) w = cosf(t * 0.5f);
-    else w = cos(t * 0.5);
-    q[0] = ax * s, q[1] = ay * s, q[2] = az * s, q[3] = w;
-}
-
-// Hamilton product, (x, y, z, w)
-template <typename F>
-__device__ __forceinline__ void qmul(const F* a, const F* b, F* o) {
-    const F x = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    const F y = a[3] * b[1] - a[0] * b[2] + a[1] * b[3] + a[2] * b[0];
-    const F z = a[3] * b[2] + a[0] * b[1] - a[1] * b[0] + a[2] * b[3];
-    const F w = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-    o[0] = x, o[1] = y, o[2] = z, o[3] = w;
-}
-
-// v rotated by the unit quaternion q: v + w t + u x t with t = 2 (u x v); exact for the identity
-__device__ __forceinline__ void qrot(const float* q, const float* v, float* o) {
-    const float tx = 2.f * (q[1] * v[2] - q[2] * v[1]), ty = 2.f * (q[2] * v[0] - q[0] * v[2]), tz = 2.f * (q[0] * v[1] - q[1] * v[0]);
-    o[0] = v[0] + q[3] * tx + (q[1] * tz - q[2] * ty);
-    o[1] = v[1] + q[3] * ty + (q[2] * tx - q[0] * tz);
-    o[2] = v[2] + q[3] * tz + (q[0] * ty - q[1] * tx);
-}
-
 __device__ __forceinline__ int kin_links(const KinSkel& sk) { return sk.n_links < 0 ? 0 : (sk.n_links > kn::MAX_LINKS ? kn::MAX_LINKS : sk.n_links); }
 
-// The link frames of one pose into this lane's LDS column F (F[(7 b + c) * COL]): base at (rx, ry, rz) with A2Q(rot[0:3]), a child's
-// frame = the parent's frame x the joint origin x A2Q(its axis-angle) (identity for a fixed joint).  rot is q + 3: the 54 rotation
-// columns.  A table entry outside its range reads as "root's child" / "fixed" and never as an address.
+// the shared FK body (tip_kin_fk.h) in fp32 on this table, unscaled
 __device__ __forceinline__ void fk_frames(const KinSkel& sk, int L, const float* __restrict__ rot, float rx, float ry, float rz, float* F) {
-    float q[4];
-    a2q<float>(rot[0], rot[1], rot[2], q);
-    F[0 * kn::COL] = rx, F[1 * kn::COL] = ry, F[2 * kn::COL] = rz;
-    for (int c = 0; c < 4; ++c) F[(3 + c) * kn::COL] = q[c];
-    for (int i = 0; i < L; ++i) {
-        const KinLink& lk = sk.link[i];
-        const int b = i + 1;
-        const int pa = (lk.parent < 0 || lk.parent >= b) ? 0 : lk.parent;
-        float pp[3], pq[4], o[3], qj[4];
-        for (int c = 0; c < 3; ++c) pp[c] = F[(7 * pa + c) * kn::COL];
-        for (int c = 0; c < 4; ++c) pq[c] = F[(7 * pa + 3 + c) * kn::COL];
-        qrot(pq, lk.jxyz, o);
-        qmul<float>(pq, lk.jq, qj);
-        const int col = lk.state_col;
-        if (col >= 3 && col <= kn::NQ - 3) {
-            float qa[4];
-            a2q<float>(rot[col - 3], rot[col - 2], rot[col - 1], qa);
-            qmul<float>(qj, qa, qj);
-        }
-        for (int c = 0; c < 3; ++c) F[(7 * b + c) * kn::COL] = pp[c] + o[c];
-        for (int c = 0; c < 4; ++c) F[(7 * b + 3 + c) * kn::COL] = qj[c];
-    }
+    fk_frames<float, false>(sk.link, L, rot, rx, ry, rz, 1.f, F);
 }
-
-// link frames -> COM poses, in place: position += R com (getLinkState fields 0-1; the inertial frames carry no rotation of their own)
-__device__ __forceinline__ void fk_to_com(const KinSkel& sk, int L, float* F) {
-    for (int i = 0; i < L; ++i) {
-        const int b = i + 1;
-        float q[4], o[3];
-        for (int c = 0; c < 4; ++c) q[c] = F[(7 * b + 3 + c) * kn::COL];
-        qrot(q, sk.link[i].com, o);
-        for (int c = 0; c < 3; ++c) F[(7 * b + c) * kn::COL] += o[c];
-    }
-}
+__device__ __forceinline__ void fk_to_com(const KinSkel& sk, int L, float* F) { fk_to_com<float, false>(sk.link, L, 1.f, F); }
 
 // rows [first, first + cnt) of out[n, L + 1, 7] from the LDS columns 0 .. cnt - 1, consecutive lanes on consecutive floats
 __device__ __forceinline__ void fk_store(const float* F, int per, long long first, int cnt, float* __restrict__ out, int lane) {

@@ -33,9 +33,21 @@ class Combined(NamedTuple):
     info: np.ndarray      # rows [start frame, end frame, down-sample rate] (int64)
 
 
+def _field(x, dev, name):
+    """One field of a file on the device as contiguous fp64: a numpy array is uploaded, a CUDA fp64 tensor on `dev` (what
+    tip_amd.syndata.synthesize returns) is used in place, without a host round trip."""
+    if isinstance(x, torch.Tensor):
+        target = dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+        if not x.is_cuda or x.dtype != torch.float64 or x.device != target:
+            raise ValueError(f"tip_amd.data.combine_motions: a tensor for {name!r} is CUDA fp64 on {target}; got {x.dtype} on {x.device}")
+        return x.contiguous()
+    return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float64)).to(dev)
+
+
 def combine_motions(files: Sequence[dict], down_sample_rates: Sequence[int], augmented_dip: Optional[Sequence[bool]] = None,
                     biases: Optional[np.ndarray] = None, device="cuda") -> Combined:
-    """files[i] = {"imu": [L,72], "nimble_qdq": [L,114], "constrs": [L,20]} (numpy fp64, as in the reference's pickles);
+    """files[i] = {"imu": [L,72], "nimble_qdq": [L,114], "constrs": [L,20]} (numpy fp64, as in the reference's pickles; each may
+    also be a CUDA fp64 tensor on `device`, used in place: tip_amd.syndata.synthesize's output);
     down_sample_rates[i] / augmented_dip[i] per file (the reference gives them per directory, :36-41).  `biases` [kept,18]
     overrides the accelerometer bias draw (default: np.random.uniform(-0.1, 0.1, 18) per kept file, as :85)."""
     L = _lib.load()
@@ -55,9 +67,7 @@ def combine_motions(files: Sequence[dict], down_sample_rates: Sequence[int], aug
             n = frames[i]
             if n == 0:
                 continue                                       # "too short" (:68-70)
-            imu = torch.as_tensor(np.ascontiguousarray(f["imu"], dtype=np.float64)).to(dev)
-            s = torch.as_tensor(np.ascontiguousarray(f["nimble_qdq"], dtype=np.float64)).to(dev)
-            c = torch.as_tensor(np.ascontiguousarray(f["constrs"], dtype=np.float64)).to(dev)
+            imu, s, c = (_field(f[k], dev, k) for k in ("imu", "nimble_qdq", "constrs"))
             if abs(len(imu) - len(s)) > 1:
                 raise AssertionError("qdq / imu length mismatch")   # :66
             b = biases[kept] if biases is not None else np.random.uniform(-BIAS_NOISE_ACC, BIAS_NOISE_ACC, 18)

@@ -32,6 +32,7 @@ import numpy as np
 DT = 1.0 / 60                       # constants.py:7
 MAX_LINKS = 32
 SBP_BODIES = ("lankle", "rankle", "lwrist", "rwrist", "root")      # get_cur_step_root_correction_from_all_constr (data_utils.py:502-508)
+IMU_BODIES = ("root", "lwrist", "rwrist", "lknee", "rknee", "upperneck")      # data-gen-and-viz-bullet-new.py:157-165 (the knee setting)
 METRICS = ("angle", "j_pos", "root_2s", "root_5s", "root_10s", "jerk", "root_jerk")      # offline_testing_simple.py:439-445
 _SKEL_DTYPE = np.dtype([("parent", "<i4"), ("state_col", "<i4"), ("joint_xyz", "<f4", 3), ("joint_q", "<f4", 4), ("com_xyz", "<f4", 3)])
 
@@ -54,9 +55,10 @@ class Skeleton:
     """The root and L links in URDF (= PyBullet) order; bodies are numbered 0 (the root) and i + 1 (link i).
     parent [L] (body index, always below the link's own), joint_xyz [L, 3] and joint_q [L, 4] (the joint origin in the parent's link
     frame), com_xyz [L, 3] (the inertial origin), state_col [L] (the column of the 57-wide q where the link's axis-angle starts, -1
-    for a fixed joint), sbp [5] (body indices of lankle, rankle, lwrist, rwrist, root), names [L + 1]."""
+    for a fixed joint), sbp [5] (body indices of lankle, rankle, lwrist, rwrist, root), names [L + 1]; imu [6] (body indices of root,
+    lwrist, rwrist, lknee, rknee, upperneck) or None: only tip_amd.syndata asks for it."""
 
-    def __init__(self, parent, joint_xyz, joint_q, com_xyz, state_col, sbp, names=None):
+    def __init__(self, parent, joint_xyz, joint_q, com_xyz, state_col, sbp, names=None, imu=None):
         who = "tip_amd.kinematics.Skeleton"
         self.parent = np.asarray(parent, dtype=np.int32).reshape(-1)
         L = self.n_links = int(self.parent.shape[0])
@@ -76,25 +78,32 @@ class Skeleton:
             raise ValueError(f"{who}: state_col is -1 (fixed) or a column 3 .. 54 of the 57-wide q; got {self.state_col.tolist()}")
         if len(self.names) != L + 1:
             raise ValueError(f"{who}: names is the root's and the {L} links'")
+        self.imu = None if imu is None else np.asarray(imu, dtype=np.int32).reshape(-1)
+        if self.imu is not None and (self.imu.shape[0] != 6 or (self.imu < 0).any() or (self.imu > L).any()):
+            raise ValueError(f"{who}: imu is six body indices in 0 .. {L} (root, lwrist, rwrist, lknee, rknee, upperneck); got "
+                             f"{self.imu.tolist()}")
         self._dev = {}
 
     @classmethod
     def from_table(cls, table):
-        """From a dict or an open .npz with the arrays parent, joint_xyz, joint_q, com_xyz, state_col, sbp and (optionally) names —
-        plain or under a "table/" prefix, as tests/golden/tip_kin_golden.npz keeps them."""
+        """From a dict or an open .npz with the arrays parent, joint_xyz, joint_q, com_xyz, state_col, sbp and (optionally) names and
+        imu — plain or under a "table/" prefix, as tests/golden/tip_kin_golden.npz keeps them (that one has no imu: it serves
+        everything here, and tip_amd.syndata says what is missing)."""
         keys = set(table.keys()) if hasattr(table, "keys") else set(table.files)
         pre = "table/" if "table/parent" in keys else ""
         need = ("parent", "joint_xyz", "joint_q", "com_xyz", "state_col", "sbp")
         missing = [k for k in need if pre + k not in keys]
         if missing:
             raise ValueError(f"tip_amd.kinematics.Skeleton.from_table: missing {missing}")
-        return cls(*[table[pre + k] for k in need], names=table[pre + "names"] if pre + "names" in keys else None)
+        return cls(*[table[pre + k] for k in need], names=table[pre + "names"] if pre + "names" in keys else None,
+                   imu=table[pre + "imu"] if pre + "imu" in keys else None)
 
     @classmethod
     def from_urdf(cls, path, char_info):
         """Parse a URDF of spherical and fixed joints.  char_info is the reference's character module (amass_char_info.py of the user's
         checkout): joint_idx names the links in PyBullet order, nimble_state_map gives the state columns by our_pose_2_bullet_format's
-        rule (data_utils.py:246-259: (nimble_state_map[idx] - 1) * 3 + 6), and lankle, rankle, lwrist, rwrist, root are the SBP bodies.
+        rule (data_utils.py:246-259: (nimble_state_map[idx] - 1) * 3 + 6), and lankle, rankle, lwrist, rwrist, root are the SBP bodies;
+        lknee, rknee and upperneck, where char_info names them, complete the IMU bodies.
         Refused: an inertial rpy that is not zero (the COM frame would be turned against the link's), a root inertial origin that is
         not zero, any other joint type, more than 32 links."""
         who = "tip_amd.kinematics.Skeleton.from_urdf"
@@ -133,7 +142,8 @@ class Skeleton:
             com.append(_floats(io, "xyz", f"link {child!r} inertial"))
             col.append(-1 if kind == "fixed" else (char_info.nimble_state_map[i] - 1) * 3 + 6)
         sbp = [getattr(char_info, n) + 1 for n in SBP_BODIES]
-        return cls(parent, jxyz, jq, com, col, sbp, names)
+        imu = [getattr(char_info, n) + 1 for n in IMU_BODIES] if all(hasattr(char_info, n) for n in IMU_BODIES) else None
+        return cls(parent, jxyz, jq, com, col, sbp, names, imu)
 
     def table(self) -> dict:
         return {"parent": self.parent, "joint_xyz": self.joint_xyz, "joint_q": self.joint_q, "com_xyz": self.com_xyz,
