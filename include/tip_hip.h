@@ -556,6 +556,56 @@ TIP_API int tip_kin_metrics(const void* skel, const float* pred_qdq, const float
                     const long long* offsets /* [count+1] */, int count, int start, int end, int i2, int i5, int i10,
                     double* out /* [count,7] */, tip_stream_t stream);
 
+/* ---- terrain: the full runner's tail — what RTRunner.step does behind the model (real_time_runner.py:451-496): the tracker above with
+ *      the per-stream height-region map (:140-262), the "establishing height" ticks (:264-277), the vertical root correction from the
+ *      map, and the two-joint leg IK (:334-382; data_utils.py:556-630) whose pose is fed back into the history.  A CONSUMER beside the
+ *      engines, as the tracker is (tip_amd.terrain): it reads s_rest / c_t, and the pose it corrects goes back through
+ *      tip_stream_history_override with fire_out as the slot list (entries < 0 are skipped there) — no engine kernel is involved.
+ *      `skel` is the kinematics table above.  The leg chains are read from it: ankle = the SBP body, knee and hip its parent and
+ *      grandparent, the hip's parent; the pose columns are those links' state columns (on the reference's character: ik_chain_map_bullet
+ *      and ik_chain_map_nimble_joint).  A chain that is not three spherical links never fires.
+ *      `state` is a caller-owned device buffer of tip_terrain_state_bytes() (8-byte aligned), one block per slot: what a tracker carry
+ *        holds; c_locs_prev[5][3], ik_target_deltas of the two ankles (fp64); the ticks of lankle, rankle, root; n_regions; the
+ *        counters off_map and regions_full; grid_num and max_regions as reset laid the block out; region_height[max_regions] and
+ *        region_weight[max_regions] (fp64); the map [grid_num, grid_num] of 4-byte cells: region index << 16 | the squared integer
+ *        distance to the centre of the update that wrote the cell (the reference's confidence is -sqrt of it; -100 is 10000, so
+ *        "confidence_old > confidence_new" is d2_old < d2_new, exactly).  Byte offsets within a block: 0 carry (1024: as
+ *        tip_kin_carry_bytes(1)), 1024 c_locs_prev, 1144 deltas, 1192 ticks, 1204 n_regions, 1208 off_map, 1212 regions_full, 1216
+ *        grid_num, 1220 max_regions, 1280 region_height, 1280 + 8 max_regions region_weight, 1280 + 16 max_regions the map.
+ *        grid_num (2 .. 4096) = int(map_bound / grid_size) * 2 and diffuse_region (1 .. 16) = round(0.5 / grid_size) are the
+ *        reference's expressions, evaluated by the host; max_regions 1 .. 65535.
+ *      tip_terrain_reset: for each j < count, block slots[j] (null: j) <- RTRunner.__init__: the carry as tip_kin_track_reset sets it,
+ *        c_locs_prev 100, ticks -1, deltas 0, region 0 of height 0 and weight 10, every cell region 0 at confidence -100.  The only
+ *        launch that touches a whole map.
+ *      tip_terrain_track: one kernel.  Sequence j < count uses block slots[j] (null: j) and rows begin[j] .. end[j] - 1, in order, and
+ *        leaves the block ready for the next chunk: any chunking gives the same bits.  flags bit 0 is
+ *        multi_sbp_terrain_and_correction.  Per valid row, in the reference's order: (1) root_pre = root + v DT (v as tip_kin_track
+ *        takes it), FK, c_locs and residues of the active SBPs against the previous frame's corrected poses, vel_res = clip(nanmean
+ *        of the two feet), vel_res[2] = 0, c_locs -= vel_res DT; (2) the ticks; (3) update_height_map_new on c_locs_prev for lankle,
+ *        then rankle, vel_res[2] += -20 d each; (4) with bit 0 and the pelvis more than 0.2 m (xy) from the mid-ankle point, the same
+ *        update for root; (5) with bit 0, correct_joint_q_for_history_feedback for lankle, then rankle; (6) root = root_pre - vel_res
+ *        DT, poses about the root, c_locs_prev = c_locs.  Outputs per row: root_out, viz_out (c_locs), q_hist_out = s_rest[:54] with the
+ *        columns the IK rewrote, fire_out = the SLOT INDEX where the IK rewrote the pose and -1 elsewhere.  A row that is not valid:
+ *        (the carry's root, 100s, s_rest[:54], -1), no state changed.
+ *        Decisions the reference leaves open.  OFF-MAP: a patch [c - d, c + d)^2 not wholly inside the map (the reference raises):
+ *        no map or region write, the update returns 0, the tick goes to -1, off_map counts it.  OVERFLOW: a new region is due and
+ *        max_regions are in use: the same, regions_full counts it.  TIES: an exact tie of |height difference| between two regions of a
+ *        patch goes to the lower region index.  TWO SBPS: with nc = 8 only the feet exist, and bit 0 is TIP_ERR_INVALID_ARG.
+ *        NON-FINITE: a non-finite c_loc is inactive (the reference's norm < 100); an index is formed only from an active location after
+ *        a range test in fp64; a non-finite row can spoil its own slot's root from there on, and nothing else.
+ *        FK is fp32 with the root at the origin; everything behind it is fp64 on the fp32 poses; outputs are rounded to fp32 once.
+ *        One wave per sequence; nothing waits on another workgroup; a block is written only by the wave whose sequence names it.
+ *      Null pointers, negative counts and sizes out of range return TIP_ERR_INVALID_ARG; a zero count returns TIP_OK without a launch. */
+TIP_API int tip_terrain_state_bytes(int n_slots, int grid_num, int max_regions, size_t* bytes);
+TIP_API int tip_terrain_reset(const void* skel, void* state, int n_slots, int grid_num, int max_regions,
+                      const int* slots /* [count] or null */, int count, const float* s_init /* [count,114] */, tip_stream_t stream);
+TIP_API int tip_terrain_track(const void* skel, void* state, int n_slots, int grid_num, int max_regions, int diffuse_region,
+                      double grid_size, const int* slots /* [count] or null */, const long long* begin, const long long* end,
+                      int count, long long n_rows, const float* s_rest /* [n_rows,111] */, const float* c_t /* [n_rows,nc] */, int nc,
+                      const unsigned char* valid /* [n_rows] or null */, int flags, float* root_out /* [n_rows,3] */,
+                      float* viz_out /* [n_rows,5,3] */, float* q_hist_out /* [n_rows,54] */, int* fire_out /* [n_rows] */,
+                      tip_stream_t stream);
+
 /* ---- synthetic data: IMU readings and stationary-body-point (SBP) labels from pose sequences — the reference's offline generator
  *      (data-gen-and-viz-bullet-new.py:44-218 over data_utils.py:27-100 get_rot_center_sample_based; bullet_agent.py for the scale),
  *      for `count` ragged sequences held back to back: sequence j is rows offsets[j] .. offsets[j + 1] - 1 of every array, offsets

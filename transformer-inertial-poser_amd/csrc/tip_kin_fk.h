@@ -122,4 +122,36 @@ __device__ __forceinline__ void fk_to_com(const KinLinkT<F>* __restrict__ link, 
     }
 }
 
+// ---- the fp32 table, carry and FK wrappers of tip_kin.hip and tip_terrain.hip ----------------------------------------------------
+// The skeleton table as the device reads it (tip_amd.kinematics.Skeleton.pack writes it; include/tip_hip.h has the layout).
+using KinLink = KinLinkT<float>;
+struct KinSkel {
+    int n_links;
+    int sbp[kn::SBPS];           // body indices of lankle, rankle, lwrist, rwrist, root
+    int pad[2];
+    KinLink link[kn::MAX_LINKS];
+};
+static_assert(sizeof(KinLink) == 48 && sizeof(KinSkel) == 32 + 48 * kn::MAX_LINKS, "KinSkel layout");
+
+// One sequence's carry between chunks: the corrected root; the corrected poses of the last valid frame with their positions taken
+// about that root (pq_prev of the runner = pq + root); and that frame's root-velocity columns, s_rest[54:57].  Those columns are
+// the runner's s_t[57:60] AFTER its pose averaging (:165-166 averages s_t[6:], the velocity included), while :159 integrates the
+// velocity BEFORE it, so the scan takes it back out: v_t = 2 a_t - a_(t-1) from the second valid frame on, v = a on the first.
+struct KinCarry {
+    double root[3];
+    float pq[kn::MAX_BODIES * 7];
+    float vprev[3];
+    int has_prev;
+    int pad[15];
+};
+static_assert(sizeof(KinCarry) == 1024, "KinCarry layout");
+
+__device__ __forceinline__ int kin_links(const KinSkel& sk) { return sk.n_links < 0 ? 0 : (sk.n_links > kn::MAX_LINKS ? kn::MAX_LINKS : sk.n_links); }
+
+// the shared FK body (tip_kin_fk.h) in fp32 on this table, unscaled
+__device__ __forceinline__ void fk_frames(const KinSkel& sk, int L, const float* __restrict__ rot, float rx, float ry, float rz, float* F) {
+    fk_frames<float, false>(sk.link, L, rot, rx, ry, rz, 1.f, F);
+}
+__device__ __forceinline__ void fk_to_com(const KinSkel& sk, int L, float* F) { fk_to_com<float, false>(sk.link, L, 1.f, F); }
+
 }  // namespace tip

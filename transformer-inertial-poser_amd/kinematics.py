@@ -19,8 +19,8 @@ A pose is xyz + (x, y, z, w).  FK is fp32; the tracker's scan and root accumulat
 metrics are fp64 sums.  One detail of the runner the tracker has to undo: :159 integrates the root velocity as predicted, while
 s_rest[54:57] is that velocity after the pose averaging of :165-166 — so v = 2 s_rest[54:57] - (the previous valid row's).
 
-RTRunner's terrain map and IK correction (real_time_runner.py:140-262, 334-382) stay with the host; fk(out_jf=True) hands a host IK
-the link frames it would otherwise compute itself."""
+RTRunner's terrain map, height correction and leg IK (real_time_runner.py:140-262, 334-382) are tip_amd.terrain, the same kind of
+consumer over the same FK; track_replay(..., terrain=dict(map_bound=..., grid_size=...)) routes a replay through it."""
 from __future__ import annotations
 
 import ctypes
@@ -313,10 +313,12 @@ def track(skel: Skeleton, s_init, s_rest, c_t, valid, offsets, device=None, chun
     return root, viz
 
 
-def track_replay(skel: Skeleton, results: Sequence, s_init, device=None) -> List[tuple]:
+def track_replay(skel: Skeleton, results: Sequence, s_init, device=None, terrain=None) -> List[tuple]:
     """ReplayPool.run's list -> per recording (qdq [L_i, 114], viz_locs [L_i, 5, 3]) as numpy float32: the script's s_traj_pred and
     viz_locs_seq before its trim (offline_testing_simple.py:123-139) — row 0 and the priming rows are s_init whole with markers at 100,
-    row t + 1 is the step on frame t.  replay.trim_like_reference serves both arrays."""
+    row t + 1 is the step on frame t.  replay.trim_like_reference serves both arrays.
+    terrain=None is RTRunnerMin's flat ground; terrain=dict(map_bound=..., grid_size=...[, max_regions=...]) is the full runner as the
+    script starts it (:169-176, multi_sbp_terrain_and_correction off), through tip_amd.terrain.track_terrain."""
     who = "track_replay"
     results = list(results)
     if not results:
@@ -336,8 +338,17 @@ def track_replay(skel: Skeleton, results: Sequence, s_init, device=None) -> List
         raise ValueError(f"tip_amd.kinematics.track_replay: the recordings' c_t widths differ ({sorted(widths)})")
     offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     s_rest = np.concatenate([np.asarray(r.s_rest, dtype=np.float32) for r in results])
-    root, viz = track(skel, s0, s_rest, np.concatenate([np.asarray(r.c_t, dtype=np.float32) for r in results]),
-                      np.concatenate([np.asarray(r.valid, dtype=bool) for r in results]), offs, device)
+    c_all = np.concatenate([np.asarray(r.c_t, dtype=np.float32) for r in results])
+    v_all = np.concatenate([np.asarray(r.valid, dtype=bool) for r in results])
+    if terrain is None:
+        root, viz = track(skel, s0, s_rest, c_all, v_all, offs, device)
+    else:
+        from .terrain import track_terrain
+        extra = set(terrain) - {"map_bound", "grid_size", "max_regions"}
+        if extra or not {"map_bound", "grid_size"} <= set(terrain):
+            raise ValueError(f"tip_amd.kinematics.track_replay: terrain is dict(map_bound=..., grid_size=...[, max_regions=...]); got "
+                             f"{sorted(terrain)}")
+        root, viz = track_terrain(skel, s0, s_rest, c_all, v_all, offs, multi_sbp=False, device=device, **terrain)[:2]
     root, viz = root.cpu().numpy(), viz.cpu().numpy()
     out = []
     for i, (a, b) in enumerate(zip(offs[:-1], offs[1:])):

@@ -49,6 +49,7 @@ EXPORTS = (
     "tip_sensor_state_bytes", "tip_sensor_reset", "tip_sensor_begin", "tip_sensor_accumulate", "tip_sensor_finish", "tip_sensor_set",
     "tip_sensor_get", "tip_sensor_transform",
     "tip_kin_skel_bytes", "tip_kin_carry_bytes", "tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_kin_metrics",
+    "tip_terrain_state_bytes", "tip_terrain_reset", "tip_terrain_track",
     "tip_syn_skel_bytes", "tip_syn_grid_bytes", "tip_syn_poses", "tip_syn_imu", "tip_syn_sbp",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
     "tip_train_bytes_f64", "tip_train_forward_f64", "tip_train_backward_f64",
@@ -198,6 +199,11 @@ def load() -> ctypes.CDLL:
     lib.tip_kin_track_reset.argtypes = [vp, vp, i32, vp, i32, vp, vp]
     lib.tip_kin_track.argtypes = [vp, vp, i32, vp, vp, vp, i32, ctypes.c_longlong, vp, vp, i32, vp, vp, vp, vp]
     lib.tip_kin_metrics.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]
+    # terrain (csrc/tip_terrain.hip): the table, the state and its shape, then as the tracker
+    lib.tip_terrain_state_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(sz)]
+    lib.tip_terrain_reset.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
+    lib.tip_terrain_track.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.c_double, vp, vp, vp, i32, ctypes.c_longlong, vp, vp, i32, vp, i32,
+                                      vp, vp, vp, vp, vp]
     # synthetic data (csrc/tip_syn.hip): device buffers, counts, then the stream
     lib.tip_syn_skel_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_syn_grid_bytes.argtypes = [ctypes.POINTER(sz)]

@@ -54,6 +54,8 @@ Model shapes (stream_shape below): the engines serve the four models the referen
 feature (x_imu 90 / 72 columns) times five or two stationary body points (size_s 131 / 119, c_t 20 / 8 columns) — and take the
 shape from the model.  override_history(q, slots): RTRunner with multi_sbp_terrain_and_correction feeds back a pose its host-side
 IK corrected, not the pose it returns (real_time_runner.py:483-495); the host hands that pose back between two frames.
+override_history_device(q_dev, slots_dev) is the same launch with the list on the device, entries < 0 skipped: tip_amd.terrain runs that
+IK on the device and hands its pose back without the host reading anything.
 
 step_packets(front, packets), both engines: the frame from RAW sensor packets [n, 42] instead of the calibrated frame — `front` is a
 tip_amd.sensors.SensorFrontEnd (the live demo's calibration and per-frame transform, live_demo_new.py:161-175, on the device), whose
@@ -315,6 +317,23 @@ class _StreamBase:
             q = self._to_dev(q.contiguous()).contiguous()
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
             self._call("history_override", self.state.data_ptr(), self.n, sl.data_ptr(), q.data_ptr(), len(idx))
+
+    def override_history_device(self, q_dev, slots_dev):
+        """override_history with the list on the device: q_dev [n, 54] float32 and slots_dev [n] int32, both CUDA tensors of this
+        engine's device.  Entry j rewrites slot slots_dev[j] from q_dev[j]; an entry below 0, and a slot that has not consumed a frame
+        yet, is skipped by the kernel, so the host never reads the list — what tip_amd.terrain.TerrainTracker.feed_back hands over
+        (its `fire`).  The same launch as override_history's, on the current stream, between two frames; nothing is re-captured."""
+        who = f"{type(self).__name__}.override_history_device"
+        for t, dt, tail, what in ((q_dev, torch.float32, (54,), "q_dev [n, 54] float32"), (slots_dev, torch.int32, (), "slots_dev [n] int32")):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == self.device and t.dtype == dt and t.is_contiguous()
+                    and tuple(t.shape[1:]) == tail and t.dim() == 1 + len(tail)):
+                raise ValueError(f"tip_amd.{who}: {what} is a contiguous CUDA tensor on {self.device}")
+        if q_dev.shape[0] != slots_dev.shape[0]:
+            raise ValueError(f"tip_amd.{who}: q_dev has {q_dev.shape[0]} rows for {slots_dev.shape[0]} list entries")
+        if slots_dev.shape[0] == 0:
+            return
+        with torch.cuda.device(self.device):
+            self._call("history_override", self.state.data_ptr(), self.n, slots_dev.data_ptr(), q_dev.data_ptr(), int(slots_dev.shape[0]))
 
     # ---- raw IMU packets (tip_amd.sensors) ------------------------------------------------------------------------------------------
     def _packets_to_raw(self, front, packets, slots, launch=True):
