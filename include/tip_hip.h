@@ -461,6 +461,33 @@ TIP_API int tip_replay_feed(const float* corpus, long long n_rows, const long lo
 TIP_API int tip_replay_collect(long long* cur, const long long* end, int n_slots, long long n_rows, const float* s_rest, const float* c_t,
                        const float* y_slot, const int* rows_slot, int size_s, float* s_out, float* c_out, float* y_out,
                        unsigned char* valid, tip_stream_t stream);
+/* The tracked frame (tip_amd.replay.ReplayPool(terrain=...)): the full runner's tail inside the pool's frame, so that the pose the leg
+ * IK corrects reaches the model's history before the next frame, as RTRunner.step feeds it back (real_time_runner.py:483-495).  On one
+ * stream, with nothing read by the host:
+ *     tip_replay_feed(...); tip_stream_ingest_mapped -> forward -> tip_stream_consume_mapped;                 (as above)
+ *     tip_replay_mask(cur, rows_slot, n, mask[n], stream);
+ *         mask[s] = rows_slot[s] >= 0 && cur[s] >= 0: slot s produced a row this frame and feeds a recording
+ *     tip_terrain_track(skel, blocks, n, ..., slots = null, begin = {0 .. n-1}, end = {1 .. n}, n, n, s_rest, c_t, nc, valid = mask, flags,
+ *                       t_root[n,3], t_viz[n,5,3], t_q_hist[n,54], t_fire[n], stream);                 (one block and one row per slot)
+ *     tip_stream_history_override[_w](state, n, t_fire, t_q_hist, n, stream);                          (entries < 0 are skipped)
+ *     tip_replay_collect_tracked(... tip_replay_collect's arguments up to valid ..., t_root, t_viz, t_q_hist, t_fire, blocks, block_stride,
+ *                                root_out[n_rows,3], viz_out[n_rows,5,3], q_hist_out[n_rows,54], fire_out[n_rows] (bytes),
+ *                                counters_out[n_rows,2] (int), stream);
+ *         for s_out / c_out / y_out / valid and the cursors: tip_replay_collect, bit for bit.  Beside it, for a slot that wrote row c + 1:
+ *         rows_slot[s] >= 0: root_out / viz_out / q_hist_out row c + 1 = t_root[s] / t_viz[s] / t_q_hist[s], fire_out = (t_fire[s] >= 0),
+ *         counters_out row = {off_map, regions_full} of block s (bytes 1208 and 1212 of blocks + s * block_stride: cumulative since the
+ *         block's reset).  rows_slot[s] < 0 (priming): root_out, q_hist_out and counters_out rows c + 1 = their rows c, viz_out = 100,
+ *         fire_out = 0 — so every row is what tip_terrain_track gives for it in a post-pass over the recording.  The HOST writes row 0 of
+ *         every recording before the run (root s_init[:3], q_hist s_init[3:57], viz 100, fire 0, counters 0) and resets the slot's block
+ *         (tip_terrain_reset) whenever the slot takes a recording.
+ * block_stride is tip_terrain_state_bytes(n, ...) / n (a multiple of 8, at least 1280); blocks 8-byte aligned.  Null pointers (y_slot /
+ * y_out as above), negative counts and size_s outside {119, 131} return TIP_ERR_INVALID_ARG; n_slots = 0 is TIP_OK without a launch. */
+TIP_API int tip_replay_mask(const long long* cur, const int* rows_slot, int n_slots, unsigned char* mask, tip_stream_t stream);
+TIP_API int tip_replay_collect_tracked(long long* cur, const long long* end, int n_slots, long long n_rows, const float* s_rest,
+                               const float* c_t, const float* y_slot, const int* rows_slot, int size_s, float* s_out, float* c_out,
+                               float* y_out, unsigned char* valid, const float* t_root, const float* t_viz, const float* t_q_hist,
+                               const int* t_fire, const void* t_state, long long block_stride, float* root_out, float* viz_out,
+                               float* q_hist_out, unsigned char* fire_out, int* counters_out, tip_stream_t stream);
 
 /* ---- sensor front end: raw IMU packets and the per-slot calibration, in front of the `raw_imu` every ingest above takes — the
  *      arithmetic the reference's live demo does on the host between its socket reader and RTRunner.step (live_demo_new.py:97-112

@@ -32,20 +32,21 @@ __global__ __launch_bounds__(256) void replay_feed_kernel(const float* __restric
     reinterpret_cast<float4*>(raw + (size_t)slot * 72)[lane] = v;
 }
 
-__global__ __launch_bounds__(256) void replay_collect_kernel(long long* __restrict__ cur, const long long* __restrict__ end, int n_slots,
-                                                             long long n_rows, const float* __restrict__ s_rest,
-                                                             const float* __restrict__ c_t, const float* __restrict__ y_slot,
-                                                             const int* __restrict__ rows_slot, int ns, float* __restrict__ s_out,
-                                                             float* __restrict__ c_out, float* __restrict__ y_out,
-                                                             unsigned char* __restrict__ valid) {
-    const int slot = blockIdx.x * kReplaySlotsPerBlock + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (slot >= n_slots) return;
+// One slot's collect, by the slot's own wave: what both collect kernels do for s_out / c_out / y_out / valid and the cursor.  Returns the
+// output row it wrote (cur + 1), or -1 when the slot wrote nothing (idle, or a cursor past the corpus); *produced says whether the slot's
+// engine row went there (rows_slot >= 0) or the start state did.
+__device__ __forceinline__ long long replay_collect_slot(int slot, int lane, long long* __restrict__ cur, const long long* __restrict__ end,
+                                                         long long n_rows, const float* __restrict__ s_rest,
+                                                         const float* __restrict__ c_t, const float* __restrict__ y_slot,
+                                                         const int* __restrict__ rows_slot, int ns, float* __restrict__ s_out,
+                                                         float* __restrict__ c_out, float* __restrict__ y_out,
+                                                         unsigned char* __restrict__ valid, bool* produced_out) {
     const long long c = cur[slot];
-    if (c < 0) return;                                      // idle
+    if (c < 0) return -1;                                   // idle
     const long long o = c + 1, e = end[slot];
     if (o >= n_rows) {                                      // (a table that points past the corpus: never written through)
         if (lane == 0) cur[slot] = -1;
-        return;
+        return -1;
     }
     const int nc = ns - 111;                                // 20 | 8 SBP columns
     const bool produced = rows_slot[slot] >= 0;             // the slot's T - 1 of this frame; < 0 while its smoother primes
@@ -67,6 +68,62 @@ __global__ __launch_bounds__(256) void replay_collect_kernel(long long* __restri
         valid[o] = produced ? 1 : 0;
         cur[slot] = (o >= e) ? -1 : o;                      // the frame at corpus row end - 1 was the last one fed
     }
+    *produced_out = produced;
+    return o;
+}
+
+__global__ __launch_bounds__(256) void replay_collect_kernel(long long* __restrict__ cur, const long long* __restrict__ end, int n_slots,
+                                                             long long n_rows, const float* __restrict__ s_rest,
+                                                             const float* __restrict__ c_t, const float* __restrict__ y_slot,
+                                                             const int* __restrict__ rows_slot, int ns, float* __restrict__ s_out,
+                                                             float* __restrict__ c_out, float* __restrict__ y_out,
+                                                             unsigned char* __restrict__ valid) {
+    const int slot = blockIdx.x * kReplaySlotsPerBlock + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (slot >= n_slots) return;
+    bool produced;
+    replay_collect_slot(slot, lane, cur, end, n_rows, s_rest, c_t, y_slot, rows_slot, ns, s_out, c_out, y_out, valid, &produced);
+}
+
+// ---- the tracked frame (ReplayPool(terrain=...)): feed -> engine -> mask -> tip_terrain_track -> tip_stream_history_override -> this ----
+//
+//   replay_mask_kernel             mask[slot] = the slot produced a row this frame AND feeds a recording: rows_slot >= 0 && cur >= 0 — the
+//                                  `valid` the terrain step takes, so that an idle slot's stale row never moves a map
+//   replay_collect_tracked_kernel  replay_collect_slot, and beside it output row cur + 1 of root / viz / q_hist / fire / counters: from the
+//                                  tracker's per-slot rows and the slot's block (off_map, regions_full at their documented byte offsets)
+//                                  when the slot produced a row; while it primes, the row before (root, q_hist, counters), markers at 100,
+//                                  fire 0 — what a terrain post-pass gives for a row that is not valid
+
+constexpr int kTerrainOffMapByte = 1208;                    // include/tip_hip.h, "terrain": off_map, then regions_full
+
+__global__ __launch_bounds__(256) void replay_mask_kernel(const long long* __restrict__ cur, const int* __restrict__ rows_slot, int n_slots,
+                                                          unsigned char* __restrict__ mask) {
+    const int slot = blockIdx.x * 256 + threadIdx.x;
+    if (slot < n_slots) mask[slot] = (rows_slot[slot] >= 0 && cur[slot] >= 0) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void replay_collect_tracked_kernel(
+    long long* __restrict__ cur, const long long* __restrict__ end, int n_slots, long long n_rows, const float* __restrict__ s_rest,
+    const float* __restrict__ c_t, const float* __restrict__ y_slot, const int* __restrict__ rows_slot, int ns, float* __restrict__ s_out,
+    float* __restrict__ c_out, float* __restrict__ y_out, unsigned char* __restrict__ valid, const float* __restrict__ t_root,
+    const float* __restrict__ t_viz, const float* __restrict__ t_q_hist, const int* __restrict__ t_fire,
+    const unsigned char* __restrict__ t_state, long long t_stride, float* __restrict__ root_out, float* __restrict__ viz_out,
+    float* __restrict__ q_hist_out, unsigned char* __restrict__ fire_out, int* __restrict__ counters_out) {
+    const int slot = blockIdx.x * kReplaySlotsPerBlock + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (slot >= n_slots) return;
+    bool produced = false;
+    const long long o = replay_collect_slot(slot, lane, cur, end, n_rows, s_rest, c_t, y_slot, rows_slot, ns, s_out, c_out, y_out, valid,
+                                            &produced);
+    if (o < 0) return;
+    const long long c = o - 1;
+    if (lane < 54) q_hist_out[(size_t)o * 54 + lane] = produced ? t_q_hist[(size_t)slot * 54 + lane] : q_hist_out[(size_t)c * 54 + lane];
+    if (lane < 15) viz_out[(size_t)o * 15 + lane] = produced ? t_viz[(size_t)slot * 15 + lane] : 100.f;
+    if (lane < 3) root_out[(size_t)o * 3 + lane] = produced ? t_root[(size_t)slot * 3 + lane] : root_out[(size_t)c * 3 + lane];
+    if (lane >= 32 && lane < 34) {
+        const int k = lane - 32;
+        const int* words = reinterpret_cast<const int*>(t_state + (size_t)slot * (size_t)t_stride + kTerrainOffMapByte);
+        counters_out[(size_t)o * 2 + k] = produced ? words[k] : counters_out[(size_t)c * 2 + k];
+    }
+    if (lane == 63) fire_out[o] = (produced && t_fire[slot] >= 0) ? 1 : 0;
 }
 
 hipError_t launch_replay_feed(const float* corpus, long long n_rows, const long long* cur, int n_slots, float* raw, hipStream_t s) {
@@ -81,6 +138,11 @@ hipError_t launch_replay_collect(long long* cur, const long long* end, int n_slo
     const int blocks = (n_slots + kReplaySlotsPerBlock - 1) / kReplaySlotsPerBlock;
     hipLaunchKernelGGL(replay_collect_kernel, dim3(blocks), dim3(256), 0, s, cur, end, n_slots, n_rows, s_rest, c_t, y_slot, rows_slot,
                        ns, s_out, c_out, y_out, valid);
+    return hipGetLastError();
+}
+
+hipError_t launch_replay_mask(const long long* cur, const int* rows_slot, int n_slots, unsigned char* mask, hipStream_t s) {
+    hipLaunchKernelGGL(replay_mask_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, s, cur, rows_slot, n_slots, mask);
     return hipGetLastError();
 }
 
@@ -112,6 +174,32 @@ int tip_replay_collect(long long* cur, const long long* end, int n_slots, long l
                                  static_cast<hipStream_t>(stream)) == hipSuccess
                ? TIP_OK
                : TIP_ERR_HIP;
+}
+
+int tip_replay_mask(const long long* cur, const int* rows_slot, int n_slots, unsigned char* mask, tip_stream_t stream) {
+    if (!cur || !rows_slot || !mask || n_slots < 0 || reinterpret_cast<uintptr_t>(cur) % 8) return TIP_ERR_INVALID_ARG;
+    if (n_slots == 0) return TIP_OK;
+    return launch_replay_mask(cur, rows_slot, n_slots, mask, static_cast<hipStream_t>(stream)) == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+}
+
+int tip_replay_collect_tracked(long long* cur, const long long* end, int n_slots, long long n_rows, const float* s_rest, const float* c_t,
+                               const float* y_slot, const int* rows_slot, int size_s, float* s_out, float* c_out, float* y_out,
+                               unsigned char* valid, const float* t_root, const float* t_viz, const float* t_q_hist, const int* t_fire,
+                               const void* t_state, long long t_stride, float* root_out, float* viz_out, float* q_hist_out,
+                               unsigned char* fire_out, int* counters_out, tip_stream_t stream) {
+    if (!cur || !end || !s_rest || !c_t || !rows_slot || !s_out || !c_out || !valid || n_rows < 0 || n_slots < 0 ||
+        (size_s != 119 && size_s != 131) || (y_out && !y_slot) || !aligned16(c_t) || !aligned16(c_out) ||
+        reinterpret_cast<uintptr_t>(cur) % 8 || reinterpret_cast<uintptr_t>(end) % 8)
+        return TIP_ERR_INVALID_ARG;
+    if (!t_root || !t_viz || !t_q_hist || !t_fire || !t_state || !root_out || !viz_out || !q_hist_out || !fire_out || !counters_out ||
+        t_stride < 1280 || t_stride % 8 || reinterpret_cast<uintptr_t>(t_state) % 8)
+        return TIP_ERR_INVALID_ARG;
+    if (n_slots == 0) return TIP_OK;
+    const int blocks = (n_slots + kReplaySlotsPerBlock - 1) / kReplaySlotsPerBlock;
+    hipLaunchKernelGGL(replay_collect_tracked_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), cur, end, n_slots,
+                       n_rows, s_rest, c_t, y_slot, rows_slot, size_s, s_out, c_out, y_out, valid, t_root, t_viz, t_q_hist, t_fire,
+                       static_cast<const unsigned char*>(t_state), t_stride, root_out, viz_out, q_hist_out, fire_out, counters_out);
+    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 
 }  // extern "C"

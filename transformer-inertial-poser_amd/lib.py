@@ -45,7 +45,7 @@ EXPORTS = (
     "tip_stream_state_bytes_w", "tip_stream_window_len_w", "tip_stream_reset_w", "tip_stream_ingest_w", "tip_stream_consume_w",
     "tip_stream_attach_w", "tip_stream_detach_w", "tip_stream_ingest_staggered_w", "tip_stream_consume_staggered_w",
     "tip_stream_ingest_mapped_w", "tip_stream_consume_mapped_w", "tip_stream_history_override_w",
-    "tip_replay_feed", "tip_replay_collect",
+    "tip_replay_feed", "tip_replay_collect", "tip_replay_mask", "tip_replay_collect_tracked",
     "tip_sensor_state_bytes", "tip_sensor_reset", "tip_sensor_begin", "tip_sensor_accumulate", "tip_sensor_finish", "tip_sensor_set",
     "tip_sensor_get", "tip_sensor_transform",
     "tip_kin_skel_bytes", "tip_kin_carry_bytes", "tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_kin_metrics",
@@ -183,6 +183,9 @@ def load() -> ctypes.CDLL:
         getattr(lib, "tip_stream_" + name.replace("_shaped", "") + "_w").argtypes = at[:-1] + [i32, vp]
     lib.tip_replay_feed.argtypes = [vp, ctypes.c_longlong, vp, i32, vp, vp]
     lib.tip_replay_collect.argtypes = [vp, vp, i32, ctypes.c_longlong, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.tip_replay_mask.argtypes = [vp, vp, i32, vp, vp]
+    # (tip_replay_collect's arguments up to valid; the tracker's four per-slot rows, its blocks and their stride; the five outputs)
+    lib.tip_replay_collect_tracked.argtypes = lib.tip_replay_collect.argtypes[:-1] + [vp] * 5 + [ctypes.c_longlong] + [vp] * 5 + [vp]
     # sensor front end (csrc/tip_sensor.hip): cal, then what the header lists, then the stream
     lib.tip_sensor_state_bytes.argtypes = [i32, ctypes.POINTER(sz)]
     lib.tip_sensor_reset.argtypes = [vp, i32, vp]

@@ -32,13 +32,28 @@ bucket's first use in a run, synchronises once as it does for every compact pool
 attach / detach on exactly the frames the plan names, and on those frames the cursor table is uploaded (one small non-blocking copy
 from pinned memory, between two replays, in front of the engine's own staged attach copy).
 
+The full runner (terrain=): ReplayPool(model, slots, ..., terrain=dict(skel=..., map_bound=5.0, grid_size=0.1, multi_sbp=True,
+max_regions=64)) runs RTRunner.step's tail — terrain map, height correction, leg IK (tip_amd.terrain) — INSIDE the frame, one
+TerrainTracker block per slot (pool.tracker), so that the pose the IK corrects reaches the model's history before the next frame as the
+reference feeds it back (real_time_runner.py:483-495; live_demo_new.py ships multi_sbp_terrain_and_correction on).  A tracked frame is
+feed -> the engine's mapped frame -> tip_replay_mask (valid = the slot produced a row and feeds a recording) -> tip_terrain_track over
+the pool's slots -> tip_stream_history_override with the tracker's `fire` as the device slot list -> tip_replay_collect_tracked, all of
+it inside the captured ("fed", B) frame: three launches more than the plain frame, nothing read by the host.  run() then returns
+TrackedReplayResult per recording: the four arrays above and root [L, 3], viz_locs [L, 5, 3], q_hist [L, 54], fire [L] — row for row
+what terrain.track_terrain gives in a post-pass (row 0 and the priming rows: s_init's root and pose, markers at 100, fire False) — and
+the recording's off_map / regions_full totals; .qdq is root | s_rest, which trim_like_reference and kinematics.evaluate take.  The
+tracker's blocks of the slots a frame attaches are reset from the recordings' s_init in front of that frame (pinned, non-blocking);
+no synchronisation is added.  With multi_sbp=False nothing is fed back and the result is the plain pool's plus the post-pass, bit for
+bit; RTRunnerMin needs no tracker in the pool (kinematics.track_replay is exact for it).  terrain=None changes nothing.
+
 Model shapes, .train() / .eval() rules and every refusal are the engine's own; the shipped loaders (past_state_dropout = 0.8,
 never .eval()) are served with live_dropout=True.
 
 Lost hand-off: the engine re-primes every attached slot and raises TipHandoffError; run() catches it once, restarts the recordings
 that were in flight from their frame 0 (their rows are overwritten), counts them in `restarts` and goes on.  The handle has demoted
 itself by then, so a second loss is raised to the caller.  A recording that finished before the loss was noticed keeps its rows: a
-row computed by the lost launch is NaN, never a finite wrong number — with valid True (ReplayResult: valid is not "finite")."""
+row computed by the lost launch is NaN, never a finite wrong number — with valid True (ReplayResult: valid is not "finite").  With a
+tracker the restarted recordings' blocks are reset as well and their rows, the tracker's included, are overwritten."""
 from __future__ import annotations
 
 import collections
@@ -63,6 +78,32 @@ class ReplayResult(NamedTuple):
     c_t: np.ndarray                 # [L, 20 | 8] float32
     valid: np.ndarray               # [L] bool
     y_last: Optional[np.ndarray]    # [L, 131 | 119] float32 (keep_y=True), else None
+
+
+class TrackedReplayResult(NamedTuple):
+    """One recording's rows from ReplayPool(terrain=...): ReplayResult's four and the full runner's tail, row for row what
+    tip_amd.terrain.track_terrain gives for the recording in a post-pass — row 0 and the priming rows hold s_init's root and pose,
+    markers at 100 and fire False.  q_hist is the pose the runner feeds back (s_rest[:, :54] with the columns the leg IK rewrote on
+    rows where fire is True); with multi_sbp it HAS gone into the model's history, so s_rest behind a fired row is not the plain
+    pool's.  off_map and regions_full are the recording's totals (map updates dropped off the map, or for want of a free region)."""
+    s_rest: np.ndarray              # [L, 111] float32
+    c_t: np.ndarray                 # [L, 20 | 8] float32
+    valid: np.ndarray               # [L] bool
+    y_last: Optional[np.ndarray]    # [L, 131 | 119] float32 (keep_y=True), else None
+    root: np.ndarray                # [L, 3] float32: RTRunner.step's qdq[:3]
+    viz_locs: np.ndarray            # [L, 5, 3] float32
+    q_hist: np.ndarray              # [L, 54] float32
+    fire: np.ndarray                # [L] bool
+    off_map: int
+    regions_full: int
+
+    @property
+    def qdq(self) -> np.ndarray:
+        """[L, 114]: root | s_rest — the script's s_traj_pred rows before its trim, as kinematics.track_replay returns them."""
+        return np.concatenate([self.root, self.s_rest], axis=1)
+
+
+TERRAIN_KEYS = ("skel", "map_bound", "grid_size", "multi_sbp", "max_regions")
 
 
 class ReplayPlan(NamedTuple):
@@ -177,13 +218,17 @@ def check_inputs(recordings, s_init):
     return recs, s
 
 
-def replay_on_host(recordings, s_init, slots: int, make_stream, n_c: int = 20, n_y: int = 131):
+def replay_on_host(recordings, s_init, slots: int, make_stream, n_c: int = 20, n_y: int = 131, make_tracker=None):
     """ReplayPool.run's bookkeeping — the plan, the cursor tables, what the feed and collect kernels do with them — in plain numpy, with
     the device's per-slot closed loop replaced by make_stream(s_init_row) -> an object whose step(raw[72]) returns None while it primes
     and (s_rest[111], c_t[n_c], y_last[n_y]) afterwards (oracle.streaming_oracle.StreamOracle with a model bound in is one).  A
     SPECIFICATION, not the code path: ReplayPool.run shares plan_replay and check_inputs with it and nothing else — the cursor tables,
     feed and collect it restates run on the device there (csrc/tip_replay.hip), and only the GPU tests check those.  It exists so that
-    the row conventions can be held against the script's loop without a device; returns (results, frames)."""
+    the row conventions can be held against the script's loop without a device; returns (results, frames).
+    make_tracker (ReplayPool(terrain=...)'s frame): make_tracker(s_init_row) -> an object whose step(s_rest[111], c_t[n_c]) returns
+    (root[3], viz_locs[5, 3], q_hist[54], fired, off_map, regions_full) — one per slot, made anew whenever the slot takes a recording.
+    It is stepped on every row a stream produced; where it fired, stream.override(q_hist) puts the pose into the stream's newest
+    history row before the next frame; the results are TrackedReplayResult."""
     recs, s0 = check_inputs(recordings, s_init)
     lengths = [r.shape[0] for r in recs]
     offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
@@ -192,30 +237,50 @@ def replay_on_host(recordings, s_init, slots: int, make_stream, n_c: int = 20, n
     s_out, c_out = np.zeros((n_rows, 111), np.float32), np.zeros((n_rows, n_c), np.float32)
     y_out, valid = np.full((n_rows, n_y), np.nan, np.float32), np.zeros(n_rows, bool)
     s_out[offs[:-1]] = s0[:, 3:]
+    tracked = make_tracker is not None
+    if tracked:
+        root_out, viz_out = np.zeros((n_rows, 3), np.float32), np.full((n_rows, 5, 3), 100.0, np.float32)
+        q_out, fire_out, cnt_out = np.zeros((n_rows, 54), np.float32), np.zeros(n_rows, bool), np.zeros((n_rows, 2), np.int32)
+        root_out[offs[:-1]], q_out[offs[:-1]] = s0[:, :3], s0[:, 3:57]
     plan = plan_replay(lengths, slots)
     cur, end = np.full(slots, -1, np.int64), np.full(slots, -1, np.int64)
-    stream = [None] * slots
+    stream, tracker = [None] * slots, [None] * slots
     for att, det in plan.frames:
         for s in det:
             stream[s] = None
         for s, i in att:
             stream[s] = make_stream(s0[i])
+            tracker[s] = make_tracker(s0[i]) if tracked else None
             cur[s], end[s] = offs[i], offs[i] + lengths[i] - 1
         raw = np.zeros((slots, 72), np.float32)                      # feed
         live = cur >= 0
         raw[live] = corpus[cur[live]]
         res = [stream[s].step(raw[s]) if stream[s] is not None else None for s in range(slots)]      # the engine's frame
+        trk = [None] * slots
+        if tracked:                                                  # the terrain step and the override, for the slots that are valid
+            for s in range(slots):
+                if res[s] is not None and cur[s] >= 0:
+                    trk[s] = tracker[s].step(res[s][0], res[s][1])
+                    if trk[s][3]:
+                        stream[s].override(np.asarray(trk[s][2]))
         for s in range(slots):                                       # collect
             c = cur[s]
             if c < 0:
                 continue
             if res[s] is None:
                 s_out[c + 1], c_out[c + 1], y_out[c + 1], valid[c + 1] = s_out[c], 0.0, np.nan, False
+                if tracked:
+                    root_out[c + 1], viz_out[c + 1], q_out[c + 1], fire_out[c + 1], cnt_out[c + 1] = root_out[c], 100.0, q_out[c], False, cnt_out[c]
             else:
                 s_out[c + 1], c_out[c + 1], y_out[c + 1] = res[s]
                 valid[c + 1] = True
+                if tracked:
+                    root_out[c + 1], viz_out[c + 1], q_out[c + 1], fire_out[c + 1] = trk[s][:4]
+                    cnt_out[c + 1] = trk[s][4:6]
             cur[s] = -1 if c + 1 >= end[s] else c + 1
     assert (cur < 0).all()
+    if tracked:
+        return _split_tracked(offs, s_out, c_out, valid, y_out, root_out, viz_out, q_out, fire_out, cnt_out), plan.n_frames
     return _split(offs, s_out, c_out, valid, y_out), plan.n_frames
 
 
@@ -224,18 +289,42 @@ def _split(offs, s_out, c_out, valid, y_out) -> List[ReplayResult]:
             for a, b in zip(offs[:-1], offs[1:])]
 
 
+def _split_tracked(offs, s_out, c_out, valid, y_out, root, viz, q_hist, fire, counters) -> List[TrackedReplayResult]:
+    return [TrackedReplayResult(s_out[a:b], c_out[a:b], valid[a:b], None if y_out is None else y_out[a:b], root[a:b], viz[a:b],
+                                q_hist[a:b], fire[a:b].astype(bool), int(counters[b - 1, 0]), int(counters[b - 1, 1]))
+            for a, b in zip(offs[:-1], offs[1:])]
+
+
 class ReplayPool:
     """See the module's docstring.  One StaggeredStreamingEngine(compact=True) with `slots` slots, owned by the pool (`engine`) and
     reused by every run(); window, live_dropout and use_graph are the engine's.  keep_y=True also returns the model's raw last rows.
+    terrain=dict(skel=..., map_bound=..., grid_size=..., multi_sbp=..., max_regions=64) puts the full runner's tail into the frame
+    (`tracker`: a TerrainTracker of `slots` blocks) and makes run() return TrackedReplayResult; unknown keys, a missing skel,
+    multi_sbp with a two-SBP model or with leg chains the IK cannot serve are ValueErrors before anything is built.
     After a run: frames, restarts, and plan (the run's ReplayPlan: which slot and engine frame each recording started on)."""
 
-    def __init__(self, model, slots: int = 64, window: int = 40, live_dropout: bool = False, use_graph: bool = True, keep_y: bool = False):
+    def __init__(self, model, slots: int = 64, window: int = 40, live_dropout: bool = False, use_graph: bool = True, keep_y: bool = False,
+                 terrain=None):
         import torch
         from . import lib as _lib
-        from .streaming import StaggeredStreamingEngine
+        from .streaming import StaggeredStreamingEngine, stream_shape
         slots = int(slots)
         if slots < 1:
             raise ValueError(f"tip_amd.replay.ReplayPool: slots must be at least 1; got {slots}")
+        if terrain is not None:          # every refusal before anything is allocated or launched
+            from .terrain import _leg_chains_ok
+            terrain = dict(terrain)
+            extra = set(terrain) - set(TERRAIN_KEYS)
+            if extra or terrain.get("skel") is None:
+                raise ValueError("tip_amd.replay.ReplayPool: terrain is dict(skel=..., map_bound=..., grid_size=..., multi_sbp=..., "
+                                 f"max_regions=...) with a skeleton; got {sorted(terrain)}")
+            if terrain.get("multi_sbp"):
+                if stream_shape(model)[0] != 5:
+                    raise ValueError("tip_amd.replay.ReplayPool: terrain multi_sbp corrects by the root's SBP, which a two-SBP model "
+                                     "does not have (tip_amd.terrain's rule)")
+                if not _leg_chains_ok(terrain["skel"]):
+                    raise ValueError("tip_amd.replay.ReplayPool: terrain multi_sbp needs both ankles below three spherical links "
+                                     "(hip, knee, ankle)")
         self.slots, self.keep_y = slots, bool(keep_y)
         self.engine = StaggeredStreamingEngine(model, np.zeros((slots, 114), dtype=np.float32), use_graph=use_graph, compact=True,
                                                live_dropout=live_dropout, window=window)
@@ -247,9 +336,18 @@ class ReplayPool:
         self._tbl = torch.full((2, slots), -1, dtype=torch.int64, device=self.engine.device)
         self._bufs = None           # the current run's corpus and outputs (what the engine's captured frames point at)
         self.frames = self.restarts = 0
+        # terrain: the full runner's tail inside the frame — one TerrainTracker block per slot, stepped, fed back and collected by the
+        # collect callable (_install), all of it inside the captured ("fed", B) frame
+        self.tracker = None
+        if terrain is not None:
+            from .terrain import TerrainTracker
+            skel = terrain.pop("skel")
+            self.tracker = TerrainTracker(skel, slots, self.engine.device, **terrain)
+            self._mask = torch.zeros(slots, dtype=torch.uint8, device=self.engine.device)
 
     # ---- the two launches around the engine's frame ----------------------------------------------------------------------------------
-    def _install(self, corpus, s_out, c_out, y_out, valid):
+    def _install(self, corpus, s_out, c_out, y_out, valid, tracked=()):
+        """tracked: a pool with a tracker passes its corpus-shaped (root_out, viz_out, q_hist_out, fire_out, counters_out)."""
         eng, lib, n, n_rows = self.engine, self.lib, self.slots, int(corpus.shape[0])
         cur, end = self._tbl[0].data_ptr(), self._tbl[1].data_ptr()
         p_corpus, p_raw = corpus.data_ptr(), eng.raw.data_ptr()
@@ -262,8 +360,29 @@ class ReplayPool:
         def collect():
             eng._check(lib.tip_replay_collect(cur, end, n, n_rows, *p_eng, eng.ns, *p_out, eng._stream()))
 
-        self._bufs = (corpus, s_out, c_out, y_out, valid)
-        eng.set_feeder(feed, collect)
+        if tracked:
+            # the terrain step over the pool's slots (valid: the mask launch), the history override for the slots that fired (the
+            # tracker's `fire` as the device slot list) and the tracked collect: three launches more, nothing read by the host
+            tt = self.tracker
+            p_trk = (tt.root.data_ptr(), tt.viz_locs.data_ptr(), tt.q_hist.data_ptr(), tt.fire.data_ptr(), tt._s.buf.data_ptr(), tt._s.stride)
+            p_new = tuple(t.data_ptr() for t in tracked)
+            frame = {"s_rest": eng.s_rest, "c_t": eng.c_t, "valid": self._mask}
+
+            def collect_tracked():
+                eng._check(lib.tip_replay_mask(cur, p_eng[3], n, self._mask.data_ptr(), eng._stream()))
+                tt.step(frame)
+                tt.feed_back(eng)
+                eng._check(lib.tip_replay_collect_tracked(cur, end, n, n_rows, *p_eng, eng.ns, *p_out, *p_trk, *p_new, eng._stream()))
+
+        self._bufs = (corpus, s_out, c_out, y_out, valid) + tuple(tracked)
+        eng.set_feeder(feed, collect_tracked if tracked else collect)
+
+    def _reset_tracker(self, pairs, s0):
+        """The tracker's blocks of the slots in `pairs` [(slot, recording), ...] start over from the recordings' s_init (pinned,
+        non-blocking: TerrainTracker.reset), in stream order before the next frame."""
+        if self.tracker is not None and pairs:
+            pairs = sorted(pairs)
+            self.tracker.reset([s for s, _ in pairs], s0[[i for _, i in pairs]])
 
     def _upload_table(self, in_flight, f, offs, lengths):
         """The cursor table as it stands before engine frame f — in_flight: {slot: (recording, the frame that fed its frame 0)} — in one
@@ -273,7 +392,7 @@ class ReplayPool:
             t[0, s], t[1, s] = offs[i] + (f - f0), offs[i] + lengths[i] - 1
         self._tbl.copy_(self._torch.from_numpy(t).pin_memory(), non_blocking=True)
 
-    def run(self, recordings, s_init) -> List[ReplayResult]:
+    def run(self, recordings, s_init) -> list:
         torch = self._torch
         recs, s0 = check_inputs(recordings, s_init)
         eng, n, dev = self.engine, self.slots, self.engine.device
@@ -294,7 +413,19 @@ class ReplayPool:
             # row 0 of every recording: its start state (what the priming rows repeat)
             start_rows = torch.from_numpy(offs[:-1].copy()).pin_memory().to(dev, non_blocking=True)
             s_out.index_copy_(0, start_rows, torch.from_numpy(s0[:, 3:].copy()).pin_memory().to(dev, non_blocking=True))
-            self._install(corpus, s_out, c_out, y_out, valid)
+            tracked = ()
+            if self.tracker is not None:
+                # the tracker's corpus-shaped rows; row 0 of every recording is the host's: s_init's root and pose, markers at 100
+                root_out = torch.zeros((n_rows, 3), dtype=torch.float32, device=dev)
+                viz_out = torch.full((n_rows, 5, 3), 100.0, dtype=torch.float32, device=dev)
+                q_out = torch.zeros((n_rows, 54), dtype=torch.float32, device=dev)
+                fire_out = torch.zeros(n_rows, dtype=torch.uint8, device=dev)
+                cnt_out = torch.zeros((n_rows, 2), dtype=torch.int32, device=dev)
+                head = torch.from_numpy(s0[:, :57].copy()).pin_memory().to(dev, non_blocking=True)
+                root_out.index_copy_(0, start_rows, head[:, :3].contiguous())
+                q_out.index_copy_(0, start_rows, head[:, 3:].contiguous())
+                tracked = (root_out, viz_out, q_out, fire_out, cnt_out)
+            self._install(corpus, s_out, c_out, y_out, valid, tracked)
 
             plan = plan_replay(lengths, n)
             self.plan = plan
@@ -315,6 +446,7 @@ class ReplayPool:
                 in_flight = {s: v for s, v in in_flight.items() if f - v[1] < lengths[v[0]] - 1}
                 if att:
                     self._upload_table(in_flight, f, offs, lengths)
+                    self._reset_tracker(att, s0)
                 try:
                     eng._step_fed()
                 except self._handoff_error:
@@ -327,10 +459,15 @@ class ReplayPool:
                     plan = _plan(lengths, n, [i for i in range(len(recs)) if i not in done_attach], occupied)
                     in_flight, f = {s: (i, 0) for s, i in occupied.items()}, 0
                     self._upload_table(in_flight, 0, offs, lengths)
+                    self._reset_tracker(list(occupied.items()), s0)
                     continue
                 f += 1
             eng.detach(plan.final_detach)
             torch.cuda.current_stream(dev).synchronize()          # the one synchronisation
             self.frames = eng.fed_frames - fed0
             y_host = None if y_out is None else y_out.cpu().numpy()
+            if self.tracker is not None:
+                return _split_tracked(offs, s_out.cpu().numpy(), c_out.cpu().numpy(), valid.cpu().numpy().astype(bool), y_host,
+                                      root_out.cpu().numpy(), viz_out.cpu().numpy(), q_out.cpu().numpy(), fire_out.cpu().numpy(),
+                                      cnt_out.cpu().numpy())
             return _split(offs, s_out.cpu().numpy(), c_out.cpu().numpy(), valid.cpu().numpy().astype(bool), y_host)

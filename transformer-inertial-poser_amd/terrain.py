@@ -21,7 +21,9 @@ frame and -1 elsewhere, and tip_stream_history_override skips entries below 0, s
 grid_num and diffuse_region are the reference's own expressions (:115, :128), evaluated here and passed as integers.  The decisions the
 reference leaves open (a patch off the map, more regions than max_regions, ties, two-SBP models, non-finite rows) are listed in the
 header.  Precision as the tracker's: FK fp32, everything behind it fp64, outputs fp32.  PyBullet and fairmotion parity are unpinned, as
-everywhere (tests/golden/make_terrain_golden.py).  Out of scope: IK feedback through ReplayPool, play_back_gt, and the arm IK the
+everywhere (tests/golden/make_terrain_golden.py).  IK feedback for recorded files runs inside the replay pool's frame:
+tip_amd.replay.ReplayPool(terrain=dict(skel=..., multi_sbp=True, ...)).  play_back_gt (real_time_runner.py:396-401) takes s_t and c_t from
+the ground truth instead of the model and runs the same tail: it is track_terrain on ground-truth rows.  Out of scope: the arm IK the
 reference never calls."""
 from __future__ import annotations
 
