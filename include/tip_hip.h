@@ -536,6 +536,52 @@ TIP_API int tip_sensor_get(const void* cal, int n_slots, const int* slots, int c
 TIP_API int tip_sensor_transform(const void* cal, const float* packets /* [n,42] */, int n_slots, float max_acc,
                          float* raw_out /* [n,72] */, tip_stream_t stream);
 
+/* ---- missing IMU readings: the reference's answer to sensors that deliver nothing for a frame (preprocess_DIP_TC_new.py:112-136
+ *      fill_in_nan_values, :160-180 get_real_imu_readings_ours_format_knee), for recorded files, for the live front end above and for
+ *      recorded sessions.  A sensor's 9 rotation values and its 3 acceleration values are two independent PARTS of a row; a part is
+ *      BAD when the sum of its values is NaN (one NaN element, or Inf - Inf), and a bad part is replaced as a whole.
+ *      Rule R ("reference"), on a sequence known in full: the mask comes from the data as it came; walking t upwards, a bad part
+ *        at t becomes, per value, (the sum in ascending row order of the values of that column that are not NaN) / (their number)
+ *        over rows 0 .. min(10, L)-1 when t <= 10 and over rows t-5 .. t-1 otherwise — of the values as they are by then, earlier
+ *        fills included; no such value gives NaN.
+ *      Rule V ("live"), for a stream, which cannot look ahead: per part a ring of the last five rows AFTER filling, `have` of them
+ *        valid, `run` consecutive fills and `total` fills.  A bad part with have >= 1 (and run < max_gap, when max_gap >= 0) becomes
+ *        (the ring's rows summed oldest to newest, fp32) / have, is pushed, and run and total go up.  A bad part with have = 0, or
+ *        past max_gap, becomes NaN in all its values and is not pushed.  A good part is pushed and sets run to 0.  max_gap = -1: no
+ *        limit, as the reference has none.  V equals R on every row t > 10 when rows 0 .. 10 are good.
+ *      tip_fill_real: rule R in fp64 on n_seq ragged sequences of one launch.  ori[n_rows, n_sensors, 9] and acc[n_rows, n_sensors, 3]
+ *        (device), sequence r being rows offsets[r] .. offsets[r+1]-1 (device, clamped to [0, n_rows]); sel[6] and rot[9] are HOST
+ *        arrays: the six sensors taken, in output order (each in [0, n_sensors)), and the row-major rotation.  out[n_rows, 72]
+ *        (device): columns 9k .. 9k+8 = rot * (filled rotation of sensor sel[k]), 54+3k .. 54+3k+2 = rot * (filled acceleration),
+ *        every value (r0 h0 + r1 h1) + r2 h2.  unfilled[n_seq] (device int): the parts of the sequence that are still bad.  Rows
+ *        that no sequence owns are not written.
+ *      tip_fill_rows: rule V on n_seq ragged sequences of frames[n_rows, 72] fp32 into out (which may be frames itself), each
+ *        sequence starting from empty rings.  flags[n_rows, 12] bytes, part k < 6 the rotation of sensor k, part 6+k its
+ *        acceleration: 0 good, 1 filled, 2 bad and left NaN.
+ *      tip_fill_state_bytes / tip_fill_reset: the rings of n slots are a caller-owned device buffer (4-byte aligned).  A reset empties
+ *        the rings and zeroes the counters of the listed slots, or of all n when slots is null (required once).
+ *      tip_fill_live: rule V for one frame, in place on raw[n, 72] — what tip_sensor_transform has just written — and flags[n, 12].
+ *        `cal` is the front end's buffer: a slot whose phase is not 4 is skipped, its NaN row stays, its rings are not touched and its
+ *        flags are 0.  No argument changes from frame to frame.
+ *      tip_fill_get: counts_out[count, 3, 12] (device int) = have | run | total of the listed slots.
+ *      tip_fill_packets: tip_sensor_transform's arithmetic (the same device function, bit for bit) on packets[n_rows, 42] of recorded
+ *        sessions, the rows of sequence r with tables[r, 126]; out[n_rows, 72].
+ *      Null buffers, negative counts, max_gap < -1, a sel outside the sensors: TIP_ERR_INVALID_ARG; a count of 0 launches nothing. */
+TIP_API int tip_fill_real(const double* ori, const double* acc, long long n_rows, int n_sensors, const long long* offsets /* [n_seq+1] */,
+                  int n_seq, const int* sel /* host [6] */, const double* rot /* host [9] */, double* out /* [n_rows,72] */,
+                  int* unfilled /* [n_seq] */, tip_stream_t stream);
+TIP_API int tip_fill_rows(const float* frames /* [n_rows,72] */, float* out, long long n_rows, const long long* offsets /* [n_seq+1] */,
+                  int n_seq, int max_gap, unsigned char* flags /* [n_rows,12] */, tip_stream_t stream);
+TIP_API int tip_fill_state_bytes(int n_slots, size_t* bytes);
+TIP_API int tip_fill_reset(void* state, int n_slots, const int* slots /* or null: all */, int count, tip_stream_t stream);
+TIP_API int tip_fill_live(void* state, const void* cal, float* raw /* [n,72] */, int n_slots, int max_gap,
+                  unsigned char* flags /* [n,12] */, tip_stream_t stream);
+TIP_API int tip_fill_get(const void* state, int n_slots, const int* slots, int count, int* counts_out /* [count,3,12] */,
+                 tip_stream_t stream);
+TIP_API int tip_fill_packets(const float* tables /* [n_seq,126] */, const float* packets /* [n_rows,42] */, long long n_rows,
+                     const long long* offsets /* [n_seq+1] */, int n_seq, float max_acc, float* out /* [n_rows,72] */,
+                     tip_stream_t stream);
+
 /* ---- kinematics: forward kinematics of the character, the root track with its SBP correction, and the evaluation script's seven
  *      metrics — what the reference does through PyBullet behind RTRunnerMin.step (real_time_runner_minimal.py:159-194;
  *      data_utils.py:262-306, 397-412, 473-548) and in offline_testing_simple.py --compare_gt (:422-453; data_utils.py:314-391).

@@ -48,6 +48,7 @@ EXPORTS = (
     "tip_replay_feed", "tip_replay_collect", "tip_replay_mask", "tip_replay_collect_tracked",
     "tip_sensor_state_bytes", "tip_sensor_reset", "tip_sensor_begin", "tip_sensor_accumulate", "tip_sensor_finish", "tip_sensor_set",
     "tip_sensor_get", "tip_sensor_transform",
+    "tip_fill_real", "tip_fill_rows", "tip_fill_state_bytes", "tip_fill_reset", "tip_fill_live", "tip_fill_get", "tip_fill_packets",
     "tip_kin_skel_bytes", "tip_kin_carry_bytes", "tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_kin_metrics",
     "tip_terrain_state_bytes", "tip_terrain_reset", "tip_terrain_track",
     "tip_syn_skel_bytes", "tip_syn_grid_bytes", "tip_syn_poses", "tip_syn_imu", "tip_syn_sbp",
@@ -195,6 +196,14 @@ def load() -> ctypes.CDLL:
     lib.tip_sensor_set.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.tip_sensor_get.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.tip_sensor_transform.argtypes = [vp, vp, i32, ctypes.c_float, vp, vp]
+    # missing readings (csrc/tip_fill.hip): rule R on recorded files, rule V on frames, on the live frame and behind recorded packets
+    lib.tip_fill_real.argtypes = [vp, vp, ctypes.c_longlong, i32, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_double), vp, vp, vp]
+    lib.tip_fill_rows.argtypes = [vp, vp, ctypes.c_longlong, vp, i32, i32, vp, vp]
+    lib.tip_fill_state_bytes.argtypes = [i32, ctypes.POINTER(sz)]
+    lib.tip_fill_reset.argtypes = [vp, i32, vp, i32, vp]
+    lib.tip_fill_live.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+    lib.tip_fill_get.argtypes = [vp, i32, vp, i32, vp, vp]
+    lib.tip_fill_packets.argtypes = [vp, vp, ctypes.c_longlong, vp, i32, ctypes.c_float, vp, vp]
     # kinematics (csrc/tip_kin.hip): the skeleton table, then what the header lists, then the stream
     lib.tip_kin_skel_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_kin_carry_bytes.argtypes = [i32, ctypes.POINTER(sz)]

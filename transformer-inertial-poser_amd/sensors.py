@@ -12,11 +12,18 @@ the 72-column frame `step(raw)` takes.  Here the tables live in HBM, one block p
     front.begin_tpose([i]);   front.accumulate(packets) ...; front.finish([i])       # hold 2: worn, standing in T-pose
     out = engine.step_packets(front, packets)                                        # packets [n,42] -> raw on the device -> the frame
     saved = front.tables([i]); other.load([i], saved)                                # a calibration kept and put back without the holds
+    front = SensorFrontEnd(n, "cuda", fill=True)                                     # a sensor that delivers nothing: the mean of its last rows
 
 packets is [n, 42] float32, per sensor q0 q1 q2 q3 ax ay az, the quaternion read as (x, y, z, w): what the demo hands to fairmotion's
 Q2R, i.e. scipy's Rotation.from_quat(q).as_matrix() (fairmotion itself is unpinned, as for A2R / R2A).  accumulate() takes the whole
 pool's packets and only the slots that are in a hold use theirs, so one wearer calibrates between the frames of the others.  Phases
 change through these calls only, so the host's copy of them (PhaseMirror) is exact and nothing here reads the device or synchronises.
+
+Missing readings (csrc/tip_fill.hip; include/tip_hip.h, "missing IMU readings"): the reference fills them when it prepares the real
+recordings (preprocess_DIP_TC_new.py:112-136, :160-180).  real_imu_frames is that preparation on the device (rule R, fp64, what
+tip_amd.data.combine_motions takes as "imu"); SensorFrontEnd(fill=True) is its live form (rule V: a ring of the last five rows after
+filling, per sensor and part), one launch behind the transform; fill_sequences and transform_sequences do the same to recorded frames
+and recorded packet sessions, frame for frame what the live front end gives, as recordings for tip_amd.replay.ReplayPool.
 """
 from __future__ import annotations
 
@@ -33,6 +40,24 @@ PACKET, TABLE = 42, 126
 # the demo's aligned T-pose (front x, left y, up z; live_demo_new.py:52-62), what finish() uses when no r_gp_b0 is given: the exact
 # form of A2R([0, 0, pi / 2]) @ [[1,0,0],[0,0,-1],[0,1,0]], whose fp64 product carries 2e-16 residues of cos(pi / 2)
 ALIGNED_T_POSE = np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
+# preprocess_DIP_TC_new.py: the six sensors the model reads (root, left wrist, right wrist, left knee, right knee, head; :166) among
+# DIP-IMU's 17, and the same six among TotalCapture's own (its scatter into 17 slots, :89-90, followed by that selection)
+SEL_DIP17 = (2, 7, 8, 11, 12, 0)
+SEL_TC6 = (5, 2, 3, 0, 1, 4)
+# ROT_MAT_OURS of the two corpora: Q2R((.5, .5, .5, .5)) in its exact form, and A2R((pi / 2, 0, 0)) as scipy gives it (tests pin both)
+ROT_DIP = np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
+_C90 = 2.220446049250313e-16                                     # scipy's cos(pi / 2) in from_rotvec([pi / 2, 0, 0]).as_matrix()
+ROT_TC = np.array([[1.0, 0.0, 0.0], [0.0, _C90, -1.0], [0.0, 1.0, _C90]])
+PARTS = 12                                                       # of a row: the rotation of sensor k (k < 6), the acceleration of sensor k - 6
+
+
+def _max_gap_arg(max_gap, who):
+    """max_gap as the C ABI takes it: None -> -1 (no limit), else an int >= 0."""
+    if max_gap is None:
+        return -1
+    if isinstance(max_gap, bool) or not isinstance(max_gap, (int, np.integer)) or max_gap < 0:
+        raise ValueError(f"tip_amd.{who}: max_gap is None (no limit) or a number of consecutive fills >= 0; got {max_gap!r}")
+    return int(max_gap)
 
 
 class PhaseMirror:
@@ -76,9 +101,15 @@ class PhaseMirror:
 class SensorFrontEnd:
     """n calibration blocks and a packet buffer [n, 42] on `device`.  max_acc: the clip of the room-frame acceleration (the demo's
     MAX_ACC).  r_gp_b0: the bone orientations of the T-pose, [6, 3, 3] or [6, 9] (kept as fp64); None is the demo's aligned T-pose,
-    [[0,0,1],[1,0,0],[0,1,0]] for all six sensors.  Every call is launches and non-blocking copies on the current stream."""
+    [[0,0,1],[1,0,0],[0,1,0]] for all six sensors.  Every call is launches and non-blocking copies on the current stream.
 
-    def __init__(self, n: int, device, max_acc: float = 10.0, r_gp_b0=None):
+    fill=True: a sensor part (9 rotation or 3 acceleration columns) that comes out of the transform with a NaN becomes the mean of the
+    slot's last five rows of that part after filling (rule V of include/tip_hip.h), one tip_fill_live launch behind the transform;
+    `filled` [n, 12] uint8 says what happened to the last frame (0 good, 1 filled, 2 left NaN: nothing to fill from, or max_gap
+    consecutive fills already made; max_gap=None is no limit, as the reference has none).  The rings of a slot are emptied whenever it
+    is calibrated anew (finish, load, begin_heading) — a new wearer never inherits another's readings — and by fill_reset."""
+
+    def __init__(self, n: int, device, max_acc: float = 10.0, r_gp_b0=None, *, fill: bool = False, max_gap=None):
         self.n = int(n)
         if self.n < 1:
             raise ValueError(f"tip_amd.SensorFrontEnd: n is the number of slots, at least 1; got {n!r}")
@@ -102,8 +133,18 @@ class SensorFrontEnd:
             if r.numel() != 54:
                 raise ValueError(f"tip_amd.SensorFrontEnd: r_gp_b0 is [6, 3, 3] or [6, 9]; got {tuple(r.shape)}")
             self.r_gp_b0 = self._to_dev(r.reshape(6, 9).contiguous())
+        self.fill = bool(fill)
+        self.max_gap = _max_gap_arg(max_gap, "SensorFrontEnd")
+        if self.max_gap >= 0 and not self.fill:
+            raise ValueError("tip_amd.SensorFrontEnd: max_gap limits the fill; give it with fill=True")
+        self.fill_state = self.filled = None
         with torch.cuda.device(self.device):
             self._check(self.lib.tip_sensor_reset(self.cal.data_ptr(), self.n, self._stream()))
+            if self.fill:
+                self._check(self.lib.tip_fill_state_bytes(self.n, ctypes.byref(nbytes)))
+                self.fill_state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+                self.filled = torch.zeros((self.n, PARTS), dtype=torch.uint8, device=self.device)
+                self._check(self.lib.tip_fill_reset(self.fill_state.data_ptr(), self.n, None, 0, self._stream()))
 
     def _check(self, status: int):
         if status < 0:
@@ -128,10 +169,44 @@ class SensorFrontEnd:
         self.packets.copy_(p if p.is_cuda else p.contiguous().pin_memory(), non_blocking=True)
 
     def _transform_into(self, raw):
-        """One tip_sensor_transform launch: the packet buffer -> raw [n, 72] (a CUDA float32 tensor of this device, contiguous)."""
+        """One tip_sensor_transform launch: the packet buffer -> raw [n, 72] (a CUDA float32 tensor of this device, contiguous); with
+        fill=True one tip_fill_live launch behind it, in place on raw."""
         with torch.cuda.device(self.device):
             self._check(self.lib.tip_sensor_transform(self.cal.data_ptr(), self.packets.data_ptr(), self.n, self.max_acc, raw.data_ptr(),
                                                       self._stream()))
+            if self.fill:
+                self._check(self.lib.tip_fill_live(self.fill_state.data_ptr(), self.cal.data_ptr(), raw.data_ptr(), self.n, self.max_gap,
+                                                   self.filled.data_ptr(), self._stream()))
+
+    # ---- missing readings (fill=True) ------------------------------------------------------------------------------------------------
+    def _fill_reset(self, idx):
+        """The rings of the listed slots start empty (nothing without fill=True)."""
+        if not self.fill or not idx:
+            return
+        with torch.cuda.device(self.device):
+            sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
+            self._check(self.lib.tip_fill_reset(self.fill_state.data_ptr(), self.n, sl.data_ptr(), len(idx), self._stream()))
+
+    def _needs_fill(self, who):
+        if not self.fill:
+            raise RuntimeError(f"tip_amd.SensorFrontEnd.{who}: this front end was built without fill=True")
+
+    def fill_reset(self, slots=None):
+        """Empty the rings and zero the counters of the listed slots (None: all)."""
+        self._needs_fill("fill_reset")
+        self._fill_reset(self._slots(slots, "fill_reset"))
+
+    def fill_counts(self, slots=None):
+        """(have, run, total) of the listed slots (None: all), three CUDA int32 tensors [len(slots), 12]: rows in the ring (0 .. 5),
+        consecutive fills up to the last frame, fills since the rings were emptied."""
+        self._needs_fill("fill_counts")
+        idx = self._slots(slots, "fill_counts")
+        out = torch.zeros((len(idx), 3, PARTS), dtype=torch.int32, device=self.device)
+        if idx:
+            with torch.cuda.device(self.device):
+                sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
+                self._check(self.lib.tip_fill_get(self.fill_state.data_ptr(), self.n, sl.data_ptr(), len(idx), out.data_ptr(), self._stream()))
+        return out[:, 0], out[:, 1], out[:, 2]
 
     # ---- the two holds ---------------------------------------------------------------------------------------------------------------
     def _begin(self, idx, which):
@@ -147,6 +222,7 @@ class SensorFrontEnd:
         idx = self._slots(slots, "begin_heading")
         self.mirror.begin_heading(idx)
         self._begin(idx, _lib.TIP_SENSOR_HEADING)
+        self._fill_reset(idx)
 
     def begin_tpose(self, slots=None):
         """Start the T-pose hold of the listed slots (live_demo_new.py:236-248); each needs a finished heading."""
@@ -175,6 +251,7 @@ class SensorFrontEnd:
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
             r = self.r_gp_b0.data_ptr() if self.r_gp_b0 is not None else None
             self._check(self.lib.tip_sensor_finish(self.cal.data_ptr(), self.n, sl.data_ptr(), len(idx), r, self._stream()))
+        self._fill_reset(idx)
 
     # ---- saved calibrations ----------------------------------------------------------------------------------------------------------
     def load(self, slots, tables):
@@ -192,6 +269,7 @@ class SensorFrontEnd:
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
             t = self._to_dev(t.contiguous()).contiguous()
             self._check(self.lib.tip_sensor_set(self.cal.data_ptr(), self.n, sl.data_ptr(), len(idx), t.data_ptr(), self._stream()))
+        self._fill_reset(idx)
 
     def tables(self, slots=None):
         """The tables of the listed slots (None: all) as a CUDA tensor [len(slots), 126], whatever their phase."""
@@ -220,3 +298,153 @@ class SensorFrontEnd:
         self._fill(packets, "SensorFrontEnd.transform")
         self._transform_into(out)
         return out
+
+
+# ---- recorded data: the real-IMU files, recorded frames with gaps, recorded packet sessions ------------------------------------------
+def _status(lib, status):
+    if status < 0:
+        raise _lib.TipStatusError(status, lib.tip_strerror(status).decode())
+
+
+def _device_of(arrays, device):
+    if device is not None:
+        dev = torch.device(device)
+    else:
+        dev = next((a.device for a in arrays if isinstance(a, torch.Tensor) and a.is_cuda), torch.device("cuda"))
+    if dev.type != "cuda":
+        raise RuntimeError("tip_amd.sensors: the fill kernels run on an MI355X; give a CUDA device")
+    return dev if dev.index is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def _to(t, dev):
+    return t.to(dev, non_blocking=True) if t.is_cuda else t.contiguous().pin_memory().to(dev, non_blocking=True)
+
+
+def _stack(arrays, dtype, width, dev, who, what):
+    """A list of [L_i, ...] arrays whose rows have `width` values -> (one contiguous [N, width] tensor on dev, int64 offsets [R + 1] on
+    dev, the lengths)."""
+    parts, lens = [], []
+    for i, a in enumerate(arrays):
+        t = torch.as_tensor(a)
+        if t.dim() < 2 or t.numel() != t.shape[0] * width:
+            raise ValueError(f"tip_amd.sensors.{who}: {what}[{i}] is [L, {width}] (or that many values per row); got {tuple(t.shape)}")
+        parts.append(_to(t.to(dtype).reshape(t.shape[0], width), dev))
+        lens.append(int(t.shape[0]))
+    if not parts:
+        raise ValueError(f"tip_amd.sensors.{who}: no sequences")
+    cat = torch.cat(parts, dim=0).contiguous() if len(parts) > 1 else parts[0].contiguous()
+    offs = _to(torch.tensor(np.concatenate(([0], np.cumsum(lens))), dtype=torch.int64), dev)
+    return cat, offs, lens
+
+
+def _split(t, lens):
+    out, at = [], 0
+    for n in lens:
+        out.append(t[at:at + n])
+        at += n
+    return out
+
+
+def real_imu_frames(ori_list, acc_list, rot, sel=SEL_DIP17, strict=True, device=None):
+    """The reference's preparation of real recordings (preprocess_DIP_TC_new.py: get_real_imu_readings_ours_format_knee over
+    fill_in_nan_values) for R recordings in one launch: ori_list[i] [L_i, S, 3, 3] and acc_list[i] [L_i, S, 3] (numpy or tensors, read as
+    fp64; S = 17 for DIP-IMU, 6 for TotalCapture as it is stored), `sel` the six sensors taken (SEL_DIP17, SEL_TC6), `rot` the corpus'
+    rotation (ROT_DIP, ROT_TC).  Returns a list of CUDA fp64 [L_i, 72] (views of one tensor): what tip_amd.data.combine_motions takes
+    as files[i]["imu"], in place.  A recording in which a part is still NaN afterwards (a sensor without one reading in rows 0 .. 9) is
+    a ValueError naming it, where the reference asserts; strict=False returns it with its NaNs and does not synchronise."""
+    who = "real_imu_frames"
+    if len(ori_list) != len(acc_list):
+        raise ValueError(f"tip_amd.sensors.{who}: {len(ori_list)} orientation arrays for {len(acc_list)} acceleration arrays")
+    sel = [int(v) for v in sel]
+    rot = np.ascontiguousarray(rot, dtype=np.float64)
+    if len(sel) != 6 or rot.shape != (3, 3):
+        raise ValueError(f"tip_amd.sensors.{who}: sel is six sensor indices and rot a 3x3 matrix")
+    if not len(ori_list):
+        raise ValueError(f"tip_amd.sensors.{who}: no sequences")
+    shape = tuple(torch.as_tensor(ori_list[0]).shape)
+    S = int(shape[1]) if len(shape) >= 3 else 0
+    if S < 1 or min(sel) < 0 or max(sel) >= S:
+        raise ValueError(f"tip_amd.sensors.{who}: ori_list[i] is [L, S, 3, 3] and sel picks six of the S sensors; got {shape} and {sel}")
+    dev = _device_of(list(ori_list) + list(acc_list), device)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ori, offs, lens = _stack(ori_list, torch.float64, S * 9, dev, who, "ori_list")
+        acc, _, lens_a = _stack(acc_list, torch.float64, S * 3, dev, who, "acc_list")
+        if lens != lens_a:
+            raise ValueError(f"tip_amd.sensors.{who}: orientation and acceleration lengths differ: {lens} and {lens_a}")
+        N, R = int(ori.shape[0]), len(lens)
+        out = torch.empty((N, 72), dtype=torch.float64, device=dev)
+        unfilled = torch.zeros(R, dtype=torch.int32, device=dev)
+        _status(lib, lib.tip_fill_real(ori.data_ptr(), acc.data_ptr(), N, S, offs.data_ptr(), R, (ctypes.c_int * 6)(*sel),
+                                       (ctypes.c_double * 9)(*rot.reshape(-1)), out.data_ptr(), unfilled.data_ptr(),
+                                       torch.cuda.current_stream(dev).cuda_stream))
+        if strict:
+            left = unfilled.cpu().numpy()
+            if left.any():
+                bad = [f"{i} ({int(left[i])} parts)" for i in np.flatnonzero(left)]
+                raise ValueError(f"tip_amd.sensors.{who}: sequences {', '.join(bad)} keep NaN readings after the fill (a sensor without "
+                                 "one reading in the rows it is filled from); strict=False returns them as they are")
+    return _split(out, lens)
+
+
+def fill_sequences(frames_list, rule="live", max_gap=None, device=None, host=False, return_flags=False):
+    """Recorded frames with gaps -> recordings: frames_list[i] is [L_i, 72] float32 (54 rotation columns, 18 acceleration columns, NaN
+    where a sensor delivered nothing); every sequence is filled as SensorFrontEnd(fill=True, max_gap=max_gap) fills a stream that
+    starts with empty rings, bit for bit, all of them in one launch.  Returns a list of CUDA float32 [L_i, 72]; host=True: numpy
+    arrays, as ReplayPool.run takes them; return_flags=True: (recordings, flags), flags[i] uint8 [L_i, 12] as SensorFrontEnd.filled.
+    rule="live" is the only rule for frames: the reference's own rule looks ahead and is real_imu_frames' (fp64, whole files)."""
+    who = "fill_sequences"
+    if rule != "live":
+        raise ValueError(f"tip_amd.sensors.{who}: rule is \"live\" (the reference's look-ahead rule is real_imu_frames'); got {rule!r}")
+    gap = _max_gap_arg(max_gap, who)
+    dev = _device_of(list(frames_list), device)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        frames, offs, lens = _stack(frames_list, torch.float32, 72, dev, who, "frames_list")
+        out = torch.empty_like(frames)
+        flags = torch.zeros((frames.shape[0], PARTS), dtype=torch.uint8, device=dev)
+        _status(lib, lib.tip_fill_rows(frames.data_ptr(), out.data_ptr(), int(frames.shape[0]), offs.data_ptr(), len(lens), gap,
+                                       flags.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return _recordings(out, flags, lens, host, return_flags)
+
+
+def _recordings(out, flags, lens, host, return_flags):
+    recs = _split(out, lens)
+    if host:
+        recs = [r.cpu().numpy() for r in recs]
+    if not return_flags:
+        return recs
+    fl = _split(flags, lens)
+    return recs, ([f.cpu().numpy() for f in fl] if host else fl)
+
+
+def transform_sequences(packets_list, tables, fill=False, max_acc=10.0, max_gap=None, device=None, host=False, return_flags=False):
+    """Recorded packet sessions -> recordings: packets_list[i] is [L_i, 42] float32 (SensorFrontEnd's packet layout), tables [R, 126]
+    the wearers' calibrations (SensorFrontEnd.tables).  Every row goes through tip_sensor_transform's arithmetic (one row-parallel
+    launch, bit for bit what SensorFrontEnd.transform gives frame by frame) and, with fill=True, through fill_sequences' launch in
+    place.  Returns as fill_sequences does."""
+    who = "transform_sequences"
+    gap = _max_gap_arg(max_gap, who)
+    if gap >= 0 and not fill:
+        raise ValueError(f"tip_amd.sensors.{who}: max_gap limits the fill; give it with fill=True")
+    max_acc = float(max_acc)
+    if not max_acc >= 0.0:
+        raise ValueError(f"tip_amd.sensors.{who}: max_acc is the acceleration clip, a number >= 0; got {max_acc!r}")
+    dev = _device_of(list(packets_list) + [tables], device)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        packets, offs, lens = _stack(packets_list, torch.float32, PACKET, dev, who, "packets_list")
+        t = torch.as_tensor(tables, dtype=torch.float32)
+        if t.dim() == 1:
+            t = t.unsqueeze(0)
+        if tuple(t.shape) != (len(lens), TABLE):
+            raise ValueError(f"tip_amd.sensors.{who}: tables is [{len(lens)}, {TABLE}], one per session; got {tuple(t.shape)}")
+        t = _to(t, dev).contiguous()
+        N = int(packets.shape[0])
+        out = torch.empty((N, 72), dtype=torch.float32, device=dev)
+        flags = torch.zeros((N, PARTS), dtype=torch.uint8, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _status(lib, lib.tip_fill_packets(t.data_ptr(), packets.data_ptr(), N, offs.data_ptr(), len(lens), max_acc, out.data_ptr(), stream))
+        if fill:
+            _status(lib, lib.tip_fill_rows(out.data_ptr(), out.data_ptr(), N, offs.data_ptr(), len(lens), gap, flags.data_ptr(), stream))
+    return _recordings(out, flags, lens, host, return_flags)
