@@ -375,6 +375,42 @@ def test_two_sbp_models(skel):
         tt.step({"s_rest": torch.zeros(3, 111, device="cuda"), "c_t": torch.zeros(3, 8, device="cuda")})
 
 
+# ---- 9. one SBP step for both runners --------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def edge_rows():
+    """Three sequences of 1, 64 and 65 rows — the edges of the 64-row FK tile — cut from the golden tracks, with the numpy oracle's word
+    that they test something: on each, some row has an active foot, and nothing the flat-ground runner makes of them is non-finite."""
+    import kin_oracle as ko
+    cuts = (("track2", 5, 6), ("track0", 0, 64), ("track1", 0, 65))      # the standing track's feet are down on its first valid row
+    seqs = []
+    for tag, a, b in cuts:
+        s_init, s_rest, ct, valid, _ = _case(tag, False)
+        seqs.append((s_init, s_rest[a:b], ct[a:b], valid[a:b]))
+    for s_init, s_rest, ct, valid in seqs:
+        for nc in (20, 8):
+            root, viz, tr = ko.track(TABLE, s_init, s_rest, ct[:, :nc], valid)
+            assert (tr["flags"] == 1).any() and np.isfinite(root).all() and np.isfinite(viz).all()
+    offs = np.concatenate([[0], np.cumsum([s[1].shape[0] for s in seqs])]).astype(np.int64)
+    return seqs, offs
+
+
+@pytest.mark.parametrize("nc", [20, 8])
+@pytest.mark.parametrize("chunk", [None, 7])
+def test_flat_ground_and_terrain_runners_agree_on_x_and_y_bit_for_bit(skel, edge_rows, chunk, nc):
+    """kinematics.track and terrain.track_terrain(multi_sbp=False) run the same SBP step (csrc/tip_kin_track.h) and disagree about the
+    height only — the flat-ground rule against the map — which neither x nor y reads: the x and y columns of root and of viz_locs are
+    the same bits."""
+    seqs, offs = edge_rows
+    s0, s_rest, ct, valid = (np.stack([s[0] for s in seqs]), np.concatenate([s[1] for s in seqs]),
+                             np.concatenate([s[2][:, :nc] for s in seqs]), np.concatenate([s[3] for s in seqs]))
+    root_k, viz_k = _np(*kin.track(skel, s0, s_rest, ct, valid, offs, chunk=chunk))
+    root_t, viz_t = _np(*terrain.track_terrain(skel, s0, s_rest, ct, valid, offs, multi_sbp=False, chunk=chunk)[:2])
+    assert root_k.shape == (130, 3) and viz_k.shape == (130, 5, 3)
+    assert np.array_equal(root_k[:, :2].view(np.uint32), root_t[:, :2].view(np.uint32))
+    assert np.array_equal(viz_k[:, :, :2].view(np.uint32), viz_t[:, :, :2].view(np.uint32))
+    assert not np.array_equal(root_k[:, 2], root_t[:, 2])              # (the two did run their own z rules)
+
+
 def test_track_replay_routes_through_the_terrain(skel):
     """kinematics.track_replay(terrain=...) is track_terrain with multi_sbp off on the same rows; terrain=None is the flat-ground tracker."""
     from tip_amd.replay import ReplayResult

@@ -266,7 +266,7 @@ int tip_gather_windows(const float* imu_c, const float* sum_c, const float* s_c,
     if (n == 0) return TIP_OK;
     hipLaunchKernelGGL(gather_windows_kernel, dim3(n), dim3(256), 0, static_cast<hipStream_t>(stream), imu_c, sum_c, s_c, t_idx, T,
                        x_imu, x_s, y);
-    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+    return tip_launch_status();
 }
 
 }  // extern "C"

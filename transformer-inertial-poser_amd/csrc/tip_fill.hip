@@ -304,7 +304,6 @@ using namespace tip;
 
 extern "C" {
 
-static int fill_done() { return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP; }
 static bool fill_bad_n(long long n) { return n < 0 || n > (1ll << 24); }
 static bool fill_bad_rows(long long n) { return n < 0 || n > (1ll << 40); }
 
@@ -322,7 +321,7 @@ int tip_fill_real(const double* ori, const double* acc, long long n_rows, int n_
     if (n_seq == 0) return TIP_OK;
     hipLaunchKernelGGL(fill_real_kernel, dim3(n_seq), dim3(384), 0, static_cast<hipStream_t>(stream), ori, acc, n_rows, n_sensors, offsets,
                        args, out, unfilled);
-    return fill_done();
+    return tip_launch_status();
 }
 
 int tip_fill_rows(const float* frames, float* out, long long n_rows, const long long* offsets, int n_seq, int max_gap,
@@ -331,7 +330,7 @@ int tip_fill_rows(const float* frames, float* out, long long n_rows, const long 
     if (n_seq == 0 || n_rows == 0) return TIP_OK;
     hipLaunchKernelGGL(fill_rows_kernel, dim3((n_seq * fl::PARTS + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), frames, out,
                        n_rows, offsets, n_seq, max_gap, flags);
-    return fill_done();
+    return tip_launch_status();
 }
 
 int tip_fill_state_bytes(int n_slots, size_t* bytes) {
@@ -346,7 +345,7 @@ int tip_fill_reset(void* state, int n_slots, const int* slots, int count, tip_st
     if (blocks == 0 || n_slots == 0) return TIP_OK;
     hipLaunchKernelGGL(fill_reset_kernel, dim3(blocks), dim3(128), 0, static_cast<hipStream_t>(stream), static_cast<FillSlot*>(state),
                        n_slots, slots);
-    return fill_done();
+    return tip_launch_status();
 }
 
 int tip_fill_live(void* state, const void* cal, float* raw, int n_slots, int max_gap, unsigned char* flags, tip_stream_t stream) {
@@ -354,7 +353,7 @@ int tip_fill_live(void* state, const void* cal, float* raw, int n_slots, int max
     if (n_slots == 0) return TIP_OK;
     hipLaunchKernelGGL(fill_live_kernel, dim3((n_slots * fl::PARTS + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<FillSlot*>(state), static_cast<const SensorCal*>(cal), raw, n_slots, max_gap, flags);
-    return fill_done();
+    return tip_launch_status();
 }
 
 int tip_fill_get(const void* state, int n_slots, const int* slots, int count, int* counts_out, tip_stream_t stream) {
@@ -362,7 +361,7 @@ int tip_fill_get(const void* state, int n_slots, const int* slots, int count, in
     if (count == 0 || n_slots == 0) return TIP_OK;
     hipLaunchKernelGGL(fill_get_kernel, dim3(count), dim3(64), 0, static_cast<hipStream_t>(stream), static_cast<const FillSlot*>(state),
                        n_slots, slots, counts_out);
-    return fill_done();
+    return tip_launch_status();
 }
 
 int tip_fill_packets(const float* tables, const float* packets, long long n_rows, const long long* offsets, int n_seq, float max_acc,
@@ -374,7 +373,7 @@ int tip_fill_packets(const float* tables, const float* packets, long long n_rows
     if (blocks > 0x7fffffffll) return TIP_ERR_INVALID_ARG;
     hipLaunchKernelGGL(fill_packets_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), tables, packets, n_rows,
                        offsets, n_seq, max_acc, out);
-    return fill_done();
+    return tip_launch_status();
 }
 
 }  // extern "C"

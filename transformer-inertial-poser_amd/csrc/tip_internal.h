@@ -276,6 +276,12 @@ __device__ __forceinline__ void guard_report(unsigned* err) {
     if (err) __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
+// What the C entry points of the consumers beside the engines (kinematics, terrain, synthesis, sensors, fill, replay, loss, data) answer
+// after a launch, and the two bounds they share: a count of slots or sequences is at most 2^24, a count of rows at most 2^30.
+inline int tip_launch_status() { return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP; }
+inline bool tip_bad_count(int n) { return n < 0 || n > (1 << 24); }
+inline bool tip_bad_rows(long long n) { return n < 0 || n > (1LL << 30); }
+
 // Launch-side caches are PER DEVICE, not per process: a process may hold one handle per GPU (include/tip_hip.h), and a
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) or an occupancy answer obtained on one device says nothing about the next.
 constexpr int kMaxDevices = 64;

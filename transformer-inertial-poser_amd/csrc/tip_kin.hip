@@ -25,8 +25,12 @@
 // root as fp64; outputs are rounded to fp32 once.  The metrics are fp64 on the fp32 poses.
 //
 // Nothing waits on another workgroup; a carry block is written by the one wave whose sequence names it.
-#include "tip_kin_fk.h"      // KinLinkT, a2q, qmul, qrot, fk_frames, fk_to_com: one body for fp32 (here) and fp64 (tip_syn.hip);
-                             // KinSkel, KinCarry and the fp32 FK wrappers, which tip_terrain.hip reads too
+//
+// The scan's frame — root_pre, the SBP locations, the residues, the nanmean and the clip — the scan state's load, advance and store,
+// and the carry's initialisation are tip_kin_track.h's: one body for this tracker and for tip_terrain.hip's.  What is written out
+// below is this tracker's own: the flat-ground z rule and the shift of the outputs.
+#include "tip_kin_track.h"   // sbp_step and the carry; over tip_kin_fk.h: KinLinkT, a2q, qmul, qrot, fk_frames, fk_to_com, one body for
+                             // fp32 (here) and fp64 (tip_syn.hip), KinSkel, KinCarry and the fp32 FK wrappers
 
 namespace tip {
 
@@ -69,18 +73,9 @@ __global__ __launch_bounds__(64) void kin_reset_kernel(const KinSkel* __restrict
     if (j >= count) return;
     const int slot = slots ? slots[j] : j;
     if (slot < 0 || slot >= n_slots) return;
-    float* F = Fs + lane;
-    const float* row = s_init + (size_t)j * kn::QDQ;
-    fk_frames(sk, L, row + 3, 0.f, 0.f, 0.f, F);
-    fk_to_com(sk, L, F);
-    KinCarry& c = carry[slot];
-    for (int k = 0; k < 3; ++k) c.root[k] = (double)row[k], c.vprev[k] = 0.f;
-    c.has_prev = 0;
-    for (int e = 0; e < (L + 1) * 7; ++e) c.pq[e] = F[e * kn::COL];
+    carry_init(sk, L, carry[slot], s_init + (size_t)j * kn::QDQ, Fs + lane);
+    carry_init_pq(carry[slot], Fs + lane, L, 0, 1);
 }
-
-// np.clip(v, -m, m): a NaN stays a NaN
-__device__ __forceinline__ double clip_nan_transparent_d(double v, double m) { return v < -m ? -m : (v > m ? m : v); }
 
 __global__ __launch_bounds__(64) void kin_track_kernel(const KinSkel* __restrict__ skp, KinCarry* __restrict__ carry, int n_slots,
                                                        const int* __restrict__ slots, const long long* __restrict__ begin,
@@ -92,31 +87,17 @@ __global__ __launch_bounds__(64) void kin_track_kernel(const KinSkel* __restrict
     __shared__ int last_s;
     const KinSkel& sk = *skp;
     const int L = kin_links(sk), lane = threadIdx.x, per = (L + 1) * 7;
-    const int seq = blockIdx.x;
-    const int slot = slots ? slots[seq] : seq;
-    if (slot < 0 || slot >= n_slots) return;                      // (uniform over the wave: every return below is)
-    long long r0 = begin[seq], r1 = end[seq];
-    if (r0 < 0) r0 = 0;
-    if (r1 > n_rows) r1 = n_rows;
-    if (r1 <= r0) return;
+    int slot;
+    long long r0, r1;
+    if (!track_range(slots, begin, end, blockIdx.x, n_slots, n_rows, slot, r0, r1)) return;      // (uniform over the wave)
     KinCarry& cr = carry[slot];
     const int n_sbps = nc / 4;
     int body[kn::SBPS];
-    for (int i = 0; i < kn::SBPS; ++i) body[i] = (sk.sbp[i] < 0 || sk.sbp[i] > L) ? 0 : sk.sbp[i];
+    sbp_bodies(sk, L, body);
     float* F = Fs + lane;
 
-    // lane 0's scan state: the corrected root, and the previous valid frame's SBP-body poses about it
-    double root[3] = {0.0, 0.0, 0.0};
-    float x1r[2][3], q1[2][4], vprev[3] = {0.f, 0.f, 0.f};
-    int has_prev = 0;
-    if (lane == 0) {
-        for (int k = 0; k < 3; ++k) root[k] = cr.root[k], vprev[k] = cr.vprev[k];
-        has_prev = cr.has_prev;
-        for (int i = 0; i < 2; ++i) {
-            for (int k = 0; k < 3; ++k) x1r[i][k] = cr.pq[7 * body[i] + k];
-            for (int k = 0; k < 4; ++k) q1[i][k] = cr.pq[7 * body[i] + 3 + k];
-        }
-    }
+    SbpScan<2> st;                                                // lane 0's scan state
+    if (lane == 0) sbp_scan_load(st, cr, body);
     for (long long t0 = r0; t0 < r1; t0 += kn::LANES) {
         const long long left = r1 - t0;
         const int cnt = left < kn::LANES ? (int)left : kn::LANES;
@@ -133,90 +114,32 @@ __global__ __launch_bounds__(64) void kin_track_kernel(const KinSkel* __restrict
                 float* ro = root_out + row * 3;
                 float* vo = viz_out + row * 15;
                 if (valid && !valid[row]) {                          // what the runner returns while it primes: the carry's root, 100s
-                    for (int k = 0; k < 3; ++k) ro[k] = (float)root[k];
+                    for (int k = 0; k < 3; ++k) ro[k] = (float)st.root[k];
                     for (int k = 0; k < 15; ++k) vo[k] = 100.f;
                     continue;
                 }
                 const float* sr = s_rest + row * kn::REST;
-                const float* ct = c_t + row * nc;
-                double pre[3], cl[kn::SBPS][3], res[2][3];
-                for (int k = 0; k < 3; ++k) {                        // :159, on the velocity from before the averaging
-                    const double v = has_prev ? 2.0 * (double)sr[54 + k] - (double)vprev[k] : (double)sr[54 + k];
-                    pre[k] = root[k] + v * kn::DT;
-                }
-                for (int i = 0; i < kn::SBPS; ++i)
-                    for (int k = 0; k < 3; ++k) cl[i][k] = 100.0;
-                const double nan = __builtin_nan("");
-                for (int i = 0; i < 2; ++i)
-                    for (int k = 0; k < 3; ++k) res[i][k] = nan;
-                for (int i = 0; i < n_sbps; ++i) {
-                    if (ct[4 * i] == 0.f) continue;                  // inactive: location 100, residue NaN
-                    double x2[3], sol[3];
-                    for (int k = 0; k < 3; ++k) {
-                        x2[k] = (double)Fs[(7 * body[i] + k) * kn::COL + j] + pre[k];
-                        sol[k] = (double)ct[4 * i + 1 + k];
-                        cl[i][k] = x2[k] + sol[k];
-                    }
-                    if (i >= 2) continue;                            // only the two feet correct the root (:517-520)
-                    double q2[4], dq[4], sq[4], sub[4], cj[4], dori[4];
-                    double nd = 0.0, ns = 0.0;
-                    for (int k = 0; k < 4; ++k) {
-                        q2[k] = (double)Fs[(7 * body[i] + 3 + k) * kn::COL + j];
-                        dq[k] = q2[k] - (double)q1[i][k], sq[k] = q2[k] + (double)q1[i][k];
-                        nd += dq[k] * dq[k], ns += sq[k] * sq[k];
-                    }
-                    const bool minus = sqrt(nd) < sqrt(ns);
-                    for (int k = 0; k < 4; ++k) sub[k] = minus ? dq[k] : sq[k];
-                    cj[0] = -q2[0], cj[1] = -q2[1], cj[2] = -q2[2], cj[3] = q2[3];
-                    qmul<double>(sub, cj, dori);
-                    double w[3], v[3];
-                    for (int k = 0; k < 3; ++k) {
-                        w[k] = 2.0 * dori[k] / kn::DT;
-                        v[k] = (x2[k] - ((double)x1r[i][k] + root[k])) / kn::DT;
-                    }
-                    res[i][0] = (w[1] * sol[2] - w[2] * sol[1]) + v[0];
-                    res[i][1] = (w[2] * sol[0] - w[0] * sol[2]) + v[1];
-                    res[i][2] = (w[0] * sol[1] - w[1] * sol[0]) + v[2];
-                }
-                bool all_nan = true;
-                for (int i = 0; i < 2; ++i)
-                    for (int k = 0; k < 3; ++k) all_nan = all_nan && (res[i][k] != res[i][k]);
-                double vr[3];
-                for (int k = 0; k < 3; ++k) {
-                    if (all_nan) { vr[k] = 0.0; continue; }
-                    const bool a = res[0][k] == res[0][k], b = res[1][k] == res[1][k];      // np.nanmean over the two feet
-                    const double m = a && b ? (res[0][k] + res[1][k]) / 2.0 : (a ? res[0][k] : (b ? res[1][k] : nan));
-                    vr[k] = clip_nan_transparent_d(m, 0.5);
-                }
+                double pre[3], cl[kn::SBPS][3], res[2][3], vr[3];
+                sbp_step<2>(st, body, sr, c_t + row * nc, n_sbps, Fs, j, pre, cl, res, vr);      // :159-183
                 vr[2] = 0.0;                                         // flat ground (:184-189), the norm test taken literally
                 for (int i = 0; i < 2; ++i)
                     if (sqrt(cl[i][0] * cl[i][0] + cl[i][1] * cl[i][1] + cl[i][2] * cl[i][2]) < 100.0) vr[2] += cl[i][2] * 1.0;
                 for (int k = 0; k < 3; ++k) {
                     const double d = vr[k] * kn::DT;
-                    root[k] = pre[k] - d;
-                    ro[k] = (float)root[k];
+                    st.root[k] = pre[k] - d;
+                    ro[k] = (float)st.root[k];
                     for (int i = 0; i < kn::SBPS; ++i) vo[3 * i + k] = (float)(cl[i][k] - d);
                 }
-                for (int i = 0; i < 2; ++i) {
-                    for (int k = 0; k < 3; ++k) x1r[i][k] = Fs[(7 * body[i] + k) * kn::COL + j];
-                    for (int k = 0; k < 4; ++k) q1[i][k] = Fs[(7 * body[i] + 3 + k) * kn::COL + j];
-                }
-                for (int k = 0; k < 3; ++k) vprev[k] = sr[54 + k];
-                has_prev = 1;
+                sbp_advance(st, body, sr, Fs, j);
                 last = j;
             }
             last_s = last;
         }
         __syncthreads();
-        const int last = last_s;
-        if (last >= 0)
-            for (int e = lane; e < per; e += kn::LANES) cr.pq[e] = Fs[e * kn::COL + last];
+        carry_store_pq(cr, Fs, per, last_s, lane);
         __syncthreads();
     }
-    if (lane == 0) {
-        for (int k = 0; k < 3; ++k) cr.root[k] = root[k], cr.vprev[k] = vprev[k];
-        cr.has_prev = has_prev;
-    }
+    if (lane == 0) sbp_scan_store(st, cr);
 }
 
 // fixed-order sum of one double per thread over a 256-thread workgroup
@@ -310,10 +233,6 @@ using namespace tip;
 
 extern "C" {
 
-static int kin_done() { return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP; }
-static bool kin_bad_rows(long long n) { return n < 0 || n > (1LL << 30); }
-static bool kin_bad_slots(int n) { return n < 0 || n > (1 << 24); }
-
 int tip_kin_skel_bytes(size_t* bytes) {
     if (!bytes) return TIP_ERR_INVALID_ARG;
     *bytes = sizeof(KinSkel);
@@ -321,33 +240,33 @@ int tip_kin_skel_bytes(size_t* bytes) {
 }
 
 int tip_kin_carry_bytes(int n_slots, size_t* bytes) {
-    if (!bytes || kin_bad_slots(n_slots)) return TIP_ERR_INVALID_ARG;
+    if (!bytes || tip_bad_count(n_slots)) return TIP_ERR_INVALID_ARG;
     *bytes = (size_t)n_slots * sizeof(KinCarry);
     return TIP_OK;
 }
 
 int tip_kin_fk(const void* skel, const float* q, int ldq, long long n, float* pq_g, float* pq_jf, tip_stream_t stream) {
-    if (!skel || !q || !pq_g || kin_bad_rows(n) || ldq < kn::NQ) return TIP_ERR_INVALID_ARG;
+    if (!skel || !q || !pq_g || tip_bad_rows(n) || ldq < kn::NQ) return TIP_ERR_INVALID_ARG;
     if (n == 0) return TIP_OK;
     hipLaunchKernelGGL(kin_fk_kernel, dim3((unsigned)((n + kn::LANES - 1) / kn::LANES)), dim3(kn::LANES), 0,
                        static_cast<hipStream_t>(stream), static_cast<const KinSkel*>(skel), q, ldq, n, pq_g, pq_jf);
-    return kin_done();
+    return tip_launch_status();
 }
 
 int tip_kin_track_reset(const void* skel, void* carry, int n_slots, const int* slots, int count, const float* s_init,
                         tip_stream_t stream) {
-    if (!skel || !carry || kin_bad_slots(n_slots) || count < 0 || (count > 0 && !s_init) || reinterpret_cast<uintptr_t>(carry) % 8)
+    if (!skel || !carry || tip_bad_count(n_slots) || count < 0 || (count > 0 && !s_init) || reinterpret_cast<uintptr_t>(carry) % 8)
         return TIP_ERR_INVALID_ARG;
     if (count == 0 || n_slots == 0) return TIP_OK;
     hipLaunchKernelGGL(kin_reset_kernel, dim3((count + kn::LANES - 1) / kn::LANES), dim3(kn::LANES), 0, static_cast<hipStream_t>(stream),
                        static_cast<const KinSkel*>(skel), static_cast<KinCarry*>(carry), n_slots, slots, count, s_init);
-    return kin_done();
+    return tip_launch_status();
 }
 
 int tip_kin_track(const void* skel, void* carry, int n_slots, const int* slots, const long long* begin, const long long* end, int count,
                   long long n_rows, const float* s_rest, const float* c_t, int nc, const unsigned char* valid, float* root_out,
                   float* viz_out, tip_stream_t stream) {
-    if (!skel || !carry || kin_bad_slots(n_slots) || count < 0 || kin_bad_rows(n_rows) || (nc != 8 && nc != 20)
+    if (!skel || !carry || tip_bad_count(n_slots) || count < 0 || tip_bad_rows(n_rows) || (nc != 8 && nc != 20)
         || reinterpret_cast<uintptr_t>(carry) % 8)
         return TIP_ERR_INVALID_ARG;
     if (count > 0 && (!begin || !end || !s_rest || !c_t || !root_out || !viz_out)) return TIP_ERR_INVALID_ARG;
@@ -355,7 +274,7 @@ int tip_kin_track(const void* skel, void* carry, int n_slots, const int* slots, 
     hipLaunchKernelGGL(kin_track_kernel, dim3(count), dim3(kn::LANES), 0, static_cast<hipStream_t>(stream),
                        static_cast<const KinSkel*>(skel), static_cast<KinCarry*>(carry), n_slots, slots, begin, end, n_rows, s_rest, c_t,
                        nc, valid, root_out, viz_out);
-    return kin_done();
+    return tip_launch_status();
 }
 
 int tip_kin_metrics(const void* skel, const float* pred_qdq, const float* gt_qdq, const float* pq_pred, const float* pq_gt,
@@ -366,7 +285,7 @@ int tip_kin_metrics(const void* skel, const float* pred_qdq, const float* gt_qdq
     if (count == 0) return TIP_OK;
     hipLaunchKernelGGL(kin_metrics_kernel, dim3(count), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const KinSkel*>(skel), pred_qdq, gt_qdq, pq_pred, pq_gt, offsets, start, end, i2, i5, i10, out);
-    return kin_done();
+    return tip_launch_status();
 }
 
 }  // extern "C"

@@ -377,7 +377,7 @@ static int loss_forward_t(const R* pred, long long ld_pred, const R* gt, long lo
     if (nb > 0)
         hipLaunchKernelGGL(loss_partial_kernel<R>, dim3(nb), dim3(kLossThreads), (size_t)(2 * kLossRows + 3) * W * sizeof(R), st, pred, ld_pred, gt, ld_gt, sh, part);
     hipLaunchKernelGGL(loss_final_kernel<R>, dim3(1), dim3(kLossThreads), 0, st, part, nb, sh, stats);
-    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+    return tip_launch_status();
 }
 
 template <typename R>
@@ -392,7 +392,7 @@ static int loss_backward_t(const R* pred, long long ld_pred, const R* gt, long l
     hipLaunchKernelGGL(loss_grad_kernel<R>, dim3(nb), dim3(kLossThreads),
                        (size_t)(2 * kLossRows + 6) * (sh.n_pose + sh.n_vel + sh.n_sbp4) * sizeof(R), static_cast<hipStream_t>(stream), pred, ld_pred, gt, ld_gt,
                        sh, stats, gout, dpred, ld_dpred);
-    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+    return tip_launch_status();
 }
 
 extern "C" {

@@ -16,7 +16,7 @@
 // workgroup; nothing waits on another workgroup; a slot is written by its own wave only, and a wave writes rows of its own
 // recording only.  Corpus and raw rows are 288 B and 16-byte aligned: one float4 per lane, 18 lanes.  c_t rows (80 / 32 B) move as
 // float4 too; s_rest (444 B) and y_last (524 / 476 B) rows are only 4-byte aligned and move one float per lane.
-#include "tip_internal.h"
+#include "tip_kin_track.h"   // TerHead: the tracked collect reads two counters of a terrain slot's block
 
 namespace tip {
 
@@ -93,7 +93,8 @@ __global__ __launch_bounds__(256) void replay_collect_kernel(long long* __restri
 //                                  when the slot produced a row; while it primes, the row before (root, q_hist, counters), markers at 100,
 //                                  fire 0 — what a terrain post-pass gives for a row that is not valid
 
-constexpr int kTerrainOffMapByte = 1208;                    // include/tip_hip.h, "terrain": off_map, then regions_full
+static_assert(offsetof(TerHead, off_map) == 1208 && offsetof(TerHead, regions_full) == 1212,
+              "include/tip_hip.h, \"terrain\": off_map, then regions_full");
 
 __global__ __launch_bounds__(256) void replay_mask_kernel(const long long* __restrict__ cur, const int* __restrict__ rows_slot, int n_slots,
                                                           unsigned char* __restrict__ mask) {
@@ -120,7 +121,7 @@ __global__ __launch_bounds__(256) void replay_collect_tracked_kernel(
     if (lane < 3) root_out[(size_t)o * 3 + lane] = produced ? t_root[(size_t)slot * 3 + lane] : root_out[(size_t)c * 3 + lane];
     if (lane >= 32 && lane < 34) {
         const int k = lane - 32;
-        const int* words = reinterpret_cast<const int*>(t_state + (size_t)slot * (size_t)t_stride + kTerrainOffMapByte);
+        const int* words = reinterpret_cast<const int*>(t_state + (size_t)slot * (size_t)t_stride + offsetof(TerHead, off_map));
         counters_out[(size_t)o * 2 + k] = produced ? words[k] : counters_out[(size_t)c * 2 + k];
     }
     if (lane == 63) fire_out[o] = (produced && t_fire[slot] >= 0) ? 1 : 0;
@@ -199,7 +200,7 @@ int tip_replay_collect_tracked(long long* cur, const long long* end, int n_slots
     hipLaunchKernelGGL(replay_collect_tracked_kernel, dim3(blocks), dim3(256), 0, static_cast<hipStream_t>(stream), cur, end, n_slots,
                        n_rows, s_rest, c_t, y_slot, rows_slot, size_s, s_out, c_out, y_out, valid, t_root, t_viz, t_q_hist, t_fire,
                        static_cast<const unsigned char*>(t_state), t_stride, root_out, viz_out, q_hist_out, fire_out, counters_out);
-    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+    return tip_launch_status();
 }
 
 }  // extern "C"

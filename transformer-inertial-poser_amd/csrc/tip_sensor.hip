@@ -137,73 +137,71 @@ using namespace tip;
 
 extern "C" {
 
-static int sensor_done() { return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP; }
 static int sensor_blocks(int n_slots) { return (n_slots * sn::SENSORS + 255) / 256; }
-static bool sensor_bad_n(int n_slots) { return n_slots < 0 || n_slots > (1 << 24); }
 
 int tip_sensor_state_bytes(int n_slots, size_t* bytes) {
-    if (!bytes || sensor_bad_n(n_slots)) return TIP_ERR_INVALID_ARG;
+    if (!bytes || tip_bad_count(n_slots)) return TIP_ERR_INVALID_ARG;
     *bytes = (size_t)n_slots * sizeof(SensorCal);
     return TIP_OK;
 }
 
 int tip_sensor_reset(void* cal, int n_slots, tip_stream_t stream) {
-    if (!cal || sensor_bad_n(n_slots) || reinterpret_cast<uintptr_t>(cal) % 8) return TIP_ERR_INVALID_ARG;
+    if (!cal || tip_bad_count(n_slots) || reinterpret_cast<uintptr_t>(cal) % 8) return TIP_ERR_INVALID_ARG;
     if (n_slots == 0) return TIP_OK;
     const size_t words = (size_t)n_slots * sizeof(SensorCal) / 4;
     hipLaunchKernelGGL(sensor_reset_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<unsigned*>(cal), words);
-    return sensor_done();
+    return tip_launch_status();
 }
 
 int tip_sensor_begin(void* cal, int n_slots, const int* slots, int count, int which, tip_stream_t stream) {
-    if (!cal || sensor_bad_n(n_slots) || count < 0 || (count > 0 && !slots) || (which != TIP_SENSOR_HEADING && which != TIP_SENSOR_TPOSE))
+    if (!cal || tip_bad_count(n_slots) || count < 0 || (count > 0 && !slots) || (which != TIP_SENSOR_HEADING && which != TIP_SENSOR_TPOSE))
         return TIP_ERR_INVALID_ARG;
     if (count == 0 || n_slots == 0) return TIP_OK;
     hipLaunchKernelGGL(sensor_begin_kernel, dim3((count + 63) / 64), dim3(64), 0, static_cast<hipStream_t>(stream),
                        static_cast<SensorCal*>(cal), n_slots, slots, count, which);
-    return sensor_done();
+    return tip_launch_status();
 }
 
 int tip_sensor_accumulate(void* cal, const float* packets, int n_slots, tip_stream_t stream) {
-    if (!cal || !packets || sensor_bad_n(n_slots)) return TIP_ERR_INVALID_ARG;
+    if (!cal || !packets || tip_bad_count(n_slots)) return TIP_ERR_INVALID_ARG;
     if (n_slots == 0) return TIP_OK;
     hipLaunchKernelGGL(sensor_accumulate_kernel, dim3(sensor_blocks(n_slots)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<SensorCal*>(cal), packets, n_slots);
-    return sensor_done();
+    return tip_launch_status();
 }
 
 int tip_sensor_finish(void* cal, int n_slots, const int* slots, int count, const double* R_Gp_B0, tip_stream_t stream) {
-    if (!cal || sensor_bad_n(n_slots) || count < 0 || (count > 0 && !slots) || reinterpret_cast<uintptr_t>(R_Gp_B0) % 8)
+    if (!cal || tip_bad_count(n_slots) || count < 0 || (count > 0 && !slots) || reinterpret_cast<uintptr_t>(R_Gp_B0) % 8)
         return TIP_ERR_INVALID_ARG;
     if (count == 0 || n_slots == 0) return TIP_OK;
     hipLaunchKernelGGL(sensor_finish_kernel, dim3(count), dim3(128), 0, static_cast<hipStream_t>(stream), static_cast<SensorCal*>(cal),
                        n_slots, slots, R_Gp_B0);
-    return sensor_done();
+    return tip_launch_status();
 }
 
 int tip_sensor_set(void* cal, int n_slots, const int* slots, int count, const float* tables, tip_stream_t stream) {
-    if (!cal || sensor_bad_n(n_slots) || count < 0 || (count > 0 && (!slots || !tables))) return TIP_ERR_INVALID_ARG;
+    if (!cal || tip_bad_count(n_slots) || count < 0 || (count > 0 && (!slots || !tables))) return TIP_ERR_INVALID_ARG;
     if (count == 0 || n_slots == 0) return TIP_OK;
     hipLaunchKernelGGL(sensor_set_kernel, dim3(count), dim3(128), 0, static_cast<hipStream_t>(stream), static_cast<SensorCal*>(cal),
                        n_slots, slots, tables);
-    return sensor_done();
+    return tip_launch_status();
 }
 
 int tip_sensor_get(const void* cal, int n_slots, const int* slots, int count, float* tables_out, tip_stream_t stream) {
-    if (!cal || sensor_bad_n(n_slots) || count < 0 || (count > 0 && (!slots || !tables_out))) return TIP_ERR_INVALID_ARG;
+    if (!cal || tip_bad_count(n_slots) || count < 0 || (count > 0 && (!slots || !tables_out))) return TIP_ERR_INVALID_ARG;
     if (count == 0 || n_slots == 0) return TIP_OK;
     hipLaunchKernelGGL(sensor_get_kernel, dim3(count), dim3(128), 0, static_cast<hipStream_t>(stream),
                        static_cast<const SensorCal*>(cal), n_slots, slots, tables_out);
-    return sensor_done();
+    return tip_launch_status();
 }
 
 int tip_sensor_transform(const void* cal, const float* packets, int n_slots, float max_acc, float* raw_out, tip_stream_t stream) {
-    if (!cal || !packets || !raw_out || sensor_bad_n(n_slots) || !(max_acc >= 0.f)) return TIP_ERR_INVALID_ARG;
+    if (!cal || !packets || !raw_out || tip_bad_count(n_slots) || !(max_acc >= 0.f)) return TIP_ERR_INVALID_ARG;
     if (n_slots == 0) return TIP_OK;
     hipLaunchKernelGGL(sensor_transform_kernel, dim3(sensor_blocks(n_slots)), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const SensorCal*>(cal), packets, n_slots, max_acc, raw_out);
-    return sensor_done();
+    return tip_launch_status();
 }
 
 }  // extern "C"

@@ -557,7 +557,7 @@ static int launch(K40 k40, KW kw, int blocks, int threads, int window, tip_strea
         hipLaunchKernelGGL(k40, dim3(blocks), dim3(threads), 0, static_cast<hipStream_t>(stream), static_cast<float*>(state), args...);
     else
         hipLaunchKernelGGL(kw, dim3(blocks), dim3(threads), 0, static_cast<hipStream_t>(stream), static_cast<float*>(state), args..., window);
-    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+    return tip_launch_status();
 }
 
 // reset (slots == nullptr: all n_streams, count == n_streams) / attach (the listed slots; shape ignored)
@@ -583,7 +583,7 @@ static int stream_ingest(void* state, const float* raw_imu, int n_streams, int f
     else
         hipLaunchKernelGGL(stream_ingest_w_kernel, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<float*>(state),
                            raw_imu, n_streams, frame_idx, x_imu, x_s, T, rows, slot_at, window);
-    return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP;
+    return tip_launch_status();
 }
 
 // consume: B rows of y.  rows == nullptr: lock step, call call_idx (B == n_streams); otherwise as stream_ingest's, call_idx AUTO

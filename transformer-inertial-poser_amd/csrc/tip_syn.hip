@@ -294,9 +294,6 @@ using namespace tip;
 
 extern "C" {
 
-static int syn_done() { return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP; }
-static bool syn_bad_rows(long long n) { return n < 0 || n > (1LL << 30); }
-static bool syn_bad_count(int n) { return n < 0 || n > (1 << 24); }
 
 int tip_syn_skel_bytes(size_t* bytes) {
     if (!bytes) return TIP_ERR_INVALID_ARG;
@@ -312,7 +309,7 @@ int tip_syn_grid_bytes(size_t* bytes) {
 
 int tip_syn_poses(const void* skel, const double* q, int ldq, const long long* offsets, int count, const double* scale, long long n,
                   double* poses, tip_stream_t stream) {
-    if (!skel || syn_bad_count(count) || syn_bad_rows(n) || ldq < kn::NQ) return TIP_ERR_INVALID_ARG;
+    if (!skel || tip_bad_count(count) || tip_bad_rows(n) || ldq < kn::NQ) return TIP_ERR_INVALID_ARG;
     if (n > 0 && (!q || !offsets || !scale || !poses || count == 0)) return TIP_ERR_INVALID_ARG;
     if (reinterpret_cast<uintptr_t>(skel) % 8 || reinterpret_cast<uintptr_t>(q) % 8 || reinterpret_cast<uintptr_t>(poses) % 8)
         return TIP_ERR_INVALID_ARG;
@@ -323,22 +320,22 @@ int tip_syn_poses(const void* skel, const double* q, int ldq, const long long* o
         return TIP_ERR_HIP;
     hipLaunchKernelGGL(syn_pose_kernel, dim3((unsigned)((n + kn::LANES - 1) / kn::LANES)), dim3(kn::LANES), sy::POSE_LDS,
                        static_cast<hipStream_t>(stream), static_cast<const SynSkel*>(skel), q, ldq, offsets, count, scale, n, poses);
-    return syn_done();
+    return tip_launch_status();
 }
 
 int tip_syn_imu(const double* poses, const long long* offsets, int count, long long n, double* imu, tip_stream_t stream) {
-    if (syn_bad_count(count) || syn_bad_rows(n)) return TIP_ERR_INVALID_ARG;
+    if (tip_bad_count(count) || tip_bad_rows(n)) return TIP_ERR_INVALID_ARG;
     if (n > 0 && (!poses || !offsets || !imu || count == 0)) return TIP_ERR_INVALID_ARG;
     if (reinterpret_cast<uintptr_t>(poses) % 8 || reinterpret_cast<uintptr_t>(imu) % 8) return TIP_ERR_INVALID_ARG;
     if (n == 0) return TIP_OK;
     hipLaunchKernelGGL(syn_imu_kernel, dim3((unsigned)((n * sy::IMUS + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), poses,
                        offsets, count, n, imu);
-    return syn_done();
+    return tip_launch_status();
 }
 
 int tip_syn_sbp(const void* grids, const double* poses, const long long* offsets, int count, long long n, double* frames,
                 double* constrs, tip_stream_t stream) {
-    if (syn_bad_count(count) || syn_bad_rows(n)) return TIP_ERR_INVALID_ARG;
+    if (tip_bad_count(count) || tip_bad_rows(n)) return TIP_ERR_INVALID_ARG;
     if (n > 0 && (!grids || !poses || !offsets || !frames || !constrs || count == 0)) return TIP_ERR_INVALID_ARG;
     if (reinterpret_cast<uintptr_t>(grids) % 8 || reinterpret_cast<uintptr_t>(poses) % 8 || reinterpret_cast<uintptr_t>(constrs) % 8
         || reinterpret_cast<uintptr_t>(frames) % 8)
@@ -352,7 +349,7 @@ int tip_syn_sbp(const void* grids, const double* poses, const long long* offsets
     hipLaunchKernelGGL((syn_sbp_kernel<256, 25>), dim3(count), dim3(256), 0, s, g, 2, 4, 1, offsets, n, frames, constrs);
     hipLaunchKernelGGL((syn_sbp_kernel<256, 7>), dim3(2 * count), dim3(256), 0, s, g, 0, 0, 2, offsets, n, frames, constrs);
     hipLaunchKernelGGL((syn_sbp_kernel<64, 2>), dim3(2 * count), dim3(64), 0, s, g, 1, 2, 2, offsets, n, frames, constrs);
-    return syn_done();
+    return tip_launch_status();
 }
 
 }  // extern "C"

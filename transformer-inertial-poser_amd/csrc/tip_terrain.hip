@@ -36,7 +36,7 @@
 // fp32 FK are used as they are where the reference's Q2R would normalise them (a difference below the fp32 FK's own rounding).
 //
 // Kernels:
-//   terrain_reset_kernel   one workgroup per listed slot: the carry as kin_reset_kernel sets it, RTRunner.__init__'s state, and the
+//   terrain_reset_kernel   one workgroup per listed slot: the carry (carry_init, as kin_reset_kernel's), RTRunner.__init__'s state, and the
 //                          only pass over a whole map
 //   terrain_track_kernel   one wave per sequence: 64 rows of FK in parallel, then the wave steps through those rows with every lane
 //                          holding the same scan state (the same fp64 statements on the same values), so that the patch — the region
@@ -44,7 +44,10 @@
 //                          lane 0's; region heights and the map go through memory with a workgroup barrier between writer and reader.
 //
 // Nothing waits on another workgroup; a slot's block is written only by the wave whose sequence names it.
-#include "tip_kin_fk.h"
+//
+// The first half of a frame — root_pre, the SBP locations, the residues, the nanmean and the clip — the scan state and the carry's
+// initialisation are tip_kin_track.h's, shared with tip_kin.hip's tracker; so are TerHead and ter_lay, which tip_replay.hip reads.
+#include "tip_kin_track.h"
 
 namespace tip {
 
@@ -53,30 +56,6 @@ constexpr int MAX_D = 16, MAX_GRID = 4096, MAX_REGIONS = 65535, TICK_LEN = 50;  
 constexpr unsigned D2_INIT = 10000;                                                   // confidence -100 (:120)
 constexpr double EPS_H = 0.1, FORCE = 20.0, PELVIS = 0.2, W0 = 10.0, IK_LO = 0.05, IK_HI = 0.5;      // :138, :124, :125, :122, :358, :353
 }  // namespace tr
-
-// One slot's block: this head, region_height[max_regions], region_weight[max_regions] (fp64), the map [grid_num, grid_num].
-struct TerHead {
-    KinCarry carry;
-    double c_prev[kn::SBPS][3];  // c_locs_prev
-    double ik_delta[2][3];       // ik_target_deltas of lankle, rankle
-    int tick[3];                 // establishing_height_phase_tick of lankle, rankle, root
-    int n_regions;
-    int off_map, regions_full;
-    int grid_num, max_regions;   // as the reset laid the block out
-    int pad[14];
-};
-static_assert(sizeof(TerHead) == 1280, "TerHead layout");
-
-struct TerLay {
-    size_t off_w, off_map, stride;
-};
-__host__ __device__ __forceinline__ TerLay ter_lay(int G, int M) {
-    TerLay l;
-    l.off_w = sizeof(TerHead) + (size_t)M * 8;
-    l.off_map = l.off_w + (size_t)M * 8;
-    l.stride = (l.off_map + (size_t)G * G * 4 + 7) & ~(size_t)7;
-    return l;
-}
 
 // The leg chains of the table: body indices of hip, knee, ankle and of the hip's parent, and the columns of s_rest the three joints
 // occupy; ok = three spherical links below a parent.
@@ -121,11 +100,8 @@ __global__ __launch_bounds__(256) void terrain_reset_kernel(const KinSkel* __res
     double* rw = reinterpret_cast<double*>(blk + lay.off_w);
     unsigned* map = reinterpret_cast<unsigned*>(blk + lay.off_map);
     const float* row = s_init + (size_t)j * kn::QDQ;
-    if (t == 0) {                                                   // the carry, as kin_reset_kernel sets it
-        fk_frames(sk, L, row + 3, 0.f, 0.f, 0.f, Fs);
-        fk_to_com(sk, L, Fs);
-        for (int k = 0; k < 3; ++k) h.carry.root[k] = (double)row[k], h.carry.vprev[k] = 0.f;
-        h.carry.has_prev = 0;
+    if (t == 0) {
+        carry_init(sk, L, h.carry, row, Fs);
         for (int i = 0; i < kn::SBPS; ++i)
             for (int k = 0; k < 3; ++k) h.c_prev[i][k] = 100.0;     // :53-54
         for (int i = 0; i < 2; ++i)
@@ -135,15 +111,14 @@ __global__ __launch_bounds__(256) void terrain_reset_kernel(const KinSkel* __res
         for (int i = 0; i < 14; ++i) h.pad[i] = 0;
     }
     __syncthreads();
-    for (int e = t; e < kn::MAX_BODIES * 7; e += 256) h.carry.pq[e] = e < (L + 1) * 7 ? Fs[e * kn::COL] : 0.f;
+    carry_init_pq(h.carry, Fs, L, t, 256);
+    for (int e = (L + 1) * 7 + t; e < kn::MAX_BODIES * 7; e += 256) h.carry.pq[e] = 0.f;      // (the whole block is defined after a reset)
     for (int e = t; e < 15; e += 256) h.carry.pad[e] = 0;
     for (int e = t; e < M; e += 256) rh[e] = 0.0, rw[e] = e == 0 ? tr::W0 : 0.0;      // :121-122
     const size_t cells = (lay.stride - lay.off_map) / 4;
     for (size_t e = t; e < cells; e += 256) map[e] = tr::D2_INIT;   // region 0, confidence -100 (:119-120)
 }
 
-// np.clip(v, -m, m): a NaN stays a NaN
-__device__ __forceinline__ double ter_clip(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ double ter_norm3(const double* v) { return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
 __device__ __forceinline__ bool ter_active(const double* c) { return ter_norm3(c) < 100.0; }      // is_c_loc_active (:19-21); false for a NaN
 __device__ __forceinline__ bool ter_all_nan(const double* v) { return v[0] != v[0] && v[1] != v[1] && v[2] != v[2]; }
@@ -156,9 +131,8 @@ __device__ __forceinline__ void ter_unit(const double* v, double* o) {
     o[0] = v[0] / n, o[1] = v[1] / n, o[2] = v[2] / n;
 }
 __device__ __forceinline__ double ter_angle(const double* a, const double* b) {
-    return acos(ter_clip(a[0] * b[0] + a[1] * b[1] + a[2] * b[2], -1.0, 1.0));
+    return acos(kin_clip(a[0] * b[0] + a[1] * b[1] + a[2] * b[2], -1.0, 1.0));
 }
-__device__ __forceinline__ void ter_conj(const double* q, double* o) { o[0] = -q[0], o[1] = -q[1], o[2] = -q[2], o[3] = q[3]; }
 // scipy's Rotation.from_quat(q).as_rotvec()
 __device__ __forceinline__ void ter_q2a(const double* qi, double* a) {
     const double n = sqrt(qi[0] * qi[0] + qi[1] * qi[1] + qi[2] * qi[2] + qi[3] * qi[3]);
@@ -180,8 +154,8 @@ __device__ __forceinline__ void ter_q2a(const double* qi, double* a) {
 __device__ void ter_leg_ik(const double* a, const double* b, const double* c, const double* qpa, const double* qa, const double* qb,
                            const double* qc, const double* c_delta, double* aa_out) {
     double pinv[4], qainv[4], target[3], ba[3], cb[3], ca[3], ta[3], ab[3];
-    ter_conj(qpa, pinv);
-    ter_conj(qa, qainv);
+    kin_conj(qpa, pinv);
+    kin_conj(qa, qainv);
     for (int k = 0; k < 3; ++k) {
         target[k] = c[k] + c_delta[k];
         ba[k] = b[k] - a[k], cb[k] = c[k] - b[k], ca[k] = c[k] - a[k], ab[k] = a[k] - b[k];
@@ -189,14 +163,14 @@ __device__ void ter_leg_ik(const double* a, const double* b, const double* c, co
     for (int k = 0; k < 3; ++k) ta[k] = target[k] - a[k];
     const double eps = 0.01;
     const double lab = ter_norm3(ba), lcb = ter_norm3(cb);
-    const double lat = ter_clip(ter_norm3(ta), eps, lab + lcb - eps);
+    const double lat = kin_clip(ter_norm3(ta), eps, lab + lcb - eps);
     double n_ca[3], n_ba[3], n_ab[3], n_cb[3], n_ta[3];
     ter_unit(ca, n_ca), ter_unit(ba, n_ba), ter_unit(ab, n_ab), ter_unit(cb, n_cb), ter_unit(ta, n_ta);
     const double ac_ab_0 = ter_angle(n_ca, n_ba);
     const double ba_bc_0 = ter_angle(n_ab, n_cb);
     const double ac_at_0 = ter_angle(n_ca, n_ta);
-    const double ac_ab_1 = acos(ter_clip((lcb * lcb - lab * lab - lat * lat) / (-2.0 * lab * lat), -1.0, 1.0));
-    const double ba_bc_1 = acos(ter_clip((lat * lat - lab * lab - lcb * lcb) / (-2.0 * lab * lcb), -1.0, 1.0));
+    const double ac_ab_1 = acos(kin_clip((lcb * lcb - lab * lab - lat * lat) / (-2.0 * lab * lat), -1.0, 1.0));
+    const double ba_bc_1 = acos(kin_clip((lat * lat - lab * lab - lcb * lcb) / (-2.0 * lab * lcb), -1.0, 1.0));
     const double up[3] = {0.0, 0.0, 1.0};
     double d[3], x0[3], x1[3], ax0g[3], ax1g[3], ax0l[3], ax1l[3];
     qrot<double>(qa, up, d);
@@ -219,7 +193,7 @@ __device__ void ter_leg_ik(const double* a, const double* b, const double* c, co
     qmul<double>(b_l, r1, b_l1);
     qmul<double>(qpa, a_l1, a_g1);
     qmul<double>(a_g1, b_l1, b_g1);
-    ter_conj(b_g1, b_g1inv);
+    kin_conj(b_g1, b_g1inv);
     qmul<double>(b_g1inv, qc, c_l1);
     ter_q2a(a_l1, aa_out), ter_q2a(b_l1, aa_out + 3), ter_q2a(c_l1, aa_out + 6);
 }
@@ -309,13 +283,9 @@ __global__ __launch_bounds__(64) void terrain_track_kernel(const KinSkel* __rest
     __shared__ float Js[18 * kn::COL];                              // link-frame positions of hip, knee, ankle of both legs
     const KinSkel& sk = *skp;
     const int L = kin_links(sk), lane = threadIdx.x, per = (L + 1) * 7;
-    const int seq = blockIdx.x;
-    const int slot = slots ? slots[seq] : seq;
-    if (slot < 0 || slot >= n_slots) return;                      // (uniform over the wave: every return below is)
-    long long r0 = begin[seq], r1 = end[seq];
-    if (r0 < 0) r0 = 0;
-    if (r1 > n_rows) r1 = n_rows;
-    if (r1 <= r0) return;
+    int slot;
+    long long r0, r1;
+    if (!track_range(slots, begin, end, blockIdx.x, n_slots, n_rows, slot, r0, r1)) return;      // (uniform over the wave: every return is)
     const TerLay lay = ter_lay(G, M);
     unsigned char* blk = state + (size_t)slot * lay.stride;
     TerHead& hd = *reinterpret_cast<TerHead*>(blk);
@@ -327,21 +297,15 @@ __global__ __launch_bounds__(64) void terrain_track_kernel(const KinSkel* __rest
     const int n_sbps = nc / 4;
     const bool multi = (flags & 1) != 0;
     int body[kn::SBPS];
-    for (int i = 0; i < kn::SBPS; ++i) body[i] = (sk.sbp[i] < 0 || sk.sbp[i] > L) ? 0 : sk.sbp[i];
+    sbp_bodies(sk, L, body);
     const TerChain chain[2] = {ter_chain(sk, L, body[0]), ter_chain(sk, L, body[1])};
-    const int rb[3] = {0, 1, 4};                                  // the SBPs whose residues are read: the feet, and the root for the IK
     float* F = Fs + lane;
 
-    // the scan state, the same in every lane
-    double root[3], delta[2][3];
-    float x1r[3][3], q1[3][4], vprev[3];
-    int has_prev = cr.has_prev;
+    // the scan state, the same in every lane: the residues read are the feet's and, for the IK, the root's
+    SbpScan<3> st;
+    double delta[2][3];
     TerScan s;
-    for (int k = 0; k < 3; ++k) root[k] = cr.root[k], vprev[k] = cr.vprev[k];
-    for (int m = 0; m < 3; ++m) {
-        for (int k = 0; k < 3; ++k) x1r[m][k] = cr.pq[7 * body[rb[m]] + k];
-        for (int k = 0; k < 4; ++k) q1[m][k] = cr.pq[7 * body[rb[m]] + 3 + k];
-    }
+    sbp_scan_load(st, cr, body);
     for (int i = 0; i < kn::SBPS; ++i)
         for (int k = 0; k < 3; ++k) s.cp[i][k] = hd.c_prev[i][k];
     for (int i = 0; i < 2; ++i)
@@ -373,63 +337,14 @@ __global__ __launch_bounds__(64) void terrain_track_kernel(const KinSkel* __rest
             const float* sr = s_rest + row * kn::REST;
             if (valid && !valid[row]) {                              // what the runner returns while it primes: the carry's root, 100s
                 for (int k = 0; k < 3; ++k)
-                    if (lane == k) ro[k] = (float)root[k];
+                    if (lane == k) ro[k] = (float)st.root[k];
                 if (lane < 15) vo[lane] = 100.f;
                 if (lane < 54) q_hist[row * 54 + lane] = sr[lane];
                 if (lane == 0) fire_out[row] = -1;
                 continue;
             }
-            const float* ct = c_t + row * nc;
-            const double nan = __builtin_nan("");
-            double pre[3], cl[kn::SBPS][3], res[3][3];
-            for (int k = 0; k < 3; ++k) {                            // :441, on the velocity from before the averaging (:447-448)
-                const double v = has_prev ? 2.0 * (double)sr[54 + k] - (double)vprev[k] : (double)sr[54 + k];
-                pre[k] = root[k] + v * kn::DT;
-            }
-            for (int i = 0; i < kn::SBPS; ++i)
-                for (int k = 0; k < 3; ++k) cl[i][k] = 100.0;
-            for (int m = 0; m < 3; ++m)
-                for (int k = 0; k < 3; ++k) res[m][k] = nan;
-#pragma unroll
-            for (int i = 0; i < kn::SBPS; ++i) {
-                if (i >= n_sbps || ct[4 * i] == 0.f) continue;       // inactive: location 100, residue NaN
-                const int bd = body[i];
-                double x2[3], sol[3];
-                for (int k = 0; k < 3; ++k) {
-                    x2[k] = (double)Fs[(7 * bd + k) * kn::COL + j] + pre[k];
-                    sol[k] = (double)ct[4 * i + 1 + k];
-                    cl[i][k] = x2[k] + sol[k];
-                }
-                const int m = i < 2 ? i : (i == 4 ? 2 : -1);
-                if (m < 0) continue;                                 // the wrists' residues are read by nobody
-                double q2[4], dq[4], sq[4], sub[4], cj[4], dori[4];
-                double nd = 0.0, ns = 0.0;
-                for (int k = 0; k < 4; ++k) {
-                    q2[k] = (double)Fs[(7 * bd + 3 + k) * kn::COL + j];
-                    dq[k] = q2[k] - (double)q1[m][k], sq[k] = q2[k] + (double)q1[m][k];
-                    nd += dq[k] * dq[k], ns += sq[k] * sq[k];
-                }
-                const bool minus = sqrt(nd) < sqrt(ns);
-                for (int k = 0; k < 4; ++k) sub[k] = minus ? dq[k] : sq[k];
-                ter_conj(q2, cj);
-                qmul<double>(sub, cj, dori);
-                double w[3], v[3];
-                for (int k = 0; k < 3; ++k) {
-                    w[k] = 2.0 * dori[k] / kn::DT;
-                    v[k] = (x2[k] - ((double)x1r[m][k] + root[k])) / kn::DT;
-                }
-                res[m][0] = (w[1] * sol[2] - w[2] * sol[1]) + v[0];
-                res[m][1] = (w[2] * sol[0] - w[0] * sol[2]) + v[1];
-                res[m][2] = (w[0] * sol[1] - w[1] * sol[0]) + v[2];
-            }
-            const bool none = ter_all_nan(res[0]) && ter_all_nan(res[1]);
-            double vr[3];
-            for (int k = 0; k < 3; ++k) {
-                if (none) { vr[k] = 0.0; continue; }
-                const bool a = res[0][k] == res[0][k], b = res[1][k] == res[1][k];      // np.nanmean over the two feet
-                const double m = a && b ? (res[0][k] + res[1][k]) / 2.0 : (a ? res[0][k] : (b ? res[1][k] : nan));
-                vr[k] = ter_clip(m, -0.5, 0.5);
-            }
+            double pre[3], cl[kn::SBPS][3], res[3][3], vr[3];
+            sbp_step<3>(st, body, sr, c_t + row * nc, n_sbps, Fs, j, pre, cl, res, vr);      // :441-461
             vr[2] = 0.0;                                             // the terrain corrects the height, not the SBPs (:462)
             for (int i = 0; i < kn::SBPS; ++i)
                 for (int k = 0; k < 3; ++k) cl[i][k] = cl[i][k] - vr[k] * kn::DT;      // :463, the inactive 100s included
@@ -437,10 +352,10 @@ __global__ __launch_bounds__(64) void terrain_track_kernel(const KinSkel* __rest
             for (int ti = 0; ti < 3; ++ti) {
                 if (s.tick[ti] < 0) continue;
                 s.tick[ti] -= 1;
-                if (!ter_active(cl[rb[ti]]) && ter_active(s.cp[rb[ti]])) s.tick[ti] = 0;
+                if (!ter_active(cl[sbp_of_res(ti)]) && ter_active(s.cp[sbp_of_res(ti)])) s.tick[ti] = 0;
             }
             for (int ti = 0; ti < 2; ++ti) {                         // :467-472
-                const double d = terrain_update(s, rh, rw, map, G, M, D, gs, rb[ti], ti, lane);
+                const double d = terrain_update(s, rh, rw, map, G, M, D, gs, sbp_of_res(ti), ti, lane);
                 vr[2] += -d * tr::FORCE;
             }
             if (multi) {
@@ -489,9 +404,9 @@ __global__ __launch_bounds__(64) void terrain_track_kernel(const KinSkel* __rest
                 }
             }
             // :489-496
-            for (int k = 0; k < 3; ++k) root[k] = pre[k] - vr[k] * kn::DT;
+            for (int k = 0; k < 3; ++k) st.root[k] = pre[k] - vr[k] * kn::DT;
             for (int k = 0; k < 3; ++k)
-                if (lane == k) ro[k] = (float)root[k];
+                if (lane == k) ro[k] = (float)st.root[k];
             for (int i = 0; i < kn::SBPS; ++i)
                 for (int k = 0; k < 3; ++k)
                     if (lane == 3 * i + k) vo[3 * i + k] = (float)cl[i][k];
@@ -507,21 +422,14 @@ __global__ __launch_bounds__(64) void terrain_track_kernel(const KinSkel* __rest
             if (lane == 0) fire_out[row] = (fired[0] || fired[1]) ? slot : -1;
             for (int i = 0; i < kn::SBPS; ++i)
                 for (int k = 0; k < 3; ++k) s.cp[i][k] = cl[i][k];
-            for (int m = 0; m < 3; ++m) {
-                for (int k = 0; k < 3; ++k) x1r[m][k] = Fs[(7 * body[rb[m]] + k) * kn::COL + j];
-                for (int k = 0; k < 4; ++k) q1[m][k] = Fs[(7 * body[rb[m]] + 3 + k) * kn::COL + j];
-            }
-            for (int k = 0; k < 3; ++k) vprev[k] = sr[54 + k];
-            has_prev = 1;
+            sbp_advance(st, body, sr, Fs, j);
             last = j;
         }
-        if (last >= 0)
-            for (int e = lane; e < per; e += kn::LANES) cr.pq[e] = Fs[e * kn::COL + last];
+        carry_store_pq(cr, Fs, per, last, lane);
         __syncthreads();
     }
     if (lane == 0) {
-        for (int k = 0; k < 3; ++k) cr.root[k] = root[k], cr.vprev[k] = vprev[k];
-        cr.has_prev = has_prev;
+        sbp_scan_store(st, cr);
         for (int i = 0; i < kn::SBPS; ++i)
             for (int k = 0; k < 3; ++k) hd.c_prev[i][k] = s.cp[i][k];
         for (int i = 0; i < 2; ++i)
@@ -537,9 +445,8 @@ using namespace tip;
 
 extern "C" {
 
-static int ter_done() { return hipGetLastError() == hipSuccess ? TIP_OK : TIP_ERR_HIP; }
 static bool ter_bad_shape(int n_slots, int grid_num, int max_regions) {
-    return n_slots < 0 || n_slots > (1 << 24) || grid_num < 2 || grid_num > tr::MAX_GRID || max_regions < 1 || max_regions > tr::MAX_REGIONS;
+    return tip_bad_count(n_slots) || grid_num < 2 || grid_num > tr::MAX_GRID || max_regions < 1 || max_regions > tr::MAX_REGIONS;
 }
 
 int tip_terrain_state_bytes(int n_slots, int grid_num, int max_regions, size_t* bytes) {
@@ -557,14 +464,14 @@ int tip_terrain_reset(const void* skel, void* state, int n_slots, int grid_num, 
     hipLaunchKernelGGL(terrain_reset_kernel, dim3(count), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const KinSkel*>(skel), static_cast<unsigned char*>(state), n_slots, grid_num, max_regions, slots, count,
                        s_init);
-    return ter_done();
+    return tip_launch_status();
 }
 
 int tip_terrain_track(const void* skel, void* state, int n_slots, int grid_num, int max_regions, int diffuse_region, double grid_size,
                       const int* slots, const long long* begin, const long long* end, int count, long long n_rows, const float* s_rest,
                       const float* c_t, int nc, const unsigned char* valid, int flags, float* root_out, float* viz_out,
                       float* q_hist_out, int* fire_out, tip_stream_t stream) {
-    if (!skel || !state || ter_bad_shape(n_slots, grid_num, max_regions) || count < 0 || n_rows < 0 || n_rows > (1LL << 30)
+    if (!skel || !state || ter_bad_shape(n_slots, grid_num, max_regions) || count < 0 || tip_bad_rows(n_rows)
         || (nc != 8 && nc != 20) || reinterpret_cast<uintptr_t>(state) % 8 || diffuse_region < 1 || diffuse_region > tr::MAX_D
         || !(grid_size > 0.0) || !(grid_size < 1e6) || (flags & ~1) || ((flags & 1) && nc != 20))
         return TIP_ERR_INVALID_ARG;
@@ -573,7 +480,7 @@ int tip_terrain_track(const void* skel, void* state, int n_slots, int grid_num, 
     hipLaunchKernelGGL(terrain_track_kernel, dim3(count), dim3(kn::LANES), 0, static_cast<hipStream_t>(stream),
                        static_cast<const KinSkel*>(skel), static_cast<unsigned char*>(state), n_slots, grid_num, max_regions, diffuse_region,
                        grid_size, slots, begin, end, n_rows, s_rest, c_t, nc, valid, flags, root_out, viz_out, q_hist_out, fire_out);
-    return ter_done();
+    return tip_launch_status();
 }
 
 }  // extern "C"

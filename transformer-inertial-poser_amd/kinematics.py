@@ -238,31 +238,51 @@ def fk(skel: Skeleton, q, out_jf: bool = False, device=None):
 
 
 # ---- the root track ------------------------------------------------------------------------------------------------------------------
-class _Carry:
-    """n carry blocks on a device (tip_kin_carry_bytes) and the launches on them."""
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+class _Blocks:
+    """n state blocks on a device with the skeleton beside them, and the reset and track launches on them.  A subclass sizes the
+    buffer (_alloc) and names the two entry points (looked up in the loaded library at every launch, so that a wrapper somebody puts
+    around one there sees the call), what they take behind (skel, blocks, n) and what track takes behind `valid`."""
+    _reset_fn = _track_fn = None
+    _reset_args = _track_args = _track_tail = ()
 
     def __init__(self, skel, n, device):
-        import torch
         self.skel, self.n, self.device = skel, int(n), _device(device)
+
+    def _alloc(self, bytes_fn, *shape):
+        import torch
         self.tlib, self.lib = _lib()
         nbytes = ctypes.c_size_t()
-        _check(self.lib.tip_kin_carry_bytes(self.n, ctypes.byref(nbytes)))
+        _check(getattr(self.lib, bytes_fn)(self.n, *shape, ctypes.byref(nbytes)))
         with torch.cuda.device(self.device):
             self.buf = torch.zeros(max(nbytes.value, 8), dtype=torch.uint8, device=self.device)
-            self.sk = skel.on(self.device)
+            self.sk = self.skel.on(self.device)
+        return nbytes.value
 
     def reset(self, slots_dev, count, s_init_dev):
         import torch
         with torch.cuda.device(self.device):
-            _check(self.lib.tip_kin_track_reset(self.sk.data_ptr(), self.buf.data_ptr(), self.n, None if slots_dev is None else slots_dev.data_ptr(),
-                                                count, s_init_dev.data_ptr(), _stream(self.device)))
+            _check(getattr(self.lib, self._reset_fn)(self.sk.data_ptr(), self.buf.data_ptr(), self.n, *self._reset_args, _ptr(slots_dev), count,
+                                  s_init_dev.data_ptr(), _stream(self.device)))
 
-    def track(self, slots_dev, begin_ptr, end_ptr, count, s_rest, c_t, valid, root, viz):
+    def track(self, slots_dev, begin_ptr, end_ptr, count, s_rest, c_t, valid, *outs):
         import torch
         with torch.cuda.device(self.device):
-            _check(self.lib.tip_kin_track(self.sk.data_ptr(), self.buf.data_ptr(), self.n, None if slots_dev is None else slots_dev.data_ptr(),
-                                          begin_ptr, end_ptr, count, int(s_rest.shape[0]), s_rest.data_ptr(), c_t.data_ptr(), int(c_t.shape[1]),
-                                          None if valid is None else valid.data_ptr(), root.data_ptr(), viz.data_ptr(), _stream(self.device)))
+            _check(getattr(self.lib, self._track_fn)(self.sk.data_ptr(), self.buf.data_ptr(), self.n, *self._track_args, _ptr(slots_dev), begin_ptr, end_ptr,
+                                  count, int(s_rest.shape[0]), s_rest.data_ptr(), c_t.data_ptr(), int(c_t.shape[1]), _ptr(valid),
+                                  *self._track_tail, *(o.data_ptr() for o in outs), _stream(self.device)))
+
+
+class _Carry(_Blocks):
+    """n carry blocks on a device (tip_kin_carry_bytes) and the launches on them."""
+    _reset_fn, _track_fn = "tip_kin_track_reset", "tip_kin_track"
+
+    def __init__(self, skel, n, device):
+        super().__init__(skel, n, device)
+        self._alloc("tip_kin_carry_bytes")
 
 
 def _track_inputs(s_rest, c_t, valid, device, who):
@@ -280,37 +300,51 @@ def _track_inputs(s_rest, c_t, valid, device, who):
     return s, c, valid
 
 
+def _track_ragged(mod, who, s_init, s_rest, c_t, valid, offsets, device, chunk, make, check_width=None):
+    """track and track_terrain behind their outputs: the inputs onto the device and checked (s_rest [N, 111], c_t [N, 8 | 20], valid [N],
+    offsets [R + 1], s_init as [R, 114]), then make(N, R) — the caller's state object of R blocks and the tuple of its output tensors —
+    then the reset and the track of every sequence, in one launch or, with chunk=k, k rows of every sequence per launch.  Returns what
+    make returned."""
+    import torch
+    s, c, v = _track_inputs(s_rest, c_t, valid, device, who)
+    if check_width is not None:
+        check_width(c)
+    o = _offsets(offsets, int(s.shape[0]), who)
+    R = o.shape[0] - 1
+    s0 = _dev_f32(s_init if np.ndim(s_init) == 2 else np.asarray(s_init)[None], device, (114,), who, "s_init")
+    if s0.shape[0] != R:
+        raise ValueError(f"tip_amd.{mod}.{who}: s_init is [R, 114] with one row per sequence ({R}); got {tuple(s0.shape)}")
+    st, outs = make(int(s.shape[0]), R)
+    if R == 0 or s.shape[0] == 0:
+        return st, outs
+    st.reset(None, R, s0)
+    if chunk is None:
+        od = torch.from_numpy(o).pin_memory().to(device, non_blocking=True)
+        st.track(None, od.data_ptr(), od.data_ptr() + 8, R, s, c, v, *outs)
+    else:
+        k = int(chunk)
+        if k < 1:
+            raise ValueError(f"tip_amd.{mod}.{who}: chunk is a number of rows, at least 1; got {chunk!r}")
+        for first in range(0, int(np.diff(o).max()), k):
+            be = np.stack([np.minimum(o[:-1] + first, o[1:]), np.minimum(o[:-1] + first + k, o[1:])])
+            bd = torch.from_numpy(be).pin_memory().to(device, non_blocking=True)
+            st.track(None, bd[0].data_ptr(), bd[1].data_ptr(), R, s, c, v, *outs)
+    return st, outs
+
+
 def track(skel: Skeleton, s_init, s_rest, c_t, valid, offsets, device=None, chunk=None):
     """R sequences back to back: s_init [R, 114], s_rest [N, 111], c_t [N, 8 | 20], valid [N] bool, offsets [R + 1] ->
     root [N, 3], viz_locs [N, 5, 3] (CUDA float32): the rows of RTRunnerMin.step's qdq[:3] and viz_locs, one kernel for the lot.
     chunk=k runs it k rows of every sequence per launch instead, through the carry: the same bits, for whoever gets rows in pieces."""
     import torch
     device = _device(device)
+
+    def make(n, R):
+        return _Carry(skel, R, device), (torch.empty((n, 3), dtype=torch.float32, device=device),
+                                         torch.empty((n, 5, 3), dtype=torch.float32, device=device))
+
     with torch.cuda.device(device):
-        s, c, v = _track_inputs(s_rest, c_t, valid, device, "track")
-        o = _offsets(offsets, int(s.shape[0]), "track")
-        R = o.shape[0] - 1
-        s0 = _dev_f32(s_init if np.ndim(s_init) == 2 else np.asarray(s_init)[None], device, (114,), "track", "s_init")
-        if s0.shape[0] != R:
-            raise ValueError(f"tip_amd.kinematics.track: s_init is [R, 114] with one row per sequence ({R}); got {tuple(s0.shape)}")
-        root = torch.empty((s.shape[0], 3), dtype=torch.float32, device=device)
-        viz = torch.empty((s.shape[0], 5, 3), dtype=torch.float32, device=device)
-        if R == 0 or s.shape[0] == 0:
-            return root, viz
-        carry = _Carry(skel, R, device)
-        carry.reset(None, R, s0)
-        if chunk is None:
-            od = torch.from_numpy(o).pin_memory().to(device, non_blocking=True)
-            carry.track(None, od.data_ptr(), od.data_ptr() + 8, R, s, c, v, root, viz)
-        else:
-            k = int(chunk)
-            if k < 1:
-                raise ValueError(f"tip_amd.kinematics.track: chunk is a number of rows, at least 1; got {chunk!r}")
-            for first in range(0, int(np.diff(o).max()), k):
-                be = np.stack([np.minimum(o[:-1] + first, o[1:]), np.minimum(o[:-1] + first + k, o[1:])])
-                bd = torch.from_numpy(be).pin_memory().to(device, non_blocking=True)
-                carry.track(None, bd[0].data_ptr(), bd[1].data_ptr(), R, s, c, v, root, viz)
-    return root, viz
+        return _track_ragged("kinematics", "track", s_init, s_rest, c_t, valid, offsets, device, chunk, make)[1]
 
 
 def track_replay(skel: Skeleton, results: Sequence, s_init, device=None, terrain=None) -> List[tuple]:
@@ -357,33 +391,30 @@ def track_replay(skel: Skeleton, results: Sequence, s_init, device=None, terrain
     return out
 
 
-class RootTracker:
-    """The live form: n carry blocks beside an engine of n slots.
-        rt = RootTracker(skel, engine.n, engine.device)
-        rt.reset(None, s_init)                 # with the engine's s_init; reset(slots, rows) whenever the engine attaches those slots
-        out = engine.step(frame)
-        root, viz_locs = rt.step(out)          # [n, 3], [n, 5, 3]: this frame's qdq[:3] and viz_locs by slot (tensors reused every frame)
-    step() is ONE launch on the current stream (call it on the engine's stream, after step; it is not part of the engine's captured
-    graph).  out=None — a lock-step engine that is still priming — launches nothing and returns the rows as they stand.  Rows whose
-    out["valid"] is False, and slots left out of `slots`, keep their carry; the former read (carry root, 100s)."""
+class _Tracker:
+    """What RootTracker and tip_amd.terrain.TerrainTracker share: n state blocks (self._s) beside an engine of n slots, the per-slot output
+    tensors self._outs (root and viz_locs first), the slot lists on the device, reset and step.  _mod, _name and _slot_who make the
+    messages."""
+    _mod = _name = _slot_who = None
 
-    def __init__(self, skel: Skeleton, n: int, device):
+    def __init__(self, n, make_state):
         import torch
         self.n = int(n)
         if self.n < 1:
-            raise ValueError(f"tip_amd.kinematics.RootTracker: n is the number of slots, at least 1; got {n!r}")
-        self._c = _Carry(skel, self.n, device)
-        self.device = self._c.device
+            raise ValueError(f"tip_amd.{self._mod}.{self._name}: n is the number of slots, at least 1; got {n!r}")
+        self._s = make_state(self.n)
+        self.device = self._s.device
         with torch.cuda.device(self.device):
             self.root = torch.zeros((self.n, 3), dtype=torch.float32, device=self.device)
             self.viz_locs = torch.full((self.n, 5, 3), 100.0, dtype=torch.float32, device=self.device)
             self._rows = torch.arange(self.n + 1, dtype=torch.int64, device=self.device)
+        self._outs = (self.root, self.viz_locs)
         self._lists = {}
 
     def _slot_tensors(self, slots, who):
         import torch
         from .streaming import slot_list
-        idx = tuple(slot_list(slots, self.n, f"RootTracker.{who}"))
+        idx = tuple(slot_list(slots, self.n, f"{self._slot_who}.{who}"))
         if idx not in self._lists:
             with torch.cuda.device(self.device):
                 a = np.array(idx, dtype=np.int64)
@@ -392,8 +423,16 @@ class RootTracker:
                                     host.to(self.device, non_blocking=True))
         return idx, self._lists[idx]
 
+    def _reset_rows(self, rows):
+        """The per-slot output rows of freshly reset slots, beyond root and viz_locs."""
+
+    def _check_width(self, c):
+        """step's check of c_t's width, where the tracker has one."""
+
+    def _before_subset_step(self):
+        """What a step on a subset of the slots does to the output rows first."""
+
     def reset(self, slots, s_init_rows):
-        """The listed slots (None: all) start over from s_init_rows [len(slots), 114]: root = s_init[:3], pq_prev = FK(s_init)."""
         import torch
         with torch.cuda.device(self.device):
             if slots is None:
@@ -402,14 +441,15 @@ class RootTracker:
                 idx, (sl, _) = self._slot_tensors(slots, "reset")
                 count = len(idx)
             s0 = _dev_f32(s_init_rows if np.ndim(s_init_rows) == 2 else np.asarray(s_init_rows)[None], self.device, (114,),
-                          "RootTracker.reset", "s_init_rows")
+                          f"{self._name}.reset", "s_init_rows")
             if s0.shape[0] != count:
-                raise ValueError(f"tip_amd.kinematics.RootTracker.reset: s_init_rows is [{count}, 114]; got {tuple(s0.shape)}")
+                raise ValueError(f"tip_amd.{self._mod}.{self._name}.reset: s_init_rows is [{count}, 114]; got {tuple(s0.shape)}")
             if count:
-                self._c.reset(sl, count, s0)
+                self._s.reset(sl, count, s0)
                 rows = slice(None) if sl is None else sl.long()
                 self.root[rows] = s0[:, :3]
                 self.viz_locs[rows] = 100.0
+                self._reset_rows(rows)
 
     def step(self, out, slots=None):
         import torch
@@ -417,16 +457,37 @@ class RootTracker:
             return self.root, self.viz_locs
         s, c, v = out["s_rest"], out["c_t"], out.get("valid")
         if tuple(s.shape) != (self.n, 111) or s.device != self.device or c.shape[0] != self.n or not s.is_contiguous() or not c.is_contiguous():
-            raise ValueError(f"tip_amd.kinematics.RootTracker.step: out is an engine's frame of {self.n} slots on {self.device}")
+            raise ValueError(f"tip_amd.{self._mod}.{self._name}.step: out is an engine's frame of {self.n} slots on {self.device}")
         if v is not None and not (isinstance(v, torch.Tensor) and v.dtype in (torch.bool, torch.uint8) and v.shape == (self.n,)):
-            raise ValueError("tip_amd.kinematics.RootTracker.step: out['valid'] is a bool tensor [n]")
+            raise ValueError(f"tip_amd.{self._mod}.{self._name}.step: out['valid'] is a bool tensor [n]")
+        self._check_width(c)
         if slots is None:
-            self._c.track(None, self._rows.data_ptr(), self._rows.data_ptr() + 8, self.n, s, c, v, self.root, self.viz_locs)
+            self._s.track(None, self._rows.data_ptr(), self._rows.data_ptr() + 8, self.n, s, c, v, *self._outs)
         else:
             idx, (sl, be) = self._slot_tensors(slots, "step")
+            self._before_subset_step()
             if idx:
-                self._c.track(sl, be[0].data_ptr(), be[1].data_ptr(), len(idx), s, c, v, self.root, self.viz_locs)
+                self._s.track(sl, be[0].data_ptr(), be[1].data_ptr(), len(idx), s, c, v, *self._outs)
         return self.root, self.viz_locs
+
+
+class RootTracker(_Tracker):
+    """The live form: n carry blocks beside an engine of n slots.
+        rt = RootTracker(skel, engine.n, engine.device)
+        rt.reset(None, s_init)                 # with the engine's s_init; reset(slots, rows) whenever the engine attaches those slots
+        out = engine.step(frame)
+        root, viz_locs = rt.step(out)          # [n, 3], [n, 5, 3]: this frame's qdq[:3] and viz_locs by slot (tensors reused every frame)
+    step() is ONE launch on the current stream (call it on the engine's stream, after step; it is not part of the engine's captured
+    graph).  out=None — a lock-step engine that is still priming — launches nothing and returns the rows as they stand.  Rows whose
+    out["valid"] is False, and slots left out of `slots`, keep their carry; the former read (carry root, 100s)."""
+    _mod, _name, _slot_who = "kinematics", "RootTracker", "RootTracker"
+
+    def __init__(self, skel: Skeleton, n: int, device):
+        super().__init__(n, lambda n: _Carry(skel, n, device))
+
+    def reset(self, slots, s_init_rows):
+        """The listed slots (None: all) start over from s_init_rows [len(slots), 114]: root = s_init[:3], pq_prev = FK(s_init)."""
+        super().reset(slots, s_init_rows)
 
 
 # ---- the seven metrics ---------------------------------------------------------------------------------------------------------------

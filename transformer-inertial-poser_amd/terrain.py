@@ -27,12 +27,11 @@ the ground truth instead of the model and runs the same tail: it is track_terrai
 reference never calls."""
 from __future__ import annotations
 
-import ctypes
 from typing import Sequence
 
 import numpy as np
 
-from .kinematics import Skeleton, _check, _dev_f32, _device, _lib, _offsets, _stream, _track_inputs
+from .kinematics import Skeleton, _Blocks, _Tracker, _device, _track_ragged
 
 HEAD_BYTES = 1280                   # include/tip_hip.h, "terrain": the block's fixed part
 
@@ -81,12 +80,12 @@ class TerrainState:
         return self.region_height[np.minimum(self.region_map, self.n_regions - 1)]
 
 
-class _State:
+class _State(_Blocks):
     """n blocks on a device (tip_terrain_state_bytes) and the launches on them."""
+    _reset_fn, _track_fn = "tip_terrain_reset", "tip_terrain_track"
 
     def __init__(self, skel, n, device, map_bound, grid_size, multi_sbp, max_regions, who):
-        import torch
-        self.skel, self.n, self.device = skel, int(n), _device(device)
+        super().__init__(skel, n, device)
         self.grid_size = float(grid_size)
         if not (self.grid_size > 0 and float(map_bound) > 0):
             raise ValueError(f"tip_amd.terrain.{who}: map_bound and grid_size are lengths in metres, above 0; got {map_bound!r}, {grid_size!r}")
@@ -99,29 +98,8 @@ class _State:
         self.flags = 1 if multi_sbp else 0
         if multi_sbp and not _leg_chains_ok(skel):
             raise ValueError(f"tip_amd.terrain.{who}: multi_sbp needs both ankles below three spherical links (hip, knee, ankle)")
-        self.tlib, self.lib = _lib()
-        nbytes = ctypes.c_size_t()
-        _check(self.lib.tip_terrain_state_bytes(self.n, self.G, self.M, ctypes.byref(nbytes)))
-        self.stride = nbytes.value // max(self.n, 1)
-        with torch.cuda.device(self.device):
-            self.buf = torch.zeros(max(nbytes.value, 8), dtype=torch.uint8, device=self.device)
-            self.sk = skel.on(self.device)
-
-    def reset(self, slots_dev, count, s_init_dev):
-        import torch
-        with torch.cuda.device(self.device):
-            _check(self.lib.tip_terrain_reset(self.sk.data_ptr(), self.buf.data_ptr(), self.n, self.G, self.M,
-                                              None if slots_dev is None else slots_dev.data_ptr(), count, s_init_dev.data_ptr(),
-                                              _stream(self.device)))
-
-    def track(self, slots_dev, begin_ptr, end_ptr, count, s_rest, c_t, valid, root, viz, q_hist, fire):
-        import torch
-        with torch.cuda.device(self.device):
-            _check(self.lib.tip_terrain_track(self.sk.data_ptr(), self.buf.data_ptr(), self.n, self.G, self.M, self.D, self.grid_size,
-                                              None if slots_dev is None else slots_dev.data_ptr(), begin_ptr, end_ptr, count,
-                                              int(s_rest.shape[0]), s_rest.data_ptr(), c_t.data_ptr(), int(c_t.shape[1]),
-                                              None if valid is None else valid.data_ptr(), self.flags, root.data_ptr(), viz.data_ptr(),
-                                              q_hist.data_ptr(), fire.data_ptr(), _stream(self.device)))
+        self.stride = self._alloc("tip_terrain_state_bytes", self.G, self.M) // max(self.n, 1)
+        self._reset_args, self._track_args, self._track_tail = (self.G, self.M), (self.G, self.M, self.D, self.grid_size), (self.flags,)
 
     def view(self, slot: int) -> TerrainState:
         slot = int(slot)
@@ -164,38 +142,19 @@ def track_terrain(skel: Skeleton, s_init, s_rest, c_t, valid, offsets, map_bound
     for the lot.  chunk=k runs it k rows of every sequence per launch instead, through the state: the same bits."""
     import torch
     device = _device(device)
+
+    def make(n, R):
+        return (_State(skel, R, device, map_bound, grid_size, multi_sbp, max_regions, "track_terrain"),
+                (torch.empty((n, 3), dtype=torch.float32, device=device), torch.empty((n, 5, 3), dtype=torch.float32, device=device),
+                 torch.empty((n, 54), dtype=torch.float32, device=device), torch.full((n,), -1, dtype=torch.int32, device=device)))
+
     with torch.cuda.device(device):
-        s, c, v = _track_inputs(s_rest, c_t, valid, device, "track_terrain")
-        _check_width(c, multi_sbp, "track_terrain")
-        o = _offsets(offsets, int(s.shape[0]), "track_terrain")
-        R = o.shape[0] - 1
-        s0 = _dev_f32(s_init if np.ndim(s_init) == 2 else np.asarray(s_init)[None], device, (114,), "track_terrain", "s_init")
-        if s0.shape[0] != R:
-            raise ValueError(f"tip_amd.terrain.track_terrain: s_init is [R, 114] with one row per sequence ({R}); got {tuple(s0.shape)}")
-        n = int(s.shape[0])
-        root = torch.empty((n, 3), dtype=torch.float32, device=device)
-        viz = torch.empty((n, 5, 3), dtype=torch.float32, device=device)
-        q_hist = torch.empty((n, 54), dtype=torch.float32, device=device)
-        fire = torch.full((n,), -1, dtype=torch.int32, device=device)
-        st = _State(skel, R, device, map_bound, grid_size, multi_sbp, max_regions, "track_terrain")
-        if R == 0 or n == 0:
-            return root, viz, q_hist, fire, TerrainStates(st)
-        st.reset(None, R, s0)
-        if chunk is None:
-            od = torch.from_numpy(o).pin_memory().to(device, non_blocking=True)
-            st.track(None, od.data_ptr(), od.data_ptr() + 8, R, s, c, v, root, viz, q_hist, fire)
-        else:
-            k = int(chunk)
-            if k < 1:
-                raise ValueError(f"tip_amd.terrain.track_terrain: chunk is a number of rows, at least 1; got {chunk!r}")
-            for first in range(0, int(np.diff(o).max()), k):
-                be = np.stack([np.minimum(o[:-1] + first, o[1:]), np.minimum(o[:-1] + first + k, o[1:])])
-                bd = torch.from_numpy(be).pin_memory().to(device, non_blocking=True)
-                st.track(None, bd[0].data_ptr(), bd[1].data_ptr(), R, s, c, v, root, viz, q_hist, fire)
-    return root, viz, q_hist, fire, TerrainStates(st)
+        st, outs = _track_ragged("terrain", "track_terrain", s_init, s_rest, c_t, valid, offsets, device, chunk, make,
+                                 lambda c: _check_width(c, multi_sbp, "track_terrain"))
+    return (*outs, TerrainStates(st))
 
 
-class TerrainTracker:
+class TerrainTracker(_Tracker):
     """The live form: n blocks beside an engine of n slots.
         tt = TerrainTracker(skel, engine.n, engine.device, map_bound=5.0, grid_size=0.1, multi_sbp=True)
         tt.reset(None, s_init)                 # with the engine's s_init; reset(slots, rows) whenever the engine attaches those slots
@@ -206,76 +165,33 @@ class TerrainTracker:
     graph).  out=None — a lock-step engine that is still priming — launches nothing.  Rows whose out["valid"] is False keep their
     state and read (the state's root, 100s, fire -1).  With a `slots` subset the slots left out keep their state too, and their fire
     entries are set to -1 first (one fill more), so that feed_back never repeats an old correction."""
+    _mod, _name, _slot_who = "terrain", "TerrainTracker", "terrain.TerrainTracker"
 
     def __init__(self, skel: Skeleton, n: int, device, map_bound: float = 5.0, grid_size: float = 0.1, multi_sbp: bool = False,
                  max_regions: int = 64):
         import torch
-        self.n = int(n)
-        if self.n < 1:
-            raise ValueError(f"tip_amd.terrain.TerrainTracker: n is the number of slots, at least 1; got {n!r}")
-        self._s = _State(skel, self.n, device, map_bound, grid_size, multi_sbp, max_regions, "TerrainTracker")
-        self.device, self.multi_sbp = self._s.device, bool(multi_sbp)
+        super().__init__(n, lambda n: _State(skel, n, device, map_bound, grid_size, multi_sbp, max_regions, "TerrainTracker"))
+        self.multi_sbp = bool(multi_sbp)
         with torch.cuda.device(self.device):
-            self.root = torch.zeros((self.n, 3), dtype=torch.float32, device=self.device)
-            self.viz_locs = torch.full((self.n, 5, 3), 100.0, dtype=torch.float32, device=self.device)
             self.q_hist = torch.zeros((self.n, 54), dtype=torch.float32, device=self.device)
             self.fire = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
-            self._rows = torch.arange(self.n + 1, dtype=torch.int64, device=self.device)
-        self._lists = {}
-
-    def _slot_tensors(self, slots, who):
-        import torch
-        from .streaming import slot_list
-        idx = tuple(slot_list(slots, self.n, f"terrain.TerrainTracker.{who}"))
-        if idx not in self._lists:
-            with torch.cuda.device(self.device):
-                a = np.array(idx, dtype=np.int64)
-                host = torch.from_numpy(np.stack([a, a + 1])).pin_memory()
-                self._lists[idx] = (torch.from_numpy(a.astype(np.int32)).pin_memory().to(self.device, non_blocking=True),
-                                    host.to(self.device, non_blocking=True))
-        return idx, self._lists[idx]
+        self._outs += (self.q_hist, self.fire)
 
     def reset(self, slots, s_init_rows):
         """The listed slots (None: all) start over from s_init_rows [len(slots), 114], as RTRunner.__init__ starts: root = s_init[:3],
         pq_prev = FK(s_init), an empty map."""
+        super().reset(slots, s_init_rows)
+
+    def _reset_rows(self, rows):
+        self.fire[rows] = -1
+
+    def _check_width(self, c):
+        _check_width(c, self.multi_sbp, "TerrainTracker.step")
+
+    def _before_subset_step(self):
         import torch
         with torch.cuda.device(self.device):
-            if slots is None:
-                count, sl = self.n, None
-            else:
-                idx, (sl, _) = self._slot_tensors(slots, "reset")
-                count = len(idx)
-            s0 = _dev_f32(s_init_rows if np.ndim(s_init_rows) == 2 else np.asarray(s_init_rows)[None], self.device, (114,),
-                          "TerrainTracker.reset", "s_init_rows")
-            if s0.shape[0] != count:
-                raise ValueError(f"tip_amd.terrain.TerrainTracker.reset: s_init_rows is [{count}, 114]; got {tuple(s0.shape)}")
-            if count:
-                self._s.reset(sl, count, s0)
-                rows = slice(None) if sl is None else sl.long()
-                self.root[rows] = s0[:, :3]
-                self.viz_locs[rows] = 100.0
-                self.fire[rows] = -1
-
-    def step(self, out, slots=None):
-        import torch
-        if out is None:
-            return self.root, self.viz_locs
-        s, c, v = out["s_rest"], out["c_t"], out.get("valid")
-        if tuple(s.shape) != (self.n, 111) or s.device != self.device or c.shape[0] != self.n or not s.is_contiguous() or not c.is_contiguous():
-            raise ValueError(f"tip_amd.terrain.TerrainTracker.step: out is an engine's frame of {self.n} slots on {self.device}")
-        if v is not None and not (isinstance(v, torch.Tensor) and v.dtype in (torch.bool, torch.uint8) and v.shape == (self.n,)):
-            raise ValueError("tip_amd.terrain.TerrainTracker.step: out['valid'] is a bool tensor [n]")
-        _check_width(c, self.multi_sbp, "TerrainTracker.step")
-        if slots is None:
-            self._s.track(None, self._rows.data_ptr(), self._rows.data_ptr() + 8, self.n, s, c, v, self.root, self.viz_locs, self.q_hist,
-                          self.fire)
-        else:
-            idx, (sl, be) = self._slot_tensors(slots, "step")
-            with torch.cuda.device(self.device):
-                self.fire.fill_(-1)
-            if idx:
-                self._s.track(sl, be[0].data_ptr(), be[1].data_ptr(), len(idx), s, c, v, self.root, self.viz_locs, self.q_hist, self.fire)
-        return self.root, self.viz_locs
+            self.fire.fill_(-1)
 
     def feed_back(self, engine):
         """The pose the IK corrected on this frame into `engine`'s history, for the slots it fired on; nothing is read by the host."""
