@@ -722,6 +722,35 @@ TIP_API int tip_syn_imu(const double* poses /* [n,8,7] */, const long long* offs
 TIP_API int tip_syn_sbp(const void* grids, const double* poses /* [n,8,7] */, const long long* offsets /* [count+1] */, int count,
                 long long n, double* frames /* [n,5,15] scratch */, double* constrs /* [n,20] */, tip_stream_t stream);
 
+/* ---- motion: SMPL pose sequences -> nimble_qdq — the ground-truth half of the reference's preprocessing (data_utils.py:103-161
+ *      get_raw_motion_info_nimble_q_dummy_dq over dip_loader.py:101-183, the root augmentation of preprocess_DIP_TC_new.py:98-107 and
+ *      fairmotion's Motion.get_pose_by_time), for `count` ragged sequences held back to back, fp64, one launch.  It produces what
+ *      tip_syn_poses and tip_combine_sequence consume (tip_amd.motion.qdq_from_smpl).  An offline producer beside the engines.
+ *      Source sequence j is rows in_offsets[j] .. in_offsets[j + 1] - 1 of poses[n_in, ldp >= 66] (one axis-angle per SMPL joint, joints
+ *      0 .. 21 read) and of trans[n_in, 3], at fps[j] frames per second; its output is rows out_offsets[j] .. out_offsets[j + 1] - 1 of
+ *      qdq[n_out, 114].  in_offsets, out_offsets [count + 1], fps [count], has_trans [count] are DEVICE arrays.  A sequence has `trans`
+ *      when trans is not null and has_trans is null or has_trans[j] != 0: its root is (A2R(pose[0:3]), trans[frame]); otherwise it is
+ *      (rot_up_R A2R(pose[0:3]), (0, 0, 0.95)), rot_up_R = Q2R((.5, .5, .5, .5)) (constants.py:21-23).
+ *      times [n_times] (device): t_0 = 0.0075, t_{k+1} = t_k + 1/60 as the HOST's running fp64 sum (np.cumsum: the reference's loop to
+ *      the bit; the device never regenerates it).  Output row k of a sequence of n frames is taken at t_k, and exists while
+ *      t_k < (n - 1) / fps — the caller sizes out_offsets by that rule.  The pose at a time: time clipped to [0, (n - 1) / fps],
+ *      frame1 = int(time fps + 1e-5), frame2 = min(frame1 + 1, n - 1); frame1 == frame2: that frame; else alpha = clip((time -
+ *      frame1 / fps) / (frame2 / fps - frame1 / fps), 0, 1), each rotation R1 A2R(alpha R2A(R1^T R2)), the root position linear.
+ *      Row k: root p (0:3), root axis-angle (3:6), the 17 spherical joints' axis-angles (6:57; joints[18] (device int): the SMPL joint
+ *      of the root, then of output columns 6, 9, ..., 54), v = (p(t_k + 1/60) - p) 60 (57:60), w = R2A(R^T R(t_k + 1/60)) 60 (60:63),
+ *      zeros (63:114).  Every column of every row is written.  Axis-angles are rotation-vector logarithms with angle in [0, pi],
+ *      taken through a quaternion (Shepperd, atan2).  A NaN or infinite source value makes what reads it NaN; rows that cannot be
+ *      addressed (offsets outside the arrays, k >= n_times, fps <= 0, a joint outside 0 .. 21) are NaN, never an access outside.
+ *      One lane per (row, slot): root, 17 joints, root at t + 1/60; tip_motion_tile answers the rows and slots of a workgroup.
+ *      Negative counts, ldp < 66, misaligned buffers and null pointers with non-zero counts return TIP_ERR_INVALID_ARG before any
+ *      launch; count = 0 or n_out = 0 returns TIP_OK without one. */
+TIP_API int tip_motion_tile(int* rows, int* slots);
+TIP_API int tip_motion_qdq(const double* poses /* [n_in,ldp] */, int ldp, const double* trans /* [n_in,3] or null */,
+                   const int* has_trans /* [count] or null */, const long long* in_offsets /* [count+1] */,
+                   const long long* out_offsets /* [count+1] */, const double* fps /* [count] */, int count, long long n_in,
+                   long long n_out, const double* times /* [n_times] */, long long n_times, const int* joints /* [18] */,
+                   double* qdq /* [n_out,114] */, tip_stream_t stream);
+
 /* ---- exact streaming reuse: tip_forward for lock-stepped streams whose windows slide by one frame per call.
  *      In the runner a frame's model inputs never change once recorded (real_time_runner_minimal.py:74,85,137: raw_imu_buffer,
  *      s_and_c_in_buffer and imu_acc_sum_buffer are append-only), so with the stochastic parts off — past_state_dropout = 0, in_dropout = 0,

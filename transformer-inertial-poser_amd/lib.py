@@ -52,6 +52,7 @@ EXPORTS = (
     "tip_kin_skel_bytes", "tip_kin_carry_bytes", "tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_kin_metrics",
     "tip_terrain_state_bytes", "tip_terrain_reset", "tip_terrain_track",
     "tip_syn_skel_bytes", "tip_syn_grid_bytes", "tip_syn_poses", "tip_syn_imu", "tip_syn_sbp",
+    "tip_motion_tile", "tip_motion_qdq",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
     "tip_train_bytes_f64", "tip_train_forward_f64", "tip_train_backward_f64",
     "tip_combine_frames", "tip_combine_scratch_bytes", "tip_combine_sequence", "tip_gather_windows",
@@ -222,6 +223,9 @@ def load() -> ctypes.CDLL:
     lib.tip_syn_poses.argtypes = [vp, vp, i32, vp, i32, vp, ctypes.c_longlong, vp, vp]
     lib.tip_syn_imu.argtypes = [vp, vp, i32, ctypes.c_longlong, vp, vp]
     lib.tip_syn_sbp.argtypes = [vp, vp, vp, i32, ctypes.c_longlong, vp, vp, vp]
+    # motion (csrc/tip_motion.hip): the source arrays and their stride, the ragged layout, the time and joint tables, the output, the stream
+    lib.tip_motion_tile.argtypes = [ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    lib.tip_motion_qdq.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, ctypes.c_longlong, ctypes.c_longlong, vp, ctypes.c_longlong, vp, vp, vp]
     u64 = ctypes.c_ulonglong
     f32 = ctypes.c_float
     lib.tip_train_bytes.argtypes = [vp, i32, i32, ctypes.POINTER(sz), ctypes.POINTER(sz)]

@@ -16,7 +16,7 @@ into each pickle once per corpus); with the generator on the device it can be re
 `nimble_qdq` is passed through as the caller gave it, unscaled, as the reference stores it.
 
 An offline producer beside the engines, like tip_amd.kinematics: it touches no engine, graph or other kernel.  The ankle-IMU variant
-(USE_KNEE_RATHER_ANKLE_IMU = False) and the loading of AMASS files into nimble_qdq are not here."""
+(USE_KNEE_RATHER_ANKLE_IMU = False) is not here; the loading of AMASS files into nimble_qdq is tip_amd.motion (syn_files chains the two)."""
 from __future__ import annotations
 
 from typing import List, Sequence
