@@ -629,6 +629,35 @@ TIP_API int tip_kin_metrics(const void* skel, const float* pred_qdq, const float
                     const long long* offsets /* [count+1] */, int count, int start, int end, int i2, int i5, int i10,
                     double* out /* [count,7] */, tip_stream_t stream);
 
+/* ---- kinematics, per-wearer body scale: the entries above for wearers of different body sizes.  The reference builds its character
+ *      with scale = h / 1.6 (data-gen-and-viz-bullet-new.py:256-257; bullet_agent.py:47,67: PyBullet's globalScaling), and
+ *      RTRunnerMin / RTRunner run on the character they are given.  For a wearer of scale s EVERY LINK'S joint_xyz AND com_xyz IS
+ *      MULTIPLIED BY s BEFORE IT IS ROTATED, and nothing else is scaled: not the root xyz of q / s_init / the root accumulator (the
+ *      wearer's metres already; tip_syn_poses scales the root too because it puts a reference motion on a scaled agent — the trackers
+ *      must not), not the r vectors of c_t, not DT, the +-0.5 clip, the 0.2 m pelvis test, the IK thresholds, the map's bound, grid
+ *      size or region epsilons.  Each entry takes what its unscaled form takes and, in front of the stream, `scale` (fp32, device):
+ *        the FK entry: one entry PER ROW, so that rows of many wearers share a launch without a search;
+ *        the reset and track entries: [n_slots], indexed by the BLOCK a sequence uses (slots[j], or j when slots is null), read once
+ *        per sequence per launch.  The scale is not kept in the carry: the caller passes the same array to the reset and to every
+ *        track, and changes an entry only together with a reset of that block (the carry's pq_prev was computed with it).
+ *      A scale that is not finite or not above 0 makes its own rows NaN — pose tables; root_out, viz_out (and q_hist_out; fire_out -1)
+ *      of the rows begin[j] .. end[j] - 1 — writes nothing to that block, the map included (a reset leaves its root NaN), touches no
+ *      other sequence and still returns TIP_OK.  A null `scale` is TIP_ERR_INVALID_ARG.  The unscaled entries are unchanged, to the
+ *      instruction: the scaled kernels are instantiations of their own (SCALED, csrc/tip_kin_fk.h), never a multiply by 1.
+ *      (Declared with the name on a line of its own: the one-line declarations above are each family's unscaled surface.) */
+TIP_API int
+tip_kin_fk_scaled(const void* skel, const float* q /* [n,ldq] */, int ldq, long long n, float* pq_g /* [n,L+1,7] */,
+                  float* pq_jf /* [n,L+1,7] or null */, const float* scale /* [n] */, tip_stream_t stream);
+TIP_API int
+tip_kin_track_reset_scaled(const void* skel, void* carry, int n_slots, const int* slots /* [count] or null */, int count,
+                           const float* s_init /* [count,114] */, const float* scale /* [n_slots], by block */, tip_stream_t stream);
+TIP_API int
+tip_kin_track_scaled(const void* skel, void* carry, int n_slots, const int* slots /* [count] or null */, const long long* begin,
+                     const long long* end, int count, long long n_rows, const float* s_rest /* [n_rows,111] */,
+                     const float* c_t /* [n_rows,nc] */, int nc, const unsigned char* valid /* [n_rows] or null */,
+                     float* root_out /* [n_rows,3] */, float* viz_out /* [n_rows,5,3] */,
+                     const float* scale /* [n_slots], by block */, tip_stream_t stream);
+
 /* ---- terrain: the full runner's tail — what RTRunner.step does behind the model (real_time_runner.py:451-496): the tracker above with
  *      the per-stream height-region map (:140-262), the "establishing height" ticks (:264-277), the vertical root correction from the
  *      map, and the two-joint leg IK (:334-382; data_utils.py:556-630) whose pose is fed back into the history.  A CONSUMER beside the
@@ -678,6 +707,22 @@ TIP_API int tip_terrain_track(const void* skel, void* state, int n_slots, int gr
                       const unsigned char* valid /* [n_rows] or null */, int flags, float* root_out /* [n_rows,3] */,
                       float* viz_out /* [n_rows,5,3] */, float* q_hist_out /* [n_rows,54] */, int* fire_out /* [n_rows] */,
                       tip_stream_t stream);
+
+/* ---- terrain, per-wearer body scale: tip_terrain_reset and tip_terrain_track for wearers of different body sizes, by the rule of
+ *      "kinematics, per-wearer body scale" above: the FK of every row — the poses the residues are taken on, the pelvis test's, the link
+ *      frames the leg IK solves on — is the wearer's, and nothing else is scaled.  The block's layout and every byte offset are the
+ *      unscaled ones: the scale is not stored. */
+TIP_API int
+tip_terrain_reset_scaled(const void* skel, void* state, int n_slots, int grid_num, int max_regions,
+                         const int* slots /* [count] or null */, int count, const float* s_init /* [count,114] */,
+                         const float* scale /* [n_slots], by block */, tip_stream_t stream);
+TIP_API int
+tip_terrain_track_scaled(const void* skel, void* state, int n_slots, int grid_num, int max_regions, int diffuse_region,
+                         double grid_size, const int* slots /* [count] or null */, const long long* begin, const long long* end,
+                         int count, long long n_rows, const float* s_rest /* [n_rows,111] */, const float* c_t /* [n_rows,nc] */,
+                         int nc, const unsigned char* valid /* [n_rows] or null */, int flags, float* root_out /* [n_rows,3] */,
+                         float* viz_out /* [n_rows,5,3] */, float* q_hist_out /* [n_rows,54] */, int* fire_out /* [n_rows] */,
+                         const float* scale /* [n_slots], by block */, tip_stream_t stream);
 
 /* ---- synthetic data: IMU readings and stationary-body-point (SBP) labels from pose sequences — the reference's offline generator
  *      (data-gen-and-viz-bullet-new.py:44-218 over data_utils.py:27-100 get_rot_center_sample_based; bullet_agent.py for the scale),

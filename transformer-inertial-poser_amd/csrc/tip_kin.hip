@@ -20,6 +20,10 @@
 //   kin_track_kernel    one wave per sequence: 64 rows of FK in parallel (root at the origin: FK does not depend on the root, and the
 //                       scan only ever adds a root to a pose), then lane 0 steps through those rows in fp64, then the next 64
 //   kin_metrics_kernel  one workgroup per file over the two FK'd trajectories, fp64 sums, a fixed-order tree reduction
+// The first three are templates over (SCALED, S...): SCALED = true is the kernel for wearers of different body sizes — every joint and
+// COM offset times the wearer's scale before it is rotated (tip_kin_fk.h), the scale read from a device array, one entry per row in
+// FK, one per block (slot) in the reset and the tracker — behind the *_scaled entries of tip_kin_scaled.hip.  The metrics need no
+// such form: they read the pose tables, which the scaled FK makes.
 //
 // PRECISION.  FK is fp32.  The scan — root accumulator, residues, clip, z rule — is fp64 on the fp32 poses, and the carry keeps the
 // root as fp64; outputs are rounded to fp32 once.  The metrics are fp64 on the fp32 poses.
@@ -29,6 +33,9 @@
 // The scan's frame — root_pre, the SBP locations, the residues, the nanmean and the clip — the scan state's load, advance and store,
 // and the carry's initialisation are tip_kin_track.h's: one body for this tracker and for tip_terrain.hip's.  What is written out
 // below is this tracker's own: the flat-ground z rule and the shift of the outputs.
+// SCALED = true is instantiated in a translation unit of its own (tip_kin_scaled.hip, which includes this file for the templates and
+// defines TIP_KIN_SCALED_TU), so that the unscaled kernels are compiled alone, as they were before there was a scale: with both in
+// one unit the inliner's choices for the unscaled ones moved (make resource-usage showed scratch where there was none).
 #include "tip_kin_track.h"   // sbp_step and the carry; over tip_kin_fk.h: KinLinkT, a2q, qmul, qrot, fk_frames, fk_to_com, one body for
                              // fp32 (here) and fp64 (tip_syn.hip), KinSkel, KinCarry and the fp32 FK wrappers
 
@@ -43,8 +50,10 @@ __device__ __forceinline__ void fk_store(const float* F, int per, long long firs
     }
 }
 
+// SCALED: `scale` has one entry per row, so rows of many wearers share a launch; a row whose scale kin_scale_ok refuses is NaN whole.
+template <bool SCALED, typename... S>
 __global__ __launch_bounds__(64) void kin_fk_kernel(const KinSkel* __restrict__ skp, const float* __restrict__ q, int ldq, long long n,
-                                                    float* __restrict__ pq_g, float* __restrict__ pq_jf) {
+                                                    float* __restrict__ pq_g, float* __restrict__ pq_jf, S... scale) {
     __shared__ float Fs[kn::MAX_BODIES * 7 * kn::COL];
     const KinSkel& sk = *skp;
     const int L = kin_links(sk), lane = threadIdx.x, per = (L + 1) * 7;
@@ -52,20 +61,29 @@ __global__ __launch_bounds__(64) void kin_fk_kernel(const KinSkel* __restrict__ 
     const long long left = n - first;
     const int cnt = left < kn::LANES ? (int)left : kn::LANES;
     float* F = Fs + lane;
+    float sc = 1.f;
+    bool ok = true;
+    if constexpr (SCALED)
+        if (lane < cnt) sc = kin_scale_ptr(scale...)[first + lane], ok = kin_scale_ok(sc);
     if (lane < cnt) {
         const float* row = q + (size_t)(first + lane) * ldq;
-        fk_frames(sk, L, row + 3, row[0], row[1], row[2], F);
+        if (ok) fk_frames_of<SCALED>(sk, L, row + 3, row[0], row[1], row[2], sc, F);
+        else
+            for (int e = 0; e < per; ++e) F[e * kn::COL] = __builtin_nanf("");
     }
     __syncthreads();
     if (pq_jf) fk_store(Fs, per, first, cnt, pq_jf, lane);
     __syncthreads();
-    if (lane < cnt) fk_to_com(sk, L, F);
+    if (lane < cnt && ok) fk_to_com_of<SCALED>(sk, L, sc, F);
     __syncthreads();
     fk_store(Fs, per, first, cnt, pq_g, lane);
 }
 
+// SCALED: `scale` is indexed by the block (slot), as the track kernel reads it.
+template <bool SCALED, typename... S>
 __global__ __launch_bounds__(64) void kin_reset_kernel(const KinSkel* __restrict__ skp, KinCarry* __restrict__ carry, int n_slots,
-                                                       const int* __restrict__ slots, int count, const float* __restrict__ s_init) {
+                                                       const int* __restrict__ slots, int count, const float* __restrict__ s_init,
+                                                       S... scale) {
     __shared__ float Fs[kn::MAX_BODIES * 7 * kn::COL];
     const KinSkel& sk = *skp;
     const int L = kin_links(sk), lane = threadIdx.x;
@@ -73,16 +91,21 @@ __global__ __launch_bounds__(64) void kin_reset_kernel(const KinSkel* __restrict
     if (j >= count) return;
     const int slot = slots ? slots[j] : j;
     if (slot < 0 || slot >= n_slots) return;
-    carry_init(sk, L, carry[slot], s_init + (size_t)j * kn::QDQ, Fs + lane);
+    const float* row = s_init + (size_t)j * kn::QDQ;
+    if constexpr (SCALED) carry_init<true>(sk, L, carry[slot], row, Fs + lane, kin_scale_ptr(scale...)[slot]);
+    else carry_init(sk, L, carry[slot], row, Fs + lane);
     carry_init_pq(carry[slot], Fs + lane, L, 0, 1);
 }
 
+// SCALED: the sequence's body scale is scale[slot], read once per launch; one that kin_scale_ok refuses makes the sequence's rows NaN and
+// leaves its carry alone.
+template <bool SCALED, typename... S>
 __global__ __launch_bounds__(64) void kin_track_kernel(const KinSkel* __restrict__ skp, KinCarry* __restrict__ carry, int n_slots,
                                                        const int* __restrict__ slots, const long long* __restrict__ begin,
                                                        const long long* __restrict__ end, long long n_rows,
                                                        const float* __restrict__ s_rest, const float* __restrict__ c_t, int nc,
                                                        const unsigned char* __restrict__ valid, float* __restrict__ root_out,
-                                                       float* __restrict__ viz_out) {
+                                                       float* __restrict__ viz_out, S... scale) {
     __shared__ float Fs[kn::MAX_BODIES * 7 * kn::COL];
     __shared__ int last_s;
     const KinSkel& sk = *skp;
@@ -91,6 +114,16 @@ __global__ __launch_bounds__(64) void kin_track_kernel(const KinSkel* __restrict
     long long r0, r1;
     if (!track_range(slots, begin, end, blockIdx.x, n_slots, n_rows, slot, r0, r1)) return;      // (uniform over the wave)
     KinCarry& cr = carry[slot];
+    float sc = 1.f;
+    if constexpr (SCALED) {
+        sc = kin_scale_ptr(scale...)[slot];
+        if (!kin_scale_ok(sc)) {                                      // (uniform over the wave)
+            const float nanf = __builtin_nanf("");
+            for (long long e = r0 * 3 + lane; e < r1 * 3; e += kn::LANES) root_out[e] = nanf;
+            for (long long e = r0 * 15 + lane; e < r1 * 15; e += kn::LANES) viz_out[e] = nanf;
+            return;
+        }
+    }
     const int n_sbps = nc / 4;
     int body[kn::SBPS];
     sbp_bodies(sk, L, body);
@@ -103,8 +136,8 @@ __global__ __launch_bounds__(64) void kin_track_kernel(const KinSkel* __restrict
         const int cnt = left < kn::LANES ? (int)left : kn::LANES;
         if (lane == 0) last_s = -1;
         if (lane < cnt && (!valid || valid[t0 + lane])) {
-            fk_frames(sk, L, s_rest + (size_t)(t0 + lane) * kn::REST, 0.f, 0.f, 0.f, F);
-            fk_to_com(sk, L, F);
+            fk_frames_of<SCALED>(sk, L, s_rest + (size_t)(t0 + lane) * kn::REST, 0.f, 0.f, 0.f, sc, F);
+            fk_to_com_of<SCALED>(sk, L, sc, F);
         }
         __syncthreads();
         if (lane == 0) {
@@ -142,6 +175,7 @@ __global__ __launch_bounds__(64) void kin_track_kernel(const KinSkel* __restrict
     if (lane == 0) sbp_scan_store(st, cr);
 }
 
+#ifndef TIP_KIN_SCALED_TU
 // fixed-order sum of one double per thread over a 256-thread workgroup
 __device__ __forceinline__ double block_sum(double v, double* sh, int t) {
     __syncthreads();
@@ -227,8 +261,11 @@ __global__ __launch_bounds__(256) void kin_metrics_kernel(const KinSkel* __restr
     }
 }
 
+#endif  // TIP_KIN_SCALED_TU
+
 }  // namespace tip
 
+#ifndef TIP_KIN_SCALED_TU
 using namespace tip;
 
 extern "C" {
@@ -248,7 +285,7 @@ int tip_kin_carry_bytes(int n_slots, size_t* bytes) {
 int tip_kin_fk(const void* skel, const float* q, int ldq, long long n, float* pq_g, float* pq_jf, tip_stream_t stream) {
     if (!skel || !q || !pq_g || tip_bad_rows(n) || ldq < kn::NQ) return TIP_ERR_INVALID_ARG;
     if (n == 0) return TIP_OK;
-    hipLaunchKernelGGL(kin_fk_kernel, dim3((unsigned)((n + kn::LANES - 1) / kn::LANES)), dim3(kn::LANES), 0,
+    hipLaunchKernelGGL((kin_fk_kernel<false>), dim3((unsigned)((n + kn::LANES - 1) / kn::LANES)), dim3(kn::LANES), 0,
                        static_cast<hipStream_t>(stream), static_cast<const KinSkel*>(skel), q, ldq, n, pq_g, pq_jf);
     return tip_launch_status();
 }
@@ -258,7 +295,7 @@ int tip_kin_track_reset(const void* skel, void* carry, int n_slots, const int* s
     if (!skel || !carry || tip_bad_count(n_slots) || count < 0 || (count > 0 && !s_init) || reinterpret_cast<uintptr_t>(carry) % 8)
         return TIP_ERR_INVALID_ARG;
     if (count == 0 || n_slots == 0) return TIP_OK;
-    hipLaunchKernelGGL(kin_reset_kernel, dim3((count + kn::LANES - 1) / kn::LANES), dim3(kn::LANES), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((kin_reset_kernel<false>), dim3((count + kn::LANES - 1) / kn::LANES), dim3(kn::LANES), 0, static_cast<hipStream_t>(stream),
                        static_cast<const KinSkel*>(skel), static_cast<KinCarry*>(carry), n_slots, slots, count, s_init);
     return tip_launch_status();
 }
@@ -271,7 +308,7 @@ int tip_kin_track(const void* skel, void* carry, int n_slots, const int* slots, 
         return TIP_ERR_INVALID_ARG;
     if (count > 0 && (!begin || !end || !s_rest || !c_t || !root_out || !viz_out)) return TIP_ERR_INVALID_ARG;
     if (count == 0 || n_slots == 0 || n_rows == 0) return TIP_OK;
-    hipLaunchKernelGGL(kin_track_kernel, dim3(count), dim3(kn::LANES), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((kin_track_kernel<false>), dim3(count), dim3(kn::LANES), 0, static_cast<hipStream_t>(stream),
                        static_cast<const KinSkel*>(skel), static_cast<KinCarry*>(carry), n_slots, slots, begin, end, n_rows, s_rest, c_t,
                        nc, valid, root_out, viz_out);
     return tip_launch_status();
@@ -289,3 +326,4 @@ int tip_kin_metrics(const void* skel, const float* pred_qdq, const float* gt_qdq
 }
 
 }  // extern "C"
+#endif  // TIP_KIN_SCALED_TU

@@ -154,4 +154,27 @@ __device__ __forceinline__ void fk_frames(const KinSkel& sk, int L, const float*
 }
 __device__ __forceinline__ void fk_to_com(const KinSkel& sk, int L, float* F) { fk_to_com<float, false>(sk.link, L, 1.f, F); }
 
+// ... and for a wearer of body scale `scale` (the _scaled entries): every joint and COM offset times `scale` before it is rotated, as
+// PyBullet's globalScaling builds a SimAgent(scale=s) (bullet_agent.py:47,67).  SCALED = false is the two wrappers above, statement for
+// statement: `scale` is not read and nothing is multiplied by 1.
+template <bool SCALED>
+__device__ __forceinline__ void fk_frames_of(const KinSkel& sk, int L, const float* __restrict__ rot, float rx, float ry, float rz, float scale,
+                                             float* F) {
+    if constexpr (SCALED) fk_frames<float, true>(sk.link, L, rot, rx, ry, rz, scale, F);
+    else fk_frames(sk, L, rot, rx, ry, rz, F);
+}
+template <bool SCALED>
+__device__ __forceinline__ void fk_to_com_of(const KinSkel& sk, int L, float scale, float* F) {
+    if constexpr (SCALED) fk_to_com<float, true>(sk.link, L, scale, F);
+    else fk_to_com(sk, L, F);
+}
+
+// A body scale the kernels accept: finite and above 0.  Any other makes its sequence's rows NaN and touches nothing else.
+__device__ __forceinline__ bool kin_scale_ok(float s) { return s > 0.f && s <= 3.402823466e38f; }
+
+// The kernels of tip_kin.hip and tip_terrain.hip are templates over (SCALED, S...): the scaled instantiation has one parameter more, the
+// scale array, as the pack S... = const float*; the unscaled one has an empty pack, i.e. the parameter list it always had.
+__device__ __forceinline__ const float* kin_scale_ptr() { return nullptr; }
+__device__ __forceinline__ const float* kin_scale_ptr(const float* scale) { return scale; }
+
 }  // namespace tip

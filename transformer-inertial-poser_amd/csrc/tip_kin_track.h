@@ -146,10 +146,17 @@ __device__ __forceinline__ void carry_store_pq(KinCarry& cr, const float* Fs, in
 // A carry at its start: root = s_init[:3], no previous velocity, pq = FK(s_init) about the root.  carry_init, by one lane, fills the LDS
 // column F with that FK and sets all but pq; carry_init_pq copies the column out, entries first, first + step, ... — by the same lane
 // (0, 1) or, behind a barrier, by a workgroup (t, its size).  Entries of pq beyond (L + 1) * 7 and the pad are the caller's.
-__device__ __forceinline__ void carry_init(const KinSkel& sk, int L, KinCarry& c, const float* __restrict__ row, float* F) {
-    fk_frames(sk, L, row + 3, 0.f, 0.f, 0.f, F);
-    fk_to_com(sk, L, F);
+// SCALED: the FK of a wearer of body scale `scale` (the root of s_init is the wearer's metres already and is not scaled); a scale that
+// kin_scale_ok refuses leaves a NaN root and NaN positions, which the track kernels never read: they test the scale first.
+template <bool SCALED = false>
+__device__ __forceinline__ void carry_init(const KinSkel& sk, int L, KinCarry& c, const float* __restrict__ row, float* F, float scale = 1.f) {
+    if constexpr (SCALED) scale = kin_scale_ok(scale) ? scale : __builtin_nanf("");
+    fk_frames_of<SCALED>(sk, L, row + 3, 0.f, 0.f, 0.f, scale, F);
+    fk_to_com_of<SCALED>(sk, L, scale, F);
     for (int k = 0; k < 3; ++k) c.root[k] = (double)row[k], c.vprev[k] = 0.f;
+    if constexpr (SCALED)
+        if (scale != scale)
+            for (int k = 0; k < 3; ++k) c.root[k] = __builtin_nan("");
     c.has_prev = 0;
 }
 __device__ __forceinline__ void carry_init_pq(KinCarry& c, const float* F, int L, int first, int step) {

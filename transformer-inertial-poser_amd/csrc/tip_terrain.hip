@@ -43,10 +43,15 @@
 //                          search over it and its merge — is lane-parallel under wave-uniform control flow.  Stores of scan state are
 //                          lane 0's; region heights and the map go through memory with a workgroup barrier between writer and reader.
 //
+// Both are templates over (SCALED, S...), as tip_kin.hip's: SCALED = true runs FK on the wearer's own body scale (read from a device
+// array by block), behind the *_scaled entries of tip_terrain_scaled.hip; the block's layout is the same.
+//
 // Nothing waits on another workgroup; a slot's block is written only by the wave whose sequence names it.
 //
 // The first half of a frame — root_pre, the SBP locations, the residues, the nanmean and the clip — the scan state and the carry's
 // initialisation are tip_kin_track.h's, shared with tip_kin.hip's tracker; so are TerHead and ter_lay, which tip_replay.hip reads.
+// SCALED = true is instantiated in a translation unit of its own (tip_terrain_scaled.hip, which includes this file for the templates
+// and defines TIP_TERRAIN_SCALED_TU), so that the unscaled kernels are compiled alone, as they were before there was a scale.
 #include "tip_kin_track.h"
 
 namespace tip {
@@ -84,9 +89,11 @@ __device__ __forceinline__ TerChain ter_chain(const KinSkel& sk, int L, int ank)
     return c;
 }
 
+// SCALED: the carry's FK is the wearer's, of body scale scale[slot] (by block, as the track kernel reads it).
+template <bool SCALED, typename... S>
 __global__ __launch_bounds__(256) void terrain_reset_kernel(const KinSkel* __restrict__ skp, unsigned char* __restrict__ state, int n_slots,
                                                             int G, int M, const int* __restrict__ slots, int count,
-                                                            const float* __restrict__ s_init) {
+                                                            const float* __restrict__ s_init, S... scale) {
     __shared__ float Fs[kn::MAX_BODIES * 7 * kn::COL];
     const KinSkel& sk = *skp;
     const int L = kin_links(sk), t = threadIdx.x, j = blockIdx.x;
@@ -101,7 +108,8 @@ __global__ __launch_bounds__(256) void terrain_reset_kernel(const KinSkel* __res
     unsigned* map = reinterpret_cast<unsigned*>(blk + lay.off_map);
     const float* row = s_init + (size_t)j * kn::QDQ;
     if (t == 0) {
-        carry_init(sk, L, h.carry, row, Fs);
+        if constexpr (SCALED) carry_init<true>(sk, L, h.carry, row, Fs, kin_scale_ptr(scale...)[slot]);
+        else carry_init(sk, L, h.carry, row, Fs);
         for (int i = 0; i < kn::SBPS; ++i)
             for (int k = 0; k < 3; ++k) h.c_prev[i][k] = 100.0;     // :53-54
         for (int i = 0; i < 2; ++i)
@@ -272,13 +280,17 @@ __device__ double terrain_update(TerScan& s, double* rh, double* rw, unsigned* m
     return new_h - h;                                               // region_height[map[centre]] - h: the centre cell (d2 = 0) is r's
 }
 
+// SCALED: the sequence's body scale is scale[slot], read once per launch: the FK of every row — the poses the residues are taken on, the
+// pelvis test's and the link frames the IK solves on — is the wearer's.  Nothing else is scaled.  A scale that kin_scale_ok refuses makes
+// the sequence's rows NaN with fire -1 and leaves its block, the map included, alone.
+template <bool SCALED, typename... S>
 __global__ __launch_bounds__(64) void terrain_track_kernel(const KinSkel* __restrict__ skp, unsigned char* __restrict__ state, int n_slots,
                                                            int G, int M, int D, double gs, const int* __restrict__ slots,
                                                            const long long* __restrict__ begin, const long long* __restrict__ end,
                                                            long long n_rows, const float* __restrict__ s_rest,
                                                            const float* __restrict__ c_t, int nc, const unsigned char* __restrict__ valid,
                                                            int flags, float* __restrict__ root_out, float* __restrict__ viz_out,
-                                                           float* __restrict__ q_hist, int* __restrict__ fire_out) {
+                                                           float* __restrict__ q_hist, int* __restrict__ fire_out, S... scale) {
     __shared__ float Fs[kn::MAX_BODIES * 7 * kn::COL];
     __shared__ float Js[18 * kn::COL];                              // link-frame positions of hip, knee, ankle of both legs
     const KinSkel& sk = *skp;
@@ -290,6 +302,18 @@ __global__ __launch_bounds__(64) void terrain_track_kernel(const KinSkel* __rest
     unsigned char* blk = state + (size_t)slot * lay.stride;
     TerHead& hd = *reinterpret_cast<TerHead*>(blk);
     if (hd.grid_num != G || hd.max_regions != M) return;          // not the layout the reset gave this block
+    float sc = 1.f;
+    if constexpr (SCALED) {
+        sc = kin_scale_ptr(scale...)[slot];
+        if (!kin_scale_ok(sc)) {
+            const float nanf = __builtin_nanf("");
+            for (long long e = r0 * 3 + lane; e < r1 * 3; e += kn::LANES) root_out[e] = nanf;
+            for (long long e = r0 * 15 + lane; e < r1 * 15; e += kn::LANES) viz_out[e] = nanf;
+            for (long long e = r0 * 54 + lane; e < r1 * 54; e += kn::LANES) q_hist[e] = nanf;
+            for (long long e = r0 + lane; e < r1; e += kn::LANES) fire_out[e] = -1;
+            return;
+        }
+    }
     double* rh = reinterpret_cast<double*>(blk + sizeof(TerHead));
     double* rw = reinterpret_cast<double*>(blk + lay.off_w);
     unsigned* map = reinterpret_cast<unsigned*>(blk + lay.off_map);
@@ -320,13 +344,13 @@ __global__ __launch_bounds__(64) void terrain_track_kernel(const KinSkel* __rest
         const long long left = r1 - t0;
         const int cnt = left < kn::LANES ? (int)left : kn::LANES;
         if (lane < cnt && (!valid || valid[t0 + lane])) {
-            fk_frames(sk, L, s_rest + (size_t)(t0 + lane) * kn::REST, 0.f, 0.f, 0.f, F);
+            fk_frames_of<SCALED>(sk, L, s_rest + (size_t)(t0 + lane) * kn::REST, 0.f, 0.f, 0.f, sc, F);
             for (int g = 0; g < 2; ++g) {
                 const int b3[3] = {chain[g].hip, chain[g].knee, chain[g].ank};
                 for (int m = 0; m < 3; ++m)
                     for (int k = 0; k < 3; ++k) Js[(9 * g + 3 * m + k) * kn::COL + lane] = F[(7 * b3[m] + k) * kn::COL];
             }
-            fk_to_com(sk, L, F);
+            fk_to_com_of<SCALED>(sk, L, sc, F);
         }
         __syncthreads();
         int last = -1;
@@ -441,13 +465,15 @@ __global__ __launch_bounds__(64) void terrain_track_kernel(const KinSkel* __rest
 
 }  // namespace tip
 
+static bool ter_bad_shape(int n_slots, int grid_num, int max_regions) {
+    using namespace tip;
+    return tip_bad_count(n_slots) || grid_num < 2 || grid_num > tr::MAX_GRID || max_regions < 1 || max_regions > tr::MAX_REGIONS;
+}
+
+#ifndef TIP_TERRAIN_SCALED_TU
 using namespace tip;
 
 extern "C" {
-
-static bool ter_bad_shape(int n_slots, int grid_num, int max_regions) {
-    return tip_bad_count(n_slots) || grid_num < 2 || grid_num > tr::MAX_GRID || max_regions < 1 || max_regions > tr::MAX_REGIONS;
-}
 
 int tip_terrain_state_bytes(int n_slots, int grid_num, int max_regions, size_t* bytes) {
     if (!bytes || ter_bad_shape(n_slots, grid_num, max_regions)) return TIP_ERR_INVALID_ARG;
@@ -461,7 +487,7 @@ int tip_terrain_reset(const void* skel, void* state, int n_slots, int grid_num, 
         || reinterpret_cast<uintptr_t>(state) % 8)
         return TIP_ERR_INVALID_ARG;
     if (count == 0 || n_slots == 0) return TIP_OK;
-    hipLaunchKernelGGL(terrain_reset_kernel, dim3(count), dim3(256), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((terrain_reset_kernel<false>), dim3(count), dim3(256), 0, static_cast<hipStream_t>(stream),
                        static_cast<const KinSkel*>(skel), static_cast<unsigned char*>(state), n_slots, grid_num, max_regions, slots, count,
                        s_init);
     return tip_launch_status();
@@ -477,10 +503,11 @@ int tip_terrain_track(const void* skel, void* state, int n_slots, int grid_num, 
         return TIP_ERR_INVALID_ARG;
     if (count > 0 && (!begin || !end || !s_rest || !c_t || !root_out || !viz_out || !q_hist_out || !fire_out)) return TIP_ERR_INVALID_ARG;
     if (count == 0 || n_slots == 0 || n_rows == 0) return TIP_OK;
-    hipLaunchKernelGGL(terrain_track_kernel, dim3(count), dim3(kn::LANES), 0, static_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((terrain_track_kernel<false>), dim3(count), dim3(kn::LANES), 0, static_cast<hipStream_t>(stream),
                        static_cast<const KinSkel*>(skel), static_cast<unsigned char*>(state), n_slots, grid_num, max_regions, diffuse_region,
                        grid_size, slots, begin, end, n_rows, s_rest, c_t, nc, valid, flags, root_out, viz_out, q_hist_out, fire_out);
     return tip_launch_status();
 }
 
 }  // extern "C"
+#endif  // TIP_TERRAIN_SCALED_TU

@@ -19,6 +19,12 @@ A pose is xyz + (x, y, z, w).  FK is fp32; the tracker's scan and root accumulat
 metrics are fp64 sums.  One detail of the runner the tracker has to undo: :159 integrates the root velocity as predicted, while
 s_rest[54:57] is that velocity after the pose averaging of :165-166 — so v = 2 s_rest[54:57] - (the previous valid row's).
 
+Wearers differ in size.  The reference builds its character with scale = h / 1.6 (scale_of_height), and the runners run on the character
+they are given; `scale` / `scales` everywhere here is that: every link's joint and COM offset times the wearer's scale before it is
+rotated, and nothing else (not the root, not c_t's vectors, no threshold).  fk takes one scale per row, the trackers one per sequence or
+slot, set when a slot is reset and at no other time (the carry's pq_prev was computed with it).  scales=None is the unscaled code path,
+launch for launch and bit for bit; with scales the *_scaled entries of the library run (kernel instantiations of their own).
+
 RTRunner's terrain map, height correction and leg IK (real_time_runner.py:140-262, 334-382) are tip_amd.terrain, the same kind of
 consumer over the same FK; track_replay(..., terrain=dict(map_bound=..., grid_size=...)) routes a replay through it."""
 from __future__ import annotations
@@ -215,11 +221,58 @@ def _stream(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
-# ---- FK ------------------------------------------------------------------------------------------------------------------------------
-def fk(skel: Skeleton, q, out_jf: bool = False, device=None):
-    """q [N, >= 57] (root xyz, root axis-angle, the joints' axis-angles; numpy or a CUDA tensor) -> pq_g [N, L + 1, 7], the COM poses
-    (PyBullet's getLinkState fields 0-1), root first; with out_jf=True also pq_jf, the link frames (fields 4-5).  CUDA float32."""
+# ---- the wearer's body scale -----------------------------------------------------------------------------------------------------------
+def scale_of_height(h: float) -> float:
+    """The reference's rule for a wearer h metres tall: scale = h / 1.6 (data-gen-and-viz-bullet-new.py:256-257, handed to SimAgent as
+    PyBullet's globalScaling, bullet_agent.py:47,67)."""
+    return float(h) / 1.6
+
+
+def check_scales(scales, count: int, who: str, scalar_ok: bool = False):
+    """`scales` as a float32 numpy array [count], or None for None.  ValueError for anything that is not `count` finite numbers above 0
+    (with scalar_ok, one number stands for all).  Host work only: every caller refuses here before it allocates or launches anything.
+    (A CUDA tensor is read back for the check.)"""
+    if scales is None:
+        return None
+    if hasattr(scales, "detach"):
+        scales = scales.detach().cpu().numpy()
+    try:
+        a = np.asarray(scales, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"tip_amd.{who}: scales is [{count}] numbers; got {type(scales).__name__}") from None
+    if scalar_ok and a.ndim == 0:
+        a = np.full(count, float(a))
+    if a.shape != (count,):
+        raise ValueError(f"tip_amd.{who}: scales is [{count}], one body scale per {'row' if scalar_ok else 'sequence'}; got {a.shape}")
+    if not (np.isfinite(a).all() and (a > 0).all()):
+        bad = int(np.nonzero(~(np.isfinite(a) & (a > 0)))[0][0])
+        raise ValueError(f"tip_amd.{who}: a body scale is a finite number above 0 (height / 1.6); got {a[bad]!r} at {bad}")
+    a = a.astype(np.float32)
+    if not (np.isfinite(a).all() and (a > 0).all()):
+        raise ValueError(f"tip_amd.{who}: a body scale must be finite and above 0 as float32 too")
+    return a
+
+
+def _scales_dev(a, device):
     import torch
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).pin_memory().to(device, non_blocking=True)
+
+
+# ---- FK ------------------------------------------------------------------------------------------------------------------------------
+def fk(skel: Skeleton, q, out_jf: bool = False, device=None, scale=None):
+    """q [N, >= 57] (root xyz, root axis-angle, the joints' axis-angles; numpy or a CUDA tensor) -> pq_g [N, L + 1, 7], the COM poses
+    (PyBullet's getLinkState fields 0-1), root first; with out_jf=True also pq_jf, the link frames (fields 4-5).  CUDA float32.
+    scale: the wearer's body scale, one number or [N] (one per row: rows of many wearers in one launch); None is the unscaled kernel.
+    A float32 CUDA tensor [N] is used where it lies, unread by the host: there the kernel's rule holds (a row whose scale is not finite
+    or not above 0 comes back NaN)."""
+    import torch
+    shape = tuple(q.shape) if hasattr(q, "shape") else np.shape(q)
+    if len(shape) != 2 or shape[1] < 57:
+        raise ValueError(f"tip_amd.kinematics.fk: q is [N, >= 57]; got {shape}")
+    on_dev = isinstance(scale, torch.Tensor) and scale.is_cuda
+    if on_dev and (scale.dtype != torch.float32 or tuple(scale.shape) != (int(shape[0]),)):
+        raise ValueError(f"tip_amd.kinematics.fk: a device scale is float32 [{int(shape[0])}]; got {scale.dtype} {tuple(scale.shape)}")
+    sc = scale.contiguous() if on_dev else check_scales(scale, int(shape[0]), "kinematics.fk", scalar_ok=True)
     device = q.device if isinstance(q, torch.Tensor) and q.is_cuda and device is None else _device(device)
     t = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32))
     if t.dim() != 2 or t.shape[1] < 57:
@@ -232,8 +285,12 @@ def fk(skel: Skeleton, q, out_jf: bool = False, device=None):
         sk = skel.on(device)
         pq_g = torch.empty((n, per, 7), dtype=torch.float32, device=device)
         pq_jf = torch.empty((n, per, 7), dtype=torch.float32, device=device) if out_jf else None
-        _check(lib.tip_kin_fk(sk.data_ptr(), t.data_ptr(), int(t.shape[1]), n, pq_g.data_ptr(), None if pq_jf is None else pq_jf.data_ptr(),
-                              _stream(device)))
+        if sc is None:
+            _check(lib.tip_kin_fk(sk.data_ptr(), t.data_ptr(), int(t.shape[1]), n, pq_g.data_ptr(), _ptr(pq_jf), _stream(device)))
+        else:
+            scd = sc.to(device) if on_dev else _scales_dev(sc, device)
+            _check(lib.tip_kin_fk_scaled(sk.data_ptr(), t.data_ptr(), int(t.shape[1]), n, pq_g.data_ptr(), _ptr(pq_jf), scd.data_ptr(),
+                                         _stream(device)))
     return (pq_g, pq_jf) if out_jf else pq_g
 
 
@@ -245,12 +302,23 @@ def _ptr(t):
 class _Blocks:
     """n state blocks on a device with the skeleton beside them, and the reset and track launches on them.  A subclass sizes the
     buffer (_alloc) and names the two entry points (looked up in the loaded library at every launch, so that a wrapper somebody puts
-    around one there sees the call), what they take behind (skel, blocks, n) and what track takes behind `valid`."""
+    around one there sees the call), what they take behind (skel, blocks, n) and what track takes behind `valid`.
+    `scale`: None, or the [n] float32 device tensor of the blocks' body scales; with one, the entries are the two names + "_scaled" and
+    take it in front of the stream (`entries` says which pair the next launch calls)."""
     _reset_fn = _track_fn = None
     _reset_args = _track_args = _track_tail = ()
+    scale = None
 
     def __init__(self, skel, n, device):
         self.skel, self.n, self.device = skel, int(n), _device(device)
+
+    @property
+    def entries(self):
+        tail = "" if self.scale is None else "_scaled"
+        return self._reset_fn + tail, self._track_fn + tail
+
+    def _scale_arg(self):
+        return () if self.scale is None else (self.scale.data_ptr(),)
 
     def _alloc(self, bytes_fn, *shape):
         import torch
@@ -265,15 +333,15 @@ class _Blocks:
     def reset(self, slots_dev, count, s_init_dev):
         import torch
         with torch.cuda.device(self.device):
-            _check(getattr(self.lib, self._reset_fn)(self.sk.data_ptr(), self.buf.data_ptr(), self.n, *self._reset_args, _ptr(slots_dev), count,
-                                  s_init_dev.data_ptr(), _stream(self.device)))
+            _check(getattr(self.lib, self.entries[0])(self.sk.data_ptr(), self.buf.data_ptr(), self.n, *self._reset_args, _ptr(slots_dev), count,
+                                  s_init_dev.data_ptr(), *self._scale_arg(), _stream(self.device)))
 
     def track(self, slots_dev, begin_ptr, end_ptr, count, s_rest, c_t, valid, *outs):
         import torch
         with torch.cuda.device(self.device):
-            _check(getattr(self.lib, self._track_fn)(self.sk.data_ptr(), self.buf.data_ptr(), self.n, *self._track_args, _ptr(slots_dev), begin_ptr, end_ptr,
+            _check(getattr(self.lib, self.entries[1])(self.sk.data_ptr(), self.buf.data_ptr(), self.n, *self._track_args, _ptr(slots_dev), begin_ptr, end_ptr,
                                   count, int(s_rest.shape[0]), s_rest.data_ptr(), c_t.data_ptr(), int(c_t.shape[1]), _ptr(valid),
-                                  *self._track_tail, *(o.data_ptr() for o in outs), _stream(self.device)))
+                                  *self._track_tail, *(o.data_ptr() for o in outs), *self._scale_arg(), _stream(self.device)))
 
 
 class _Carry(_Blocks):
@@ -300,11 +368,19 @@ def _track_inputs(s_rest, c_t, valid, device, who):
     return s, c, valid
 
 
-def _track_ragged(mod, who, s_init, s_rest, c_t, valid, offsets, device, chunk, make, check_width=None):
+def _ragged_scales(mod, who, scales, offsets):
+    """track's / track_terrain's scales [R] checked on the host (R from offsets), before anything else is looked at."""
+    if scales is None:
+        return None
+    return check_scales(scales, max(int(np.asarray(offsets).reshape(-1).shape[0]) - 1, 0), f"{mod}.{who}")
+
+
+def _track_ragged(mod, who, s_init, s_rest, c_t, valid, offsets, device, chunk, make, check_width=None, scales=None):
     """track and track_terrain behind their outputs: the inputs onto the device and checked (s_rest [N, 111], c_t [N, 8 | 20], valid [N],
     offsets [R + 1], s_init as [R, 114]), then make(N, R) — the caller's state object of R blocks and the tuple of its output tensors —
     then the reset and the track of every sequence, in one launch or, with chunk=k, k rows of every sequence per launch.  Returns what
-    make returned."""
+    make returned.  scales: None, or the sequences' body scales [R] as check_scales returned them — the state object then calls the
+    scaled entries with them."""
     import torch
     s, c, v = _track_inputs(s_rest, c_t, valid, device, who)
     if check_width is not None:
@@ -314,9 +390,13 @@ def _track_ragged(mod, who, s_init, s_rest, c_t, valid, offsets, device, chunk, 
     s0 = _dev_f32(s_init if np.ndim(s_init) == 2 else np.asarray(s_init)[None], device, (114,), who, "s_init")
     if s0.shape[0] != R:
         raise ValueError(f"tip_amd.{mod}.{who}: s_init is [R, 114] with one row per sequence ({R}); got {tuple(s0.shape)}")
+    if scales is not None and scales.shape[0] != R:
+        raise ValueError(f"tip_amd.{mod}.{who}: scales is [R], one body scale per sequence ({R}); got {scales.shape}")
     st, outs = make(int(s.shape[0]), R)
     if R == 0 or s.shape[0] == 0:
         return st, outs
+    if scales is not None:
+        st.scale = _scales_dev(scales, device)
     st.reset(None, R, s0)
     if chunk is None:
         od = torch.from_numpy(o).pin_memory().to(device, non_blocking=True)
@@ -332,11 +412,13 @@ def _track_ragged(mod, who, s_init, s_rest, c_t, valid, offsets, device, chunk, 
     return st, outs
 
 
-def track(skel: Skeleton, s_init, s_rest, c_t, valid, offsets, device=None, chunk=None):
+def track(skel: Skeleton, s_init, s_rest, c_t, valid, offsets, device=None, chunk=None, scales=None):
     """R sequences back to back: s_init [R, 114], s_rest [N, 111], c_t [N, 8 | 20], valid [N] bool, offsets [R + 1] ->
     root [N, 3], viz_locs [N, 5, 3] (CUDA float32): the rows of RTRunnerMin.step's qdq[:3] and viz_locs, one kernel for the lot.
-    chunk=k runs it k rows of every sequence per launch instead, through the carry: the same bits, for whoever gets rows in pieces."""
+    chunk=k runs it k rows of every sequence per launch instead, through the carry: the same bits, for whoever gets rows in pieces.
+    scales [R]: the sequences' body scales (None: the unscaled kernels)."""
     import torch
+    scales = _ragged_scales("kinematics", "track", scales, offsets)
     device = _device(device)
 
     def make(n, R):
@@ -344,19 +426,21 @@ def track(skel: Skeleton, s_init, s_rest, c_t, valid, offsets, device=None, chun
                                          torch.empty((n, 5, 3), dtype=torch.float32, device=device))
 
     with torch.cuda.device(device):
-        return _track_ragged("kinematics", "track", s_init, s_rest, c_t, valid, offsets, device, chunk, make)[1]
+        return _track_ragged("kinematics", "track", s_init, s_rest, c_t, valid, offsets, device, chunk, make, scales=scales)[1]
 
 
-def track_replay(skel: Skeleton, results: Sequence, s_init, device=None, terrain=None) -> List[tuple]:
+def track_replay(skel: Skeleton, results: Sequence, s_init, device=None, terrain=None, scales=None) -> List[tuple]:
     """ReplayPool.run's list -> per recording (qdq [L_i, 114], viz_locs [L_i, 5, 3]) as numpy float32: the script's s_traj_pred and
     viz_locs_seq before its trim (offline_testing_simple.py:123-139) — row 0 and the priming rows are s_init whole with markers at 100,
     row t + 1 is the step on frame t.  replay.trim_like_reference serves both arrays.
     terrain=None is RTRunnerMin's flat ground; terrain=dict(map_bound=..., grid_size=...[, max_regions=...]) is the full runner as the
-    script starts it (:169-176, multi_sbp_terrain_and_correction off), through tip_amd.terrain.track_terrain."""
+    script starts it (:169-176, multi_sbp_terrain_and_correction off), through tip_amd.terrain.track_terrain.
+    scales [R]: the recordings' body scales — what a file made by motion.syn_files at scale != 1 has to be tracked with."""
     who = "track_replay"
     results = list(results)
     if not results:
         raise ValueError("tip_amd.kinematics.track_replay: no recordings")
+    scales = check_scales(scales, len(results), "kinematics.track_replay")
     s0 = np.ascontiguousarray(s_init, dtype=np.float32)
     s0 = s0[None] if s0.ndim == 1 else s0
     if s0.shape != (len(results), 114):
@@ -374,15 +458,16 @@ def track_replay(skel: Skeleton, results: Sequence, s_init, device=None, terrain
     s_rest = np.concatenate([np.asarray(r.s_rest, dtype=np.float32) for r in results])
     c_all = np.concatenate([np.asarray(r.c_t, dtype=np.float32) for r in results])
     v_all = np.concatenate([np.asarray(r.valid, dtype=bool) for r in results])
+    kw = {} if scales is None else {"scales": scales}          # (scales=None: the call as it always was)
     if terrain is None:
-        root, viz = track(skel, s0, s_rest, c_all, v_all, offs, device)
+        root, viz = track(skel, s0, s_rest, c_all, v_all, offs, device, **kw)
     else:
         from .terrain import track_terrain
         extra = set(terrain) - {"map_bound", "grid_size", "max_regions"}
         if extra or not {"map_bound", "grid_size"} <= set(terrain):
             raise ValueError(f"tip_amd.kinematics.track_replay: terrain is dict(map_bound=..., grid_size=...[, max_regions=...]); got "
                              f"{sorted(terrain)}")
-        root, viz = track_terrain(skel, s0, s_rest, c_all, v_all, offs, multi_sbp=False, device=device, **terrain)[:2]
+        root, viz = track_terrain(skel, s0, s_rest, c_all, v_all, offs, multi_sbp=False, device=device, **kw, **terrain)[:2]
     root, viz = root.cpu().numpy(), viz.cpu().numpy()
     out = []
     for i, (a, b) in enumerate(zip(offs[:-1], offs[1:])):
@@ -408,6 +493,7 @@ class _Tracker:
             self.root = torch.zeros((self.n, 3), dtype=torch.float32, device=self.device)
             self.viz_locs = torch.full((self.n, 5, 3), 100.0, dtype=torch.float32, device=self.device)
             self._rows = torch.arange(self.n + 1, dtype=torch.int64, device=self.device)
+            self.scale = torch.ones(self.n, dtype=torch.float32, device=self.device)      # the slots' body scales; 1 until a reset gives one
         self._outs = (self.root, self.viz_locs)
         self._lists = {}
 
@@ -432,8 +518,23 @@ class _Tracker:
     def _before_subset_step(self):
         """What a step on a subset of the slots does to the output rows first."""
 
-    def reset(self, slots, s_init_rows):
+    @property
+    def entries(self):
+        """The two library entries the next reset and step call: the unscaled pair until a reset has been given scales."""
+        return self._s.entries
+
+    def _unscaled(self):
+        """Back to the unscaled entries with every slot at scale 1 (ReplayPool.run(scales=None) after a run with scales)."""
+        if self._s.scale is not None:
+            self._s.scale = None
+            self.scale.fill_(1.0)
+
+    def reset(self, slots, s_init_rows, scales=None):
         import torch
+        from .streaming import slot_list
+        who = f"{self._mod}.{self._name}.reset"
+        count = self.n if slots is None else len(slot_list(slots, self.n, f"{self._slot_who}.reset"))
+        scales = check_scales(scales, count, who)          # (host only: refused before anything is uploaded or launched)
         with torch.cuda.device(self.device):
             if slots is None:
                 count, sl = self.n, None
@@ -445,8 +546,15 @@ class _Tracker:
             if s0.shape[0] != count:
                 raise ValueError(f"tip_amd.{self._mod}.{self._name}.reset: s_init_rows is [{count}, 114]; got {tuple(s0.shape)}")
             if count:
-                self._s.reset(sl, count, s0)
                 rows = slice(None) if sl is None else sl.long()
+                # a slot's scale is set here and nowhere else: the carry's pq_prev is computed with it.  A reset without scales puts
+                # the slot back to 1; a tracker that was never given a scale does not touch the array and keeps the unscaled entries.
+                if scales is not None:
+                    self._s.scale = self.scale
+                    self.scale[rows] = _scales_dev(scales, self.device)
+                elif self._s.scale is not None:
+                    self.scale[rows] = 1.0
+                self._s.reset(sl, count, s0)
                 self.root[rows] = s0[:, :3]
                 self.viz_locs[rows] = 100.0
                 self._reset_rows(rows)
@@ -479,15 +587,18 @@ class RootTracker(_Tracker):
         root, viz_locs = rt.step(out)          # [n, 3], [n, 5, 3]: this frame's qdq[:3] and viz_locs by slot (tensors reused every frame)
     step() is ONE launch on the current stream (call it on the engine's stream, after step; it is not part of the engine's captured
     graph).  out=None — a lock-step engine that is still priming — launches nothing and returns the rows as they stand.  Rows whose
-    out["valid"] is False, and slots left out of `slots`, keep their carry; the former read (carry root, 100s)."""
+    out["valid"] is False, and slots left out of `slots`, keep their carry; the former read (carry root, 100s).
+    A pool of wearers of different heights: rt.reset(slots, rows, scales=[scale_of_height(h), ...]) — still one launch per frame."""
     _mod, _name, _slot_who = "kinematics", "RootTracker", "RootTracker"
 
     def __init__(self, skel: Skeleton, n: int, device):
         super().__init__(n, lambda n: _Carry(skel, n, device))
 
-    def reset(self, slots, s_init_rows):
-        """The listed slots (None: all) start over from s_init_rows [len(slots), 114]: root = s_init[:3], pq_prev = FK(s_init)."""
-        super().reset(slots, s_init_rows)
+    def reset(self, slots, s_init_rows, scales=None):
+        """The listed slots (None: all) start over from s_init_rows [len(slots), 114]: root = s_init[:3], pq_prev = FK(s_init).
+        scales [len(slots)]: the body scales of the wearers these slots take (rt.scale [n] holds them on the device, 1 where none was
+        given); from the first reset with scales on, reset and step call the scaled entries."""
+        super().reset(slots, s_init_rows, scales)
 
 
 # ---- the seven metrics ---------------------------------------------------------------------------------------------------------------
@@ -496,12 +607,14 @@ def root_indices(n: int) -> List[int]:
     return [int(np.minimum(int(t / DT) - 1, n - 1)) for t in (2.0, 5.0, 10.0)]
 
 
-def evaluate(skel: Skeleton, pred_qdq, gt_qdq, offsets, start: int = 30, end: int = 6, device=None) -> np.ndarray:
+def evaluate(skel: Skeleton, pred_qdq, gt_qdq, offsets, start: int = 30, end: int = 6, device=None, scales=None) -> np.ndarray:
     """R files back to back: pred_qdq, gt_qdq [N, 114] (numpy or CUDA tensors), offsets [R + 1] -> [R, 7] float64, the columns METRICS in
     the script's order (offline_testing_simple.py:439-445), over rows start .. L - end - 1 of each file with FK of both trajectories.
     The script's means and maxima over files (:447-461) are numpy on the result.  A file with fewer than 4 rows in range is a
-    ValueError (the reference would print the NaN of an empty mean; it never sees such a file, :371)."""
+    ValueError (the reference would print the NaN of an empty mean; it never sees such a file, :371).
+    scales [R]: the files' body scales; both trajectories of a file go through FK at its scale (None: the unscaled kernel)."""
     import torch
+    scales = _ragged_scales("kinematics", "evaluate", scales, offsets)
     device = _device(device)
     start, end = int(start), int(end)
     if start < 0 or end < 0:
@@ -523,7 +636,13 @@ def evaluate(skel: Skeleton, pred_qdq, gt_qdq, offsets, start: int = 30, end: in
         _, lib = _lib()
         i2, i5, i10 = (int(t / DT) - 1 for t in (2.0, 5.0, 10.0))      # the script's expression; the kernel clamps to each file's own rows
         sk = skel.on(device)
-        pq_p, pq_g = fk(skel, p, device=device), fk(skel, g, device=device)
+        if scales is not None and scales.shape[0] != R:
+            raise ValueError(f"tip_amd.kinematics.evaluate: scales is [R], one body scale per file ({R}); got {scales.shape}")
+        rows = None
+        if scales is not None:          # one entry per row, expanded on the device ([R] goes up, output_size spares the synchronisation)
+            lens_d = torch.from_numpy(lens.astype(np.int64)).pin_memory().to(device, non_blocking=True)
+            rows = torch.repeat_interleave(_scales_dev(scales, device), lens_d, output_size=int(p.shape[0]))
+        pq_p, pq_g = fk(skel, p, device=device, scale=rows), fk(skel, g, device=device, scale=rows)
         od = torch.from_numpy(o).pin_memory().to(device, non_blocking=True)
         out = torch.empty((R, 7), dtype=torch.float64, device=device)
         _check(lib.tip_kin_metrics(sk.data_ptr(), p.data_ptr(), g.data_ptr(), pq_p.data_ptr(), pq_g.data_ptr(), od.data_ptr(), R, start, end,

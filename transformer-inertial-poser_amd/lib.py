@@ -51,6 +51,7 @@ EXPORTS = (
     "tip_fill_real", "tip_fill_rows", "tip_fill_state_bytes", "tip_fill_reset", "tip_fill_live", "tip_fill_get", "tip_fill_packets",
     "tip_kin_skel_bytes", "tip_kin_carry_bytes", "tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_kin_metrics",
     "tip_terrain_state_bytes", "tip_terrain_reset", "tip_terrain_track",
+    "tip_kin_fk_scaled", "tip_kin_track_reset_scaled", "tip_kin_track_scaled", "tip_terrain_reset_scaled", "tip_terrain_track_scaled",
     "tip_syn_skel_bytes", "tip_syn_grid_bytes", "tip_syn_poses", "tip_syn_imu", "tip_syn_sbp",
     "tip_motion_tile", "tip_motion_qdq",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
@@ -217,6 +218,10 @@ def load() -> ctypes.CDLL:
     lib.tip_terrain_reset.argtypes = [vp, vp, i32, i32, i32, vp, i32, vp, vp]
     lib.tip_terrain_track.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.c_double, vp, vp, vp, i32, ctypes.c_longlong, vp, vp, i32, vp, i32,
                                       vp, vp, vp, vp, vp]
+    # per-wearer body scale (csrc/tip_kin_scaled.hip, csrc/tip_terrain_scaled.hip): the unscaled arguments with `scale` in front of the stream
+    for name in ("tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_terrain_reset", "tip_terrain_track"):
+        at = getattr(lib, name).argtypes
+        getattr(lib, name + "_scaled").argtypes = at[:-1] + [vp, vp]
     # synthetic data (csrc/tip_syn.hip): device buffers, counts, then the stream
     lib.tip_syn_skel_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_syn_grid_bytes.argtypes = [ctypes.POINTER(sz)]

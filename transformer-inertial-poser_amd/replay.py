@@ -377,12 +377,13 @@ class ReplayPool:
         self._bufs = (corpus, s_out, c_out, y_out, valid) + tuple(tracked)
         eng.set_feeder(feed, collect_tracked if tracked else collect)
 
-    def _reset_tracker(self, pairs, s0):
+    def _reset_tracker(self, pairs, s0, scales=None):
         """The tracker's blocks of the slots in `pairs` [(slot, recording), ...] start over from the recordings' s_init (pinned,
-        non-blocking: TerrainTracker.reset), in stream order before the next frame."""
+        non-blocking: TerrainTracker.reset) and, with scales, take the recordings' body scales, in stream order before the next frame."""
         if self.tracker is not None and pairs:
             pairs = sorted(pairs)
-            self.tracker.reset([s for s, _ in pairs], s0[[i for _, i in pairs]])
+            kw = {} if scales is None else {"scales": scales[[i for _, i in pairs]]}
+            self.tracker.reset([s for s, _ in pairs], s0[[i for _, i in pairs]], **kw)
 
     def _upload_table(self, in_flight, f, offs, lengths):
         """The cursor table as it stands before engine frame f — in_flight: {slot: (recording, the frame that fed its frame 0)} — in one
@@ -392,9 +393,19 @@ class ReplayPool:
             t[0, s], t[1, s] = offs[i] + (f - f0), offs[i] + lengths[i] - 1
         self._tbl.copy_(self._torch.from_numpy(t).pin_memory(), non_blocking=True)
 
-    def run(self, recordings, s_init) -> list:
-        torch = self._torch
+    def run(self, recordings, s_init, scales=None) -> list:
+        """scales [R] (pools with terrain= only): the recordings' body scales (tip_amd.kinematics.scale_of_height).  A recording's scale
+        goes to its slot's block with the reset the pool issues at the recording's attach frame, and again on a restart after a lost
+        hand-off; the captured frame reads the tracker's scale array where it lies, so a frame has no launch more and a run still one
+        synchronisation.  scales=None is the unscaled frame."""
         recs, s0 = check_inputs(recordings, s_init)
+        if scales is not None:          # refused before anything is allocated or launched
+            from .kinematics import check_scales
+            if self.tracker is None:
+                raise ValueError("tip_amd.replay.ReplayPool.run: scales are the body scales the pool's tracker runs FK with; this pool "
+                                 "has none (ReplayPool(terrain=dict(skel=..., ...)))")
+            scales = check_scales(scales, len(recs), "replay.ReplayPool.run")
+        torch = self._torch
         eng, n, dev = self.engine, self.slots, self.engine.device
         lengths = [r.shape[0] for r in recs]
         offs = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
@@ -405,6 +416,8 @@ class ReplayPool:
             # every slot detached and at rest, graphs of the previous run dropped
             eng.detach([i for i in range(n) if eng.attached[i]])
             eng.reset()
+            if scales is None and self.tracker is not None:
+                self.tracker._unscaled()          # (after a run with scales: back to the unscaled entries before the frame is captured)
             corpus = torch.from_numpy(np.concatenate(recs)).pin_memory().to(dev, non_blocking=True)
             s_out = torch.zeros((n_rows, 111), dtype=torch.float32, device=dev)
             c_out = torch.zeros((n_rows, eng.nc), dtype=torch.float32, device=dev)
@@ -446,7 +459,7 @@ class ReplayPool:
                 in_flight = {s: v for s, v in in_flight.items() if f - v[1] < lengths[v[0]] - 1}
                 if att:
                     self._upload_table(in_flight, f, offs, lengths)
-                    self._reset_tracker(att, s0)
+                    self._reset_tracker(att, s0, scales)
                 try:
                     eng._step_fed()
                 except self._handoff_error:
@@ -459,7 +472,7 @@ class ReplayPool:
                     plan = _plan(lengths, n, [i for i in range(len(recs)) if i not in done_attach], occupied)
                     in_flight, f = {s: (i, 0) for s, i in occupied.items()}, 0
                     self._upload_table(in_flight, 0, offs, lengths)
-                    self._reset_tracker(list(occupied.items()), s0)
+                    self._reset_tracker(list(occupied.items()), s0, scales)
                     continue
                 f += 1
             eng.detach(plan.final_detach)

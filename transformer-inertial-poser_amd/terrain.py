@@ -31,7 +31,7 @@ from typing import Sequence
 
 import numpy as np
 
-from .kinematics import Skeleton, _Blocks, _Tracker, _device, _track_ragged
+from .kinematics import Skeleton, _Blocks, _Tracker, _device, _ragged_scales, _track_ragged
 
 HEAD_BYTES = 1280                   # include/tip_hip.h, "terrain": the block's fixed part
 
@@ -135,12 +135,15 @@ def _check_width(c, multi_sbp, who):
 
 
 def track_terrain(skel: Skeleton, s_init, s_rest, c_t, valid, offsets, map_bound: float = 5.0, grid_size: float = 0.1,
-                  multi_sbp: bool = False, max_regions: int = 64, chunk=None, device=None):
+                  multi_sbp: bool = False, max_regions: int = 64, chunk=None, device=None, scales=None):
     """R sequences back to back: s_init [R, 114], s_rest [N, 111], c_t [N, 8 | 20], valid [N] bool, offsets [R + 1] ->
     root [N, 3], viz_locs [N, 5, 3], q_hist [N, 54] (float32), fire [N] (int32: the sequence's index where the IK rewrote the pose, else
     -1) on the device, and the TerrainStates: the rows of RTRunner.step's qdq[:3] and viz_locs and the pose it feeds back, one kernel
-    for the lot.  chunk=k runs it k rows of every sequence per launch instead, through the state: the same bits."""
+    for the lot.  chunk=k runs it k rows of every sequence per launch instead, through the state: the same bits.
+    scales [R]: the sequences' body scales (tip_amd.kinematics: every joint and COM offset times the scale, nothing else — not the map's
+    bound or grid, not the 0.2 m pelvis test, not the IK's thresholds); None is the unscaled kernels."""
     import torch
+    scales = _ragged_scales("terrain", "track_terrain", scales, offsets)
     device = _device(device)
 
     def make(n, R):
@@ -150,7 +153,7 @@ def track_terrain(skel: Skeleton, s_init, s_rest, c_t, valid, offsets, map_bound
 
     with torch.cuda.device(device):
         st, outs = _track_ragged("terrain", "track_terrain", s_init, s_rest, c_t, valid, offsets, device, chunk, make,
-                                 lambda c: _check_width(c, multi_sbp, "track_terrain"))
+                                 lambda c: _check_width(c, multi_sbp, "track_terrain"), scales=scales)
     return (*outs, TerrainStates(st))
 
 
@@ -164,7 +167,9 @@ class TerrainTracker(_Tracker):
     step() is ONE launch on the current stream (call it on the engine's stream, after step; it is not part of the engine's captured
     graph).  out=None — a lock-step engine that is still priming — launches nothing.  Rows whose out["valid"] is False keep their
     state and read (the state's root, 100s, fire -1).  With a `slots` subset the slots left out keep their state too, and their fire
-    entries are set to -1 first (one fill more), so that feed_back never repeats an old correction."""
+    entries are set to -1 first (one fill more), so that feed_back never repeats an old correction.
+    A pool of wearers of different heights: tt.reset(slots, rows, scales=[kinematics.scale_of_height(h), ...]) — every wearer's residue,
+    map and IK pose on legs of the wearer's own length, still one launch per frame."""
     _mod, _name, _slot_who = "terrain", "TerrainTracker", "terrain.TerrainTracker"
 
     def __init__(self, skel: Skeleton, n: int, device, map_bound: float = 5.0, grid_size: float = 0.1, multi_sbp: bool = False,
@@ -177,10 +182,11 @@ class TerrainTracker(_Tracker):
             self.fire = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
         self._outs += (self.q_hist, self.fire)
 
-    def reset(self, slots, s_init_rows):
+    def reset(self, slots, s_init_rows, scales=None):
         """The listed slots (None: all) start over from s_init_rows [len(slots), 114], as RTRunner.__init__ starts: root = s_init[:3],
-        pq_prev = FK(s_init), an empty map."""
-        super().reset(slots, s_init_rows)
+        pq_prev = FK(s_init), an empty map.  scales [len(slots)]: the body scales of the wearers these slots take, as
+        RootTracker.reset's (tt.scale [n] on the device; step and feed_back are as they were)."""
+        super().reset(slots, s_init_rows, scales)
 
     def _reset_rows(self, rows):
         self.fire[rows] = -1
