@@ -582,6 +582,78 @@ TIP_API int tip_fill_packets(const float* tables /* [n_seq,126] */, const float*
                      const long long* offsets /* [n_seq+1] */, int n_seq, float max_acc, float* out /* [n_rows,72] */,
                      tip_stream_t stream);
 
+/* ---- timestamped packets: every wearer resampled to the pool's tick grid, in front of the sensor front end above, whose packets[n,42]
+ *      must be one packet per slot per 60 Hz frame.  The reference serves its one wearer with a zero-order hold: the reader thread
+ *      overwrites current_reading whenever a packet arrives (live_demo_new.py:82-115) and the loop takes what is there once per
+ *      clock.tick(FREQ) (:161-162, :281-307).  Here a slot keeps its last packets with their stamps, and one launch per tick gives every
+ *      slot its packet AT the tick — sensors at 100 or 120 Hz, a 50 Hz wearer beside a 60 Hz one, bursts, recorded sessions off the grid.
+ *      Stamps and query times are fp64 seconds everywhere (an epoch-sized stamp, 1.7e9 s, still resolves 2.4e-7 s; fp32 resolves 128 s).
+ *      `state` is a caller-owned device buffer of tip_resample_state_bytes() (8-byte aligned), one block of bytes / n_slots per slot: the
+ *      ring index of the oldest entry, `have` (entries in the ring, 0 .. depth), `total` (packets taken) and `dropped` (packets refused),
+ *      4-byte ints; depth fp64 stamps; depth packets [42] fp32.  depth is 2 .. 64 and is given to every call as the state was sized.
+ *      tip_resample_reset: the blocks of the listed slots, or of all n when slots is null (required once), to zero: an empty ring.
+ *      tip_resample_push: m arrivals, packets[m,42], slots[m], times[m] (device arrays).  The arrivals of one slot are taken in array
+ *        order.  A slot outside [0, n) is skipped.  A stamp that is not finite, or (have > 0) not above the slot's newest stamp — a
+ *        duplicate, an out-of-order packet — is refused: dropped += 1, nothing else changes.  Otherwise the packet is appended as it is,
+ *        NaNs included, a full ring losing its oldest entry, and total += 1.  One wave per slot, and EVERY slot's wave reads the whole
+ *        slot list: a push costs n_slots x m reads of slots[] (measured at m = 2 n_slots, the per-tick case: 3.3 us at 256 slots, 7.0 us
+ *        at 1024).  A burst or a catch-up with m far above n_slots at a large n grows with the product: push it in pieces per tick,
+ *        or use tip_resample_rows, which searches.
+ *      tip_resample_emit: the per-tick launch.  t[n] is a DEVICE array (a captured frame freezes its arguments).  Per slot, with
+ *        tau = t[slot] - delay (fp64) and the ring's stamps s_0 < ... < s_last, packets_out[slot] and flags[slot] are
+ *          ring empty                                                              NaN                      3
+ *          not (tau >= s_0)  (before the ring, or tau NaN)                         NaN                      4
+ *          tau >= s_last and (max_hold < 0 or tau - s_last <= max_hold)            the newest packet        1
+ *          tau >= s_last otherwise                                                 NaN                      2
+ *          s_i <= tau < s_(i+1), HOLD: max_hold < 0 or tau - s_i <= max_hold       packet i                 1
+ *                                      otherwise                                   NaN                      2
+ *          s_i <= tau < s_(i+1), SLERP, max_hold >= 0 and s_(i+1) - s_i > max_hold as the two HOLD rows (nothing is interpolated across a dropout)
+ *          s_i <= tau < s_(i+1), SLERP otherwise                                   interpolated at u = (tau - s_i) / (s_(i+1) - s_i), fp64    0
+ *        A packet that is given is copied bit for bit.  HOLD with delay 0 is the reference's rule; SLERP needs delay > 0 to have a
+ *        later packet at all (delay = one sensor period keeps tau inside the ring).  Every decision is an fp64 comparison of the
+ *        expressions above.  One thread per (slot, sensor); tip_resample_tile answers the slots (or rows) of a workgroup.
+ *      Interpolation of sensor k between a = q0 q1 q2 q3 ax ay az of packet i and b of packet i + 1, fp32 unless said, every sum left to
+ *        right, nothing contracted:
+ *          Ra = Q2R(a[0:4]), Rb = Q2R(b[0:4]): the sensor front end's (normalise, then scipy's polynomials).  A zero or non-finite
+ *            quaternion on either side gives the sensor's seven output columns NaN and touches nothing else.
+ *          qa = a[0:4] / sqrt(a0 a0 + a1 a1 + a2 a2 + a3 a3), qb likewise; dot = qa0 qb0 + qa1 qb1 + qa2 qb2 + qa3 qb3;
+ *            dot < 0: qb = -qb, dot = -dot (the shorter arc).
+ *          fp64: d = min(dot, 1); d > 1 - 1e-6: w0 = 1 - u, w1 = u; else th = acos(d), w0 = sin((1 - u) th) / sin(th),
+ *            w1 = sin(u th) / sin(th); each rounded once to fp32.
+ *          q = w0 qa + w1 qb per component, then q / sqrt(q0 q0 + q1 q1 + q2 q2 + q3 q3): unit, its sign the earlier packet's
+ *            (a q of length zero or not finite: seven NaN).
+ *          The acceleration is a lerp in the GLOBAL frame, where gravity is constant, not of sensor-frame numbers: uf = (float) u,
+ *            vf = 1 - uf; ga_r = Ra[r,0] a4 + Ra[r,1] a5 + Ra[r,2] a6, gb_r from Rb and b; g_r = vf ga_r + uf gb_r; with Rq = Q2R(q),
+ *            out[4 + c] = Rq[0,c] g_0 + Rq[1,c] g_1 + Rq[2,c] g_2.  A NaN acceleration component makes the sensor's three acceleration
+ *            columns NaN and leaves its quaternion.
+ *      tip_resample_get: counts_out[count, 3] (device int) = have | dropped | total of the listed slots; a slot outside [0, n) leaves
+ *        its row as it was.  It runs on `stream` like every other *_get entry of this header.
+ *      tip_resample_rows: the same for n_seq ragged recorded sequences in one launch.  Sequence j is rows in_offsets[j] ..
+ *        in_offsets[j + 1] - 1 of packets[n_in, 42] and stamps[n_in] (strictly increasing within a sequence: the host checks), and
+ *        its output rows out_offsets[j] .. out_offsets[j + 1] - 1 of packets_out[n_out, 42] and flags[n_out], taken at t_out[n_out]
+ *        (all device arrays).  An output row sees what a live ring would hold at its tick — the packets of its sequence with a stamp
+ *        <= t_out[row], of these the last `depth` — and then the rule of tip_resample_emit, bit for bit.  The sequence of a row and
+ *        the packets before its tick are found by searches, not scans.  A row no sequence owns is NaN with flag 3; input offsets are
+ *        clamped to [0, n_in] and to ascending order before they index anything.  out_offsets is trusted to ascend from 0 to n_out: it
+ *        is only compared with the row's number and never used as an index, so a wrong one misplaces rows and reads nothing outside.
+ *      Null buffers, misaligned state, negative counts, a depth outside 2 .. 64, a delay that is negative or not finite, a NaN max_hold
+ *      and an unknown mode return TIP_ERR_INVALID_ARG before any launch; n_slots = 0, m = 0, count = 0, n_out = 0 launch nothing. */
+#define TIP_RESAMPLE_HOLD  0
+#define TIP_RESAMPLE_SLERP 1
+TIP_API int tip_resample_tile(int* rows);
+TIP_API int tip_resample_state_bytes(int n_slots, int depth, size_t* bytes);
+TIP_API int tip_resample_reset(void* state, int n_slots, int depth, const int* slots /* or null: all */, int count, tip_stream_t stream);
+TIP_API int tip_resample_push(void* state, int n_slots, int depth, const float* packets /* [m,42] */, const int* slots /* [m] */,
+                      const double* times /* [m] */, int m, tip_stream_t stream);
+TIP_API int tip_resample_emit(void* state, int n_slots, int depth, const double* t /* device [n] */, double delay, double max_hold,
+                      int mode, float* packets_out /* [n,42] */, unsigned char* flags /* [n] */, tip_stream_t stream);
+TIP_API int tip_resample_get(const void* state, int n_slots, int depth, const int* slots, int count, int* counts_out /* [count,3] */,
+                     tip_stream_t stream);
+TIP_API int tip_resample_rows(const float* packets /* [n_in,42] */, const double* stamps /* [n_in] */,
+                      const long long* in_offsets /* [n_seq+1] */, long long n_in, const double* t_out /* [n_out] */,
+                      const long long* out_offsets /* [n_seq+1] */, long long n_out, int n_seq, double delay, double max_hold, int mode,
+                      int depth, float* packets_out /* [n_out,42] */, unsigned char* flags /* [n_out] */, tip_stream_t stream);
+
 /* ---- kinematics: forward kinematics of the character, the root track with its SBP correction, and the evaluation script's seven
  *      metrics — what the reference does through PyBullet behind RTRunnerMin.step (real_time_runner_minimal.py:159-194;
  *      data_utils.py:262-306, 397-412, 473-548) and in offline_testing_simple.py --compare_gt (:422-453; data_utils.py:314-391).

@@ -31,6 +31,7 @@ TIP_ERR_HANDOFF = -8
 TIP_ERR_UNSUPPORTED_CONFIG = -2
 TIP_LOSS_Q, TIP_LOSS_C, TIP_LOSS_J, TIP_LOSS_STATS = 1, 2, 4, 16
 TIP_SENSOR_HEADING, TIP_SENSOR_TPOSE = 1, 2   # tip_sensor_begin: which hold starts
+TIP_RESAMPLE_HOLD, TIP_RESAMPLE_SLERP = 0, 1   # tip_resample_emit / tip_resample_rows: mode
 
 # every symbol include/tip_hip.h declares (tests check that the .so exports exactly these + the hooks of tip_hip_debug.h)
 EXPORTS = (
@@ -49,6 +50,8 @@ EXPORTS = (
     "tip_sensor_state_bytes", "tip_sensor_reset", "tip_sensor_begin", "tip_sensor_accumulate", "tip_sensor_finish", "tip_sensor_set",
     "tip_sensor_get", "tip_sensor_transform",
     "tip_fill_real", "tip_fill_rows", "tip_fill_state_bytes", "tip_fill_reset", "tip_fill_live", "tip_fill_get", "tip_fill_packets",
+    "tip_resample_tile", "tip_resample_state_bytes", "tip_resample_reset", "tip_resample_push", "tip_resample_emit", "tip_resample_get",
+    "tip_resample_rows",
     "tip_kin_skel_bytes", "tip_kin_carry_bytes", "tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_kin_metrics",
     "tip_terrain_state_bytes", "tip_terrain_reset", "tip_terrain_track",
     "tip_kin_fk_scaled", "tip_kin_track_reset_scaled", "tip_kin_track_scaled", "tip_terrain_reset_scaled", "tip_terrain_track_scaled",
@@ -206,6 +209,15 @@ def load() -> ctypes.CDLL:
     lib.tip_fill_live.argtypes = [vp, vp, vp, i32, i32, vp, vp]
     lib.tip_fill_get.argtypes = [vp, i32, vp, i32, vp, vp]
     lib.tip_fill_packets.argtypes = [vp, vp, ctypes.c_longlong, vp, i32, ctypes.c_float, vp, vp]
+    # timestamped packets (csrc/tip_resample.hip): state, n, depth first; stamps, query times, delay and max_hold are fp64
+    f64 = ctypes.c_double
+    lib.tip_resample_tile.argtypes = [ctypes.POINTER(i32)]
+    lib.tip_resample_state_bytes.argtypes = [i32, i32, ctypes.POINTER(sz)]
+    lib.tip_resample_reset.argtypes = [vp, i32, i32, vp, i32, vp]
+    lib.tip_resample_push.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
+    lib.tip_resample_emit.argtypes = [vp, i32, i32, vp, f64, f64, i32, vp, vp, vp]
+    lib.tip_resample_get.argtypes = [vp, i32, i32, vp, i32, vp, vp]
+    lib.tip_resample_rows.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.c_longlong, i32, f64, f64, i32, i32, vp, vp, vp]
     # kinematics (csrc/tip_kin.hip): the skeleton table, then what the header lists, then the stream
     lib.tip_kin_skel_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_kin_carry_bytes.argtypes = [i32, ctypes.POINTER(sz)]

@@ -24,6 +24,16 @@ recordings (preprocess_DIP_TC_new.py:112-136, :160-180).  real_imu_frames is tha
 tip_amd.data.combine_motions takes as "imu"); SensorFrontEnd(fill=True) is its live form (rule V: a ring of the last five rows after
 filling, per sensor and part), one launch behind the transform; fill_sequences and transform_sequences do the same to recorded frames
 and recorded packet sessions, frame for frame what the live front end gives, as recordings for tip_amd.replay.ReplayPool.
+
+Timestamped packets (csrc/tip_resample.hip; include/tip_hip.h, "timestamped packets"): everything above takes one packet per slot per
+60 Hz frame, all wearers in step.  The demo gets there with a zero-order hold for its one wearer (live_demo_new.py:82-115, :161-162).
+PacketResampler is that for a pool, on the device: packets arrive with fp64 stamps at whatever rate each wearer's sensors send,
+emit(t) gives every slot its packet at the tick — held, or interpolated between the two packets around t - delay — and the result
+is the [n, 42] every method above and every engine's step_packets take; resample_sequences is the same for recorded sessions.
+
+    rs = PacketResampler(n, "cuda", mode="slerp", delay=1 / 100, max_hold=0.1)      # 100 Hz sensors: one period of delay
+    rs.push(packets, slots, times)                                                  # whatever arrived since the last tick
+    out = engine.step_packets(front, rs.emit(t))                                    # t: the tick, a number or [n]; rs.flags says how
 """
 from __future__ import annotations
 
@@ -448,3 +458,285 @@ def transform_sequences(packets_list, tables, fill=False, max_acc=10.0, max_gap=
         if fill:
             _status(lib, lib.tip_fill_rows(out.data_ptr(), out.data_ptr(), N, offs.data_ptr(), len(lens), gap, flags.data_ptr(), stream))
     return _recordings(out, flags, lens, host, return_flags)
+
+
+# ---- timestamped packets: every wearer resampled to the tick grid ----------------------------------------------------------------------
+MODES = {"hold": _lib.TIP_RESAMPLE_HOLD, "slerp": _lib.TIP_RESAMPLE_SLERP}
+# what emit says about a slot's row: interpolated; a packet held (copied bit for bit); NaN because the packet to hold is older than
+# max_hold; NaN because the ring is empty; NaN because t - delay is before the ring's oldest packet
+INTERPOLATED, HELD, STALE, EMPTY, EARLY = range(5)
+
+
+def _resample_rule(mode, delay, max_hold, depth, who):
+    """(mode, delay, max_hold, depth) as the C ABI takes them; anything else is a ValueError in `who`'s name."""
+    if mode not in MODES:
+        raise ValueError(f"tip_amd.sensors.{who}: mode is \"slerp\" or \"hold\"; got {mode!r}")
+    try:
+        delay = float(delay)
+    except (TypeError, ValueError):
+        delay = float("nan")
+    if not (delay >= 0.0 and np.isfinite(delay)):
+        raise ValueError(f"tip_amd.sensors.{who}: delay is the age of the emitted packet in seconds, a finite number >= 0 (nothing is "
+                         f"extrapolated past the newest packet); got {delay!r}")
+    if max_hold is None:
+        hold = -1.0
+    else:
+        try:
+            hold = float(max_hold)
+        except (TypeError, ValueError):
+            hold = float("nan")
+        if not hold >= 0.0:
+            raise ValueError(f"tip_amd.sensors.{who}: max_hold is None (no limit) or the oldest packet that may be held, in seconds "
+                             f">= 0; got {max_hold!r}")
+    if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 2 <= depth <= 64:
+        raise ValueError(f"tip_amd.sensors.{who}: depth is the number of packets a slot keeps, an int in 2 .. 64; got {depth!r}")
+    return MODES[mode], delay, hold, int(depth)
+
+
+def tick_times(t0, count, rate_hz=60.0):
+    """The tick grid: float64 [count], t0 + k * (1.0 / rate_hz) — a product, not a running sum, so tick k is the same number wherever
+    it is computed."""
+    if isinstance(count, bool) or not isinstance(count, (int, np.integer)) or count < 0:
+        raise ValueError(f"tip_amd.sensors.tick_times: count is a number of ticks >= 0; got {count!r}")
+    rate, t0 = float(rate_hz), float(t0)
+    if not (rate > 0.0 and np.isfinite(rate)) or not np.isfinite(t0):
+        raise ValueError(f"tip_amd.sensors.tick_times: t0 is finite and rate_hz a finite number > 0; got {t0!r}, {rate_hz!r}")
+    return t0 + np.arange(int(count), dtype=np.float64) * (1.0 / rate)
+
+
+def _times_f64(t, what):
+    """Stamps or query times as a float64 tensor.  Anything that is no tensor goes through numpy as float64 (torch reads a list of
+    Python floats as float32: 1.7e9 + 0.123 would become 1.7e9); a tensor must be float64 or of an integer type."""
+    if not isinstance(t, torch.Tensor):
+        if isinstance(t, (np.ndarray, np.generic)) and t.dtype.kind == "f" and t.dtype.itemsize < 8:
+            raise ValueError(f"{what} are float64 seconds; a {t.dtype} array has already lost them (1.7e9 s in float32 resolves 128 s)")
+        try:
+            return torch.from_numpy(np.asarray(t, dtype=np.float64, order="C"))
+        except (TypeError, ValueError):
+            raise ValueError(f"{what} are seconds, numbers read as float64; got {type(t).__name__}") from None
+    if t.dtype == torch.float64:
+        return t
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"{what} are float64 seconds; a {t.dtype} tensor has already lost them (1.7e9 s in float32 resolves 128 s)")
+    return t.to(torch.float64)
+
+
+def _tick_rule(rate_hz, delay, who):
+    """(rate_hz, delay) of a tick grid as floats; anything else is a ValueError in `who`'s name."""
+    try:
+        rate, delay = float(rate_hz), float(delay)
+    except (TypeError, ValueError):
+        rate, delay = float("nan"), float("nan")
+    if not (rate > 0.0 and np.isfinite(rate)):
+        raise ValueError(f"tip_amd.sensors.{who}: rate_hz is the tick rate, a finite number > 0; got {rate_hz!r}")
+    if not (delay >= 0.0 and np.isfinite(delay)):
+        raise ValueError(f"tip_amd.sensors.{who}: delay is a finite number of seconds >= 0; got {delay!r}")
+    return rate, delay
+
+
+class PacketResampler:
+    """n rings of the last `depth` packets with their fp64 stamps on `device`, and the per-tick launch that gives every slot its
+    packet at the tick (csrc/tip_resample.hip).  mode "hold": the newest packet not after t - delay, the demo's rule at delay 0;
+    "slerp": interpolated between the two packets around t - delay (quaternions on the shorter arc, accelerations linearly in the
+    global frame), which needs a delay of about one sensor period to have a later packet.  max_hold (seconds; None: no limit): a packet
+    older than that is not held and nothing is interpolated across a longer gap — the slot gets a NaN row, which fill=True of the front
+    end fills or the engines' NaN contract takes.  No call synchronises; everything runs on the current stream."""
+
+    def __init__(self, n: int, device, *, mode: str = "slerp", delay: float = 0.0, max_hold=None, depth: int = 8):
+        who = "PacketResampler"
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"tip_amd.sensors.{who}: n is the number of slots, at least 1; got {n!r}")
+        self.n = int(n)
+        self.mode_name = mode
+        self.mode, self.delay, self.max_hold, self.depth = _resample_rule(mode, delay, max_hold, depth, who)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("tip_amd.sensors.PacketResampler runs on an MI355X: give it the engine's device")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = _lib.load()
+        nbytes = ctypes.c_size_t()
+        _status(self.lib, self.lib.tip_resample_state_bytes(self.n, self.depth, ctypes.byref(nbytes)))
+        self.state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        self.t = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+        self.flags = torch.full((self.n,), EMPTY, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _status(self.lib, self.lib.tip_resample_reset(self.state.data_ptr(), self.n, self.depth, None, 0, self._stream()))
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _slots(self, slots, who):
+        return list(range(self.n)) if slots is None else slot_list(slots, self.n, f"sensors.PacketResampler.{who}")
+
+    def push(self, packets, slots, times):
+        """m arrivals: packets [m, 42] float32, slots [m] (an arrival for a slot outside [0, n) is skipped), times [m] float64 seconds.
+        The arrivals of one slot are taken in array order; one whose stamp is not finite or not above the slot's newest is dropped and
+        counted.  Host inputs go up in ONE non-blocking copy from pinned memory; CUDA tensors are used where they lie.  times that are
+        no tensor (lists, numpy arrays) are read as float64 whatever they hold; a tensor of a narrower float type is refused: at an
+        epoch-sized stamp float32 has already lost the packet's time."""
+        who = "tip_amd.sensors.PacketResampler.push"
+        args = [torch.as_tensor(packets), torch.as_tensor(slots), _times_f64(times, f"{who}: times")]
+        m = int(args[1].numel())
+        if args[0].dim() != 2 or tuple(args[0].shape) != (m, PACKET) or args[1].dim() != 1 or tuple(args[2].shape) != (m,):
+            raise ValueError(f"{who}: packets is [m, {PACKET}], slots [m] and times [m]; got {tuple(args[0].shape)}, "
+                             f"{tuple(args[1].shape)}, {tuple(args[2].shape)}")
+        if m == 0:
+            return
+        if args[1].dtype.is_floating_point or args[1].dtype == torch.bool:
+            raise ValueError(f"{who}: slots are integers; got {args[1].dtype}")
+        dtypes = (torch.float32, torch.int32, torch.float64)
+        with torch.cuda.device(self.device):
+            if not any(a.is_cuda for a in args):
+                # times | packets | slots in one pinned image: 8 m + 168 m + 4 m bytes, every part aligned to its type
+                image = torch.empty(180 * m, dtype=torch.uint8).pin_memory()
+                image[: 8 * m].view(torch.float64).copy_(args[2].reshape(m))
+                image[8 * m: 176 * m].view(torch.float32).copy_(args[0].reshape(-1))
+                image[176 * m:].view(torch.int32).copy_(args[1].reshape(m))
+                dev = image.to(self.device, non_blocking=True)
+                t, p, s = dev[: 8 * m].view(torch.float64), dev[8 * m: 176 * m].view(torch.float32), dev[176 * m:].view(torch.int32)
+            else:
+                p, s, t = (_to(a.to(d), self.device).contiguous() for a, d in zip(args, dtypes))
+            _status(self.lib, self.lib.tip_resample_push(self.state.data_ptr(), self.n, self.depth, p.data_ptr(), s.data_ptr(), t.data_ptr(),
+                                                         m, self._stream()))
+
+    def emit(self, t, out=None):
+        """Every slot's packet at tick t -> a CUDA float32 [n, 42] (`out`, or a new tensor); `flags` [n] uint8 says how each row came
+        about (INTERPOLATED, HELD, STALE, EMPTY, EARLY; the last three are NaN rows).  t: a number or anything 0-d (one tick for the
+        pool), or [n]; lists and numpy arrays are read as float64, a tensor of a narrower float type is refused.  A CUDA float64 [n]
+        tensor is read WHERE IT LIES, which is what a captured frame needs: it must be contiguous and on this device, else it is
+        refused rather than copied behind the caller's back.  Everything else goes through the resampler's own buffer `t`."""
+        who = "tip_amd.sensors.PacketResampler.emit"
+        if out is None:
+            out = torch.empty((self.n, PACKET), dtype=torch.float32, device=self.device)
+        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32
+              or tuple(out.shape) != (self.n, PACKET) or not out.is_contiguous()):
+            raise ValueError(f"{who}: out is a contiguous float32 [{self.n}, {PACKET}] tensor on {self.device}")
+        if isinstance(t, bool):
+            raise ValueError(f"{who}: t is a number or [{self.n}] times in seconds; got {t!r}")
+        h = _times_f64(t, f"{who}: t")
+        if h.dim() > 1 or (h.dim() == 1 and tuple(h.shape) != (self.n,)):
+            raise ValueError(f"{who}: t is a number or [{self.n}] times in seconds; got {tuple(h.shape)}")
+        if h.is_cuda and h.dim() == 1 and isinstance(t, torch.Tensor) and t.dtype == torch.float64:
+            if h.device != self.device or not h.is_contiguous():
+                raise ValueError(f"{who}: a CUDA float64 [{self.n}] tensor is read where it lies: it must be contiguous and on {self.device}")
+            tq = h
+        else:
+            tq = self.t
+            if h.dim() == 0 and not h.is_cuda:
+                tq.fill_(float(h))
+            else:                                                 # (a 0-d value is broadcast)
+                tq.copy_(h if h.is_cuda else h.contiguous().pin_memory(), non_blocking=True)
+        with torch.cuda.device(self.device):
+            _status(self.lib, self.lib.tip_resample_emit(self.state.data_ptr(), self.n, self.depth, tq.data_ptr(), self.delay, self.max_hold,
+                                                         self.mode, out.data_ptr(), self.flags.data_ptr(), self._stream()))
+        return out
+
+    def reset(self, slots=None):
+        """Empty the rings and zero the counters of the listed slots (None: all): a slot that takes a new wearer."""
+        idx = self._slots(slots, "reset")
+        if not idx:
+            return
+        with torch.cuda.device(self.device):
+            sl = _to(torch.tensor(idx, dtype=torch.int32), self.device)
+            _status(self.lib, self.lib.tip_resample_reset(self.state.data_ptr(), self.n, self.depth, sl.data_ptr(), len(idx), self._stream()))
+
+    def counts(self, slots=None):
+        """(have, dropped, total) of the listed slots (None: all), three CUDA int32 tensors [len(slots)]: packets in the ring
+        (0 .. depth), packets refused for their stamp, packets taken since the last reset."""
+        idx = self._slots(slots, "counts")
+        out = torch.zeros((len(idx), 3), dtype=torch.int32, device=self.device)
+        if idx:
+            with torch.cuda.device(self.device):
+                sl = _to(torch.tensor(idx, dtype=torch.int32), self.device)
+                _status(self.lib, self.lib.tip_resample_get(self.state.data_ptr(), self.n, self.depth, sl.data_ptr(), len(idx), out.data_ptr(),
+                                                            self._stream()))
+        return out[:, 0], out[:, 1], out[:, 2]
+
+
+def _sequence_times(times_list, lens, who):
+    """times_list as host float64 arrays, one per sequence, each finite and strictly increasing; a bad one is a ValueError naming the
+    sequence and the row."""
+    if len(times_list) != len(lens):
+        raise ValueError(f"tip_amd.sensors.{who}: {len(lens)} packet arrays for {len(times_list)} time arrays")
+    out = []
+    for i, (t, L) in enumerate(zip(times_list, lens)):
+        if isinstance(t, torch.Tensor):
+            t = t.detach().cpu().numpy()
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        if t.shape != (L,):
+            raise ValueError(f"tip_amd.sensors.{who}: times_list[{i}] is [{L}], one stamp per packet row; got {t.shape}")
+        bad = np.flatnonzero(~np.isfinite(t))
+        if bad.size:
+            raise ValueError(f"tip_amd.sensors.{who}: times_list[{i}] row {int(bad[0])} is not finite")
+        bad = np.flatnonzero(~(np.diff(t) > 0.0))
+        if bad.size:
+            raise ValueError(f"tip_amd.sensors.{who}: times_list[{i}] row {int(bad[0]) + 1} is not after row {int(bad[0])} "
+                             "(stamps are strictly increasing)")
+        out.append(t)
+    return out
+
+
+def sequence_ticks(times, rate_hz=60.0, delay=0.0, t_start=None):
+    """The ticks resample_sequences takes a sequence at (host, float64): tick_times from t_start (None: the first stamp + delay, the
+    first tick with something to give) while tick - delay <= the last stamp, so that every row has a packet at or after it.
+    rate_hz, delay and t_start are checked as resample_sequences checks them; times [L] is the sequence's (ascending) stamps."""
+    who = "sequence_ticks"
+    rate_hz, delay = _tick_rule(rate_hz, delay, who)
+    times = np.asarray(times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else times, dtype=np.float64)
+    if times.ndim != 1:
+        raise ValueError(f"tip_amd.sensors.{who}: times is [L], a sequence's stamps; got {times.shape}")
+    if times.size == 0:
+        return np.empty(0, dtype=np.float64)
+    if not (np.isfinite(times[0]) and np.isfinite(times[-1])) or (t_start is not None and not np.isfinite(float(t_start))):
+        raise ValueError(f"tip_amd.sensors.{who}: the stamps and t_start are finite; got {times[0]!r} .. {times[-1]!r}, {t_start!r}")
+    t0 = float(times[0]) + delay if t_start is None else float(t_start)
+    most = int(np.floor(max((float(times[-1]) + delay - t0) * rate_hz, -1.0))) + 2
+    ticks = tick_times(t0, max(most, 0), rate_hz)
+    return ticks[ticks - delay <= times[-1]]
+
+
+def resample_sequences(packets_list, times_list, rate_hz=60.0, *, mode="slerp", delay=0.0, max_hold=None, depth=8, t_start=None,
+                       device=None, host=False):
+    """Recorded packet sessions whose stamps are not on the grid -> sessions that are: packets_list[i] is [L_i, 42] float32 and
+    times_list[i] its stamps [L_i] (host float64; finite and strictly increasing, else a ValueError naming the sequence and the row).
+    Sequence i is taken at sequence_ticks(times_list[i], rate_hz, delay, t_start) — t_start None, a number, or one number per sequence —
+    and every output row is what a PacketResampler(mode, delay, max_hold, depth) that was pushed everything stamped up to the row's
+    tick emits there, bit for bit, all sequences in one launch.  Returns (packets, flags): lists of CUDA float32 [K_i, 42] and uint8
+    [K_i] (host=True: numpy arrays).  The packets are what transform_sequences takes."""
+    who = "resample_sequences"
+    mode_c, delay, hold, depth = _resample_rule(mode, delay, max_hold, depth, who)
+    rate = float(rate_hz)
+    if not (rate > 0.0 and np.isfinite(rate)):
+        raise ValueError(f"tip_amd.sensors.{who}: rate_hz is the tick rate, a finite number > 0; got {rate_hz!r}")
+    if not len(packets_list):
+        raise ValueError(f"tip_amd.sensors.{who}: no sequences")
+    lens = []
+    for i, p in enumerate(packets_list):
+        shape = tuple(p.shape) if hasattr(p, "shape") else np.shape(p)
+        if len(shape) != 2 or shape[1] != PACKET:
+            raise ValueError(f"tip_amd.sensors.{who}: packets_list[{i}] is [L, {PACKET}]; got {shape}")
+        lens.append(int(shape[0]))
+    times = _sequence_times(times_list, lens, who)
+    if t_start is None or np.ndim(t_start) == 0:
+        starts = [t_start] * len(lens)
+    else:
+        starts = [float(v) for v in np.asarray(t_start, dtype=np.float64).reshape(-1)]
+        if len(starts) != len(lens):
+            raise ValueError(f"tip_amd.sensors.{who}: t_start is None, a number or one number per sequence; got {len(starts)} for {len(lens)}")
+    ticks = [sequence_ticks(t, rate, delay, s) for t, s in zip(times, starts)]
+    out_lens = [int(t.shape[0]) for t in ticks]
+    dev = _device_of(list(packets_list), device)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        packets, in_off, _ = _stack(packets_list, torch.float32, PACKET, dev, who, "packets_list")
+        stamps = _to(torch.from_numpy(np.concatenate(times)), dev)
+        t_out = _to(torch.from_numpy(np.concatenate(ticks)), dev)
+        out_off = _to(torch.tensor(np.concatenate(([0], np.cumsum(out_lens))), dtype=torch.int64), dev)
+        K = int(sum(out_lens))
+        out = torch.empty((K, PACKET), dtype=torch.float32, device=dev)
+        flags = torch.empty(K, dtype=torch.uint8, device=dev)
+        _status(lib, lib.tip_resample_rows(packets.data_ptr(), stamps.data_ptr(), in_off.data_ptr(), int(packets.shape[0]), t_out.data_ptr(),
+                                           out_off.data_ptr(), K, len(lens), delay, hold, mode_c, depth, out.data_ptr(), flags.data_ptr(),
+                                           torch.cuda.current_stream(dev).cuda_stream))
+    return _recordings(out, flags, out_lens, host, True)
