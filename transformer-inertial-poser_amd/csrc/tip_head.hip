@@ -23,7 +23,7 @@
 // A row's summation order depends on the tile kind only (B: per wave one MFMA chain over its 16 k-steps; T: four chains, one
 // per lg, combined (p0 + p2) + (p1 + p3); then the eight waves ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7))).  In MODE 0 row
 // t of a window is a T row iff t mod 40 >= 32, so row T - 1 always is: MODE 2 reproduces it bit for bit (forward_last ==
-// forward[:, -1], tested).  Other window lengths keep head_gemm_kernel in both forms.
+// forward[:, -1], tested).  Other window lengths, and state widths outside 129 .. 131, keep head_gemm_kernel in both forms.
 #include "tip_head.h"
 
 namespace tip {
@@ -69,7 +69,9 @@ extern "C" int tip_debug_read_head_trace(unsigned long long* out, int n) {
 hipError_t launch_head_ksplit(const float* A, long long lda, const float* wfrag, const float* bias, float* Y, int ldy, int M, int N,
                               int K, bool last_only, int num_cus, hipStream_t s, const int* rows, int rows_T) {
     if (M <= 0) return hipSuccess;
-    if (K != 512 || N <= 128 || N > 144) return hipErrorInvalidValue;
+    // Column block 8 keeps THREE columns (128 .. 130) in its compact image (hd::C8_FLOATS, c8_reduce): N = 129 .. 131 only.  Up to 144
+    // columns were accepted here once, and columns 131 .. N - 1 were never stored (tests/test_paper_width_shapes_gpu.py, size_s 143).
+    if (K != 512 || N <= 128 || N > 131) return hipErrorInvalidValue;
     if (rows) {
         // A = the first row of window 0, lda = the row stride, M = windows: both tile kinds, each storing its own rows
         if (rows_T < 1 || rows_T % 40 || lda * 4 > 0x7fffffffLL || ((long long)M * rows_T - 1) * lda + K > 0x1fffffffLL ||

@@ -532,7 +532,7 @@ bool rnn_uses_sentinel(const Dims& d, int B, int T, int cluster);
 hipError_t launch_head_gemm(const float* A, long long lda, const float* wfrag, const float* bias, float* Y, int ldy,
                             int M, int N, int K, hipStream_t s, const int* rows = nullptr, int rows_T = 0);
 
-// the same product with the weight resident in registers (tip_head.hip): K = 512, 128 < N <= 144, window length a multiple of 40
+// the same product with the weight resident in registers (tip_head.hip): K = 512, 128 < N <= 131, window length a multiple of 40
 // (full output: M a multiple of 40; last_only: M = one row per window, bit-identical to row T-1 of the full output).
 // hipErrorInvalidValue = shape not served (nothing launched).
 // rows: as launch_head_gemm's (two launches, one per tile kind: every row keeps the bits the full output gives it; rows_T a multiple of 40)
