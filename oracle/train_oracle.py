@@ -54,7 +54,7 @@ def drop_scale(seed: int, site: int, n: int, p: float, idx=None) -> np.ndarray:
 
 
 def forward(cfg: dict, params: "dict[str, torch.Tensor]", x_imu, x_s, keep_mask=None, keep_scale=1.0, p_drop=0.0, seed=0,
-            dtype=torch.float64, relu_gates=None, window_ids=None):
+            dtype=torch.float64, relu_gates=None, window_ids=None, gates_out=None):
     """y [B,T,size_s] with autograd attached to `params` (fp64 leaf tensors).  x_imu/x_s: numpy fp32, or torch tensors of `dtype`
     (leaves that may require grad: gradients w.r.t. the inputs; d x_s is zero where x_s is NaN, as nan_to_num's derivative).
 
@@ -62,6 +62,8 @@ def forward(cfg: dict, params: "dict[str, torch.Tensor]", x_imu, x_s, keep_mask=
     pre-activation is within fp32 rounding of zero may be open in one implementation and closed in another, and either
     choice is a valid (sub)gradient.  When the gates of the implementation under test are passed, the oracle
     differentiates the SAME linear piece, so the comparison is not polluted by such flips.
+    gates_out: optional list; the L boolean arrays [B,T,F] of THIS run's open hidden units are appended to it (what to pass as
+    relu_gates to a run of another precision).
 
     window_ids: optional positions (int array of B) of the given windows in a larger batch.  The encoder dropout masks are then
     those the kernels draw for these windows in that batch: the hash of the FULL-batch element index, per site
@@ -108,6 +110,8 @@ def forward(cfg: dict, params: "dict[str, torch.Tensor]", x_imu, x_s, keep_mask=
         z = torch.nn.functional.layer_norm(z + a * site(l, 1, (B, T, D)), (D,), params[p + "norm1.weight"],
                                            params[p + "norm1.bias"], 1e-5)
         f = torch.nn.functional.linear(z, params[p + "linear1.weight"], params[p + "linear1.bias"])
+        if gates_out is not None:
+            gates_out.append((f.detach() > 0).numpy() if relu_gates is None else np.asarray(relu_gates[l]).reshape(B, T, F_) > 0)
         f = torch.relu(f) if relu_gates is None else f * torch.tensor(np.asarray(relu_gates[l]).reshape(B, T, F_), dtype=dtype)
         f = torch.nn.functional.linear(f * site(l, 2, (B, T, F_)), params[p + "linear2.weight"], params[p + "linear2.bias"])
         z = torch.nn.functional.layer_norm(z + f * site(l, 3, (B, T, D)), (D,), params[p + "norm2.weight"],
@@ -124,7 +128,7 @@ def forward(cfg: dict, params: "dict[str, torch.Tensor]", x_imu, x_s, keep_mask=
 
 
 def step(cfg, weights: "dict[str, np.ndarray]", x_imu, x_s, cot, keep_mask=None, keep_scale=1.0, p_drop=0.0, seed=0,
-         relu_gates=None, window_ids=None, input_grads=False, dtype=torch.float64):
+         relu_gates=None, window_ids=None, input_grads=False, dtype=torch.float64, gates_out=None):
     """(y, grads) of loss = sum(y * cot): what `loss.backward()` leaves in .grad for that loss.
     input_grads: also return (d x_imu, d x_s) as a third element.  window_ids: see forward.  dtype: float32 gives the
     reference's own fp32 rounding noise at a shape (what a tolerance above the fp64 default has to be justified by)."""
@@ -134,7 +138,7 @@ def step(cfg, weights: "dict[str, np.ndarray]", x_imu, x_s, cot, keep_mask=None,
         xi = torch.tensor(np.asarray(x_imu), dtype=dtype, requires_grad=True)
         xs = torch.tensor(np.asarray(x_s), dtype=dtype, requires_grad=True)
     y = forward(cfg, params, xi, xs, keep_mask, keep_scale, p_drop, seed, dtype=dtype, relu_gates=relu_gates,
-                window_ids=window_ids)
+                window_ids=window_ids, gates_out=gates_out)
     (y * torch.tensor(np.asarray(cot), dtype=dtype)).sum().backward()
     grads = {k: v.grad.numpy() for k, v in params.items()}
     if input_grads:
