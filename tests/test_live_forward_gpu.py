@@ -117,6 +117,32 @@ def test_same_decisions_as_the_training_forward():
     m.check_handoffs()
 
 
+@pytest.mark.parametrize("T", [40, 7])
+@pytest.mark.parametrize("B", [1, 24, 25])
+def test_dropout_entry_point_is_the_live_one_on_the_few_stream_plan(B, T):
+    """tip_forward_dropout and tip_forward_live(rows = seeds_dev = NULL) are one body: the same bits on the same handle, seeds and full
+    output — in the one-launch form (B = 1, 24) and on the launch chain (B = 25)."""
+    cfg = synth.PAPER
+    m, _ = _model(cfg)
+    m.refresh_packed()
+    h = m._ensure_handle()
+    x_imu, x_s = synth.make_inputs(cfg, B, T, seed=77 + B)
+    xi, xs = torch.tensor(x_imu).cuda(), torch.tensor(x_s).cuda()
+    ws = torch.empty(m.workspace_bytes(B, T), dtype=torch.uint8, device="cuda")
+    y_drop, y_live = (torch.full((B, T, cfg["size_s"]), float("nan"), device="cuda") for _ in range(2))
+    stream = torch.cuda.current_stream().cuda_stream
+    scale = 1.0 / (1.0 - _f32(P_STATE))
+    n0 = m.hip_forward_count()
+    h.forward_dropout(xi.data_ptr(), xs.data_ptr(), y_drop.data_ptr(), B, T, 0, None, scale, P_STATE, SEEDS[1], P_DROP, SEEDS[0],
+                      ws.data_ptr(), ws.numel(), stream)
+    h.forward_live(xi.data_ptr(), xs.data_ptr(), y_live.data_ptr(), B, T, None, 0, None, scale, P_STATE, SEEDS[1], P_DROP, SEEDS[0], None,
+                   ws.data_ptr(), ws.numel(), stream)
+    torch.cuda.synchronize()
+    assert m.hip_forward_count() == n0 + 2
+    assert torch.isfinite(y_drop).all() and torch.equal(y_drop, y_live)
+    m.check_handoffs()
+
+
 @pytest.mark.parametrize("B", [5, 70])
 def test_seeds_through_device_memory(B):
     """seeds_dev == the same values by argument, bit for bit, on both plans; tip_seeds_next leaves the documented successors (computed

@@ -207,6 +207,41 @@ def test_reuse_is_refused_where_it_would_not_be_exact():
             m3.forward_last_reuse(xi[:, :1, :80], xs[:, :1], ring, 0)
 
 
+def test_reuse_rejects_bad_out_and_workspace_before_any_launch():
+    """out= and workspace= of forward_last_reuse are held to forward_last's checks: nothing is launched, nothing behind a wrong-shaped
+    `out` is written, and the next valid call is the recomputing forward's bits."""
+    cfg, B, T, S = synth.PAPER, 2, 40, 131
+    m = _model()
+    x_imu, x_s = synth.make_inputs(cfg, B, T, seed=5)
+    xi, xs = torch.tensor(x_imu).cuda(), torch.tensor(x_s).cuda()
+    ring = m.reuse_cache(B)
+    need = m.workspace_bytes(B, T)
+    SENTINEL = -7.25
+    block = torch.full((4 * S,), SENTINEL, device="cuda")            # a [3, 131] `out` and a guard row right behind it
+    short = torch.empty(need - 1, dtype=torch.uint8, device="cuda")
+    skewed = torch.empty(need + 256, dtype=torch.uint8, device="cuda")[128:]
+    assert skewed.data_ptr() % 256 == 128
+    good_ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+    with torch.no_grad():
+        for f in range(T - 1):                                        # frames 0 .. 38 enter the ring while the windows grow
+            m.forward_last_reuse(xi[:, :f + 1], xs[:, :f + 1], ring, f)
+        n0 = m.hip_forward_count()
+        for kw in (dict(out=block[:3 * S].view(3, S)), dict(out=torch.empty((B, S), dtype=torch.float64, device="cuda")),
+                   dict(workspace=short), dict(workspace=skewed)):
+            with pytest.raises(RuntimeError, match="out=|workspace="):
+                m.forward_last_reuse(xi, xs, ring, T - 1, **kw)
+        torch.cuda.synchronize()
+        assert m.hip_forward_count() == n0
+        assert bool((block == SENTINEL).all())
+        y = m.forward_last_reuse(xi, xs, ring, T - 1, workspace=good_ws, out=torch.empty((B, S), device="cuda"))
+        m.set_plan("fused2")
+        y_ref = m.forward_last(xi, xs)
+        m.set_plan("auto")
+    torch.cuda.synchronize()
+    assert torch.isfinite(y).all() and torch.equal(y, y_ref)
+    m.check_handoffs()
+
+
 def test_reuse_auto_engages_only_where_it_pays_and_is_exact():
     """reuse="auto": on where the two-window encoder is AUTO's plan anyway (>= two windows per CU) and the model has no stochastic
     part; off (silently: it is an optimisation, not a request) everywhere else."""

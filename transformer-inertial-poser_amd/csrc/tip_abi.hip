@@ -628,33 +628,67 @@ static int run_tail(LaunchSeq& q) {
 #undef TIP_STAGE
 #undef TIP_TRY
 
+// What every forward entry point settles before its first launch (forward_prepare)
+struct ForwardPrep {
+    hipStream_t s;
+    int cus;              // the stream's CU mask counts, not the device's CU total
+    Workspace ws;         // the carve-up for all B windows
+    const float* mask;    // null: no keep mask from the caller
+    float keep_scale;     // 1 unless a keep mask is applied — the caller's, or one drawn inside the first kernel (`mask_drawn`)
+    bool few;             // the few-stream latency plan serves this call (live entry points)
+};
+// plans an entry point runs on: what schedule_forward picks after the preamble (tip_forward / _rows / _reuse), the few-stream latency
+// plan only (tip_forward_dropout), or that plan where it serves and the hybrid encoder's live mode elsewhere (tip_forward_live)
+enum ForwardServe { kServeScheduled, kServeFewOnly, kServeLive };
+
+// The preamble of every forward entry point: argument, readiness and hand-off checks, the B == 0 exit, the entry point's plan-support
+// test, the workspace, then stream and CU count.  True: go on and launch with *p.  False: return *status (TIP_OK for an empty batch).
+static bool forward_prepare(tip_handle* h, const float* x_imu, const float* x_s, const float* y, int B, int T, int flags, const float* keep_mask,
+                            float keep_scale, bool mask_drawn, void* workspace, size_t workspace_bytes, tip_stream_t stream,
+                            ForwardServe serve, ForwardPrep* p, int* status) {
+    auto stop = [&](int st) { *status = st; return false; };
+    if (!h || !x_imu || !x_s || !y || B < 0 || T < 1) return stop(TIP_ERR_INVALID_ARG);
+    const Dims& d = h->d;
+    // (cfg.t_max is a sizing hint, not a limit: the reference builds its causal mask for any window length, :56-58,85; what
+    // bounds B * T here are the 32-bit byte offsets of the buffer descriptors)
+    if ((long long)B * T * (long long)std::max(std::max(3 * d.D, d.F), std::max(d.R, d.InPad)) * 4 > 0x7fffffffLL)
+        return stop(TIP_ERR_UNSUPPORTED_CONFIG);
+    if ((flags & TIP_FWD_KEEP_MASK) && !keep_mask) return stop(TIP_ERR_INVALID_ARG);
+    if (!h->packed_dev) return stop(TIP_ERR_NOT_READY);
+    if (tip_check(h, 0) != TIP_OK) return stop(TIP_ERR_HANDOFF);   // sticky: an earlier launch lost a hand-off (tip_check(h, 1) clears)
+    if (B == 0) return stop(TIP_OK);
+    // the few-stream latency plan is the only one with the dropout sites; a demoted handle takes no cooperating kernel (its GEMV
+    // recurrence is one).  tip_forward_dropout's caller falls back to tip_train_forward; tip_forward_live runs everything else — a
+    // demoted handle too — on the one-window hybrid encoder's live mode, which serves what the hybrid training forward serves
+    p->few = serve != kServeScheduled && !h->demoted && latency_supported(d, B, T);
+    if (serve == kServeFewOnly && !p->few) return stop(TIP_ERR_UNSUPPORTED_CONFIG);
+    if (serve == kServeLive && !p->few && !(fused_supported(d, T) && fused_has_rnn_ih(d))) return stop(TIP_ERR_UNSUPPORTED_CONFIG);
+    p->ws = carve_workspace(d, B, T);
+    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 || workspace_bytes < p->ws.total_bytes) return stop(TIP_ERR_WORKSPACE);
+    p->s = static_cast<hipStream_t>(stream);
+    p->cus = effective_cus(h->num_cus, p->s);
+    p->mask = (flags & TIP_FWD_KEEP_MASK) ? keep_mask : nullptr;
+    p->keep_scale = p->mask || mask_drawn ? keep_scale : 1.f;
+    return true;
+}
+
 // rows (tip_forward_rows; null: tip_forward): one output row per window, row rows[b] of window b — only the output projection's row
 // addressing differs (TIP_FWD_LAST_ROW_ONLY is set with it, so everything that depends on the output's shape takes the last-row form)
 static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, int flags,
                         const float* keep_mask, float keep_scale, void* workspace, size_t workspace_bytes,
                         tip_stream_t stream, const ReuseCtx* reuse, const int* rows = nullptr) {
-    if (!h || !x_imu || !x_s || !y || B < 0 || T < 1) return TIP_ERR_INVALID_ARG;
-    // (cfg.t_max is a sizing hint, not a limit: the reference builds its causal mask for any window length, :56-58,85; what
-    // bounds B * T here are the 32-bit byte offsets of the buffer descriptors)
-    if ((long long)B * T * (long long)std::max(std::max(3 * h->d.D, h->d.F), std::max(h->d.R, h->d.InPad)) * 4 > 0x7fffffffLL)
-        return TIP_ERR_UNSUPPORTED_CONFIG;
-    if ((flags & TIP_FWD_KEEP_MASK) && !keep_mask) return TIP_ERR_INVALID_ARG;
-    if (!h->packed_dev) return TIP_ERR_NOT_READY;
-    if (tip_check(h, 0) != TIP_OK) return TIP_ERR_HANDOFF;   // sticky: an earlier launch lost a hand-off (tip_check(h, 1) clears)
-    if (B == 0) return TIP_OK;
+    ForwardPrep f;
+    int status;
+    if (!forward_prepare(h, x_imu, x_s, y, B, T, flags, keep_mask, keep_scale, false, workspace, workspace_bytes, stream, kServeScheduled, &f, &status))
+        return status;
     const Dims& d = h->d;
-    const Workspace ws = carve_workspace(d, B, T);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 || workspace_bytes < ws.total_bytes)
-        return TIP_ERR_WORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int cus = effective_cus(h->num_cus, s);   // the stream's CU mask counts, not the device's CU total
+    hipStream_t s = f.s;
     // (tip_forward_reuse, full windows: ONE launch sequence on the two-window encoder's reuse form, whatever the batch; while the windows
     // still grow, T < 40, the ring update below is all the reuse form does and the forward is tip_forward's)
     const bool reuse_full = reuse && T == 40;
-    const Schedule sc = schedule_forward(ScheduleIn{d, B, T, cus, h->num_cus, h->plan, h->rnn_cluster, h->f1s_parts, h->demoted != 0, reuse_full,
+    const Schedule sc = schedule_forward(ScheduleIn{d, B, T, f.cus, h->num_cus, h->plan, h->rnn_cluster, h->f1s_parts, h->demoted != 0, reuse_full,
                                                     workspace_bytes});
     if (sc.status != TIP_OK) return sc.status;
-    const float* mask = (flags & TIP_FWD_KEEP_MASK) ? keep_mask : nullptr;
     const size_t row_i = (size_t)T * d.n_imu_total, row_s = (size_t)T * d.S;
     const size_t row_y = (flags & TIP_FWD_LAST_ROW_ONLY) ? (size_t)d.S : row_s;
     // A shared tail: both parts in ONE launch sequence over the whole batch's carve-up.  Otherwise every part is a launch sequence of its
@@ -662,9 +696,9 @@ static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, flo
     const int nseq = sc.shared_tail ? 1 : sc.nparts;
     for (int i = 0; i < nseq; ++i) {
         const int first = sc.part[i].first, n = sc.shared_tail ? B : sc.part[i].count;
-        LaunchSeq q{h, s, cus, x_imu + first * row_i, x_s + first * row_s, mask ? mask + first * row_s : nullptr, mask ? keep_scale : 1.f,
+        LaunchSeq q{h, s, f.cus, x_imu + first * row_i, x_s + first * row_s, f.mask ? f.mask + first * row_s : nullptr, f.keep_scale,
                     y + first * row_y, rows ? rows + first : nullptr, n, T, flags, static_cast<float*>(workspace),
-                    n == B ? ws : carve_workspace(d, n, T), sc.part[i].rnn_cluster, reuse_full ? reuse : nullptr, nullptr};
+                    n == B ? f.ws : carve_workspace(d, n, T), sc.part[i].rnn_cluster, reuse_full ? reuse : nullptr, nullptr};
         CoopSerial serial(h->device, s);   // forwards of different streams do not overlap on the device (cooperating kernels)
         if (serial.status != hipSuccess) return fail_hip(h, serial.status, "stream serialisation");
         if (reuse) {
@@ -729,91 +763,61 @@ int tip_draw_keep_mask(float p_state, unsigned long long state_seed, float* mask
     return launch_keep_mask(mask, n, key, thresh, static_cast<hipStream_t>(stream)) == hipSuccess ? TIP_OK : TIP_ERR_HIP;
 }
 
-int tip_forward_dropout(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, int flags,
-                        const float* keep_mask, float keep_scale, float p_state, unsigned long long state_seed, float p_drop,
-                        unsigned long long seed, void* workspace, size_t workspace_bytes, tip_stream_t stream) {
-    if (!h || !x_imu || !x_s || !y || B < 0 || T < 1) return TIP_ERR_INVALID_ARG;
+// tip_forward_dropout and tip_forward_live: ONE launch sequence with the encoder's dropout sites and the past-state keep mask live.
+// few_only (tip_forward_dropout): the few-stream latency plan or TIP_ERR_UNSUPPORTED_CONFIG, never the hybrid encoder's live mode.
+static int live_impl(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, const int* rows, int flags,
+                     const float* keep_mask, float keep_scale, float p_state, unsigned long long state_seed, float p_drop,
+                     unsigned long long seed, const unsigned long long* seeds_dev, void* workspace, size_t workspace_bytes,
+                     tip_stream_t stream, bool few_only) {
     if (p_drop < 0.f || p_drop >= 1.f) return TIP_ERR_INVALID_ARG;
+    if (rows) flags |= TIP_FWD_LAST_ROW_ONLY;
     unsigned mkey = 0, mthresh = 0;
     if (!(flags & TIP_FWD_KEEP_MASK) && p_state > 0.f && !state_mask_params(p_state, state_seed, &mkey, &mthresh)) return TIP_ERR_INVALID_ARG;
-    if ((flags & TIP_FWD_KEEP_MASK) && !keep_mask) return TIP_ERR_INVALID_ARG;
-    if (!h->packed_dev) return TIP_ERR_NOT_READY;
-    if (tip_check(h, 0) != TIP_OK) return TIP_ERR_HANDOFF;
-    if (B == 0) return TIP_OK;
-    const Dims& d = h->d;
-    // the few-stream latency plan is the only one with the dropout sites; a demoted handle takes no cooperating kernel (its GEMV
-    // recurrence is one): the caller falls back to tip_train_forward
-    if (h->demoted || !latency_supported(d, B, T)) return TIP_ERR_UNSUPPORTED_CONFIG;
-    const Workspace ws = carve_workspace(d, B, T);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 || workspace_bytes < ws.total_bytes) return TIP_ERR_WORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int cus = effective_cus(h->num_cus, s);
-    CoopSerial serial(h->device, s);
+    ForwardPrep f;
+    int status;
+    if (!forward_prepare(h, x_imu, x_s, y, B, T, flags, keep_mask, keep_scale, mthresh != 0, workspace, workspace_bytes, stream,
+                         few_only ? kServeFewOnly : kServeLive, &f, &status))
+        return status;
+    int rnn_cluster = 0;
+    if (!f.few) {   // (the recurrence variant as the forward pinned to the hybrid plan resolves it)
+        const Schedule sc = schedule_forward(ScheduleIn{h->d, B, T, f.cus, h->num_cus, TIP_PLAN_FUSEDH, h->rnn_cluster, h->f1s_parts, h->demoted != 0,
+                                                        false, workspace_bytes});
+        if (sc.status != TIP_OK) return sc.status;
+        rnn_cluster = sc.part[0].rnn_cluster;
+    }
+    CoopSerial serial(h->device, f.s);
     if (serial.status != hipSuccess) return fail_hip(h, serial.status, "stream serialisation");
-    const float* mask = (flags & TIP_FWD_KEEP_MASK) ? keep_mask : nullptr;
-    if (!mask && !mthresh) keep_scale = 1.f;
     TrainDropout td = make_train_dropout(p_drop, seed);
     td.mkey = mkey;
     td.mthresh = mthresh;
-    LaunchSeq q{h, s, cus, x_imu, x_s, mask, keep_scale, y, nullptr, B, T, flags, static_cast<float*>(workspace), ws, 0, nullptr, &td};
-    int st = run_encoder(q, SchedPart{0, B, TIP_PLAN_LATENCY, 0}, 0);
+    td.seeds_dev = seeds_dev;   // (td.state_seed stays 0: the few-stream plan's mask key is mkey, the hybrid live mode reads lt.lv)
+    LiveTrain lt;
+    lt.sv = nullptr;
+    lt.x0 = lt.qkv = lt.ast = lt.att = lt.z1 = lt.st1 = lt.x1 = lt.hid = lt.z2 = lt.st2 = lt.xo = lt.layer_stride = 0;
+    lt.seed = seed; lt.thresh = td.thresh; lt.scale = td.scale;
+    lt.lv = LiveArgs{seeds_dev, state_seed, f.mask ? 0u : mthresh};
+    LaunchSeq q{h, f.s, f.cus, x_imu, x_s, f.mask, f.keep_scale, y, rows, B, T, flags, static_cast<float*>(workspace), f.ws, rnn_cluster, nullptr,
+                f.few ? &td : nullptr, f.few ? nullptr : &lt};
+    int st = run_encoder(q, SchedPart{0, B, f.few ? TIP_PLAN_LATENCY : TIP_PLAN_FUSEDH, rnn_cluster}, 0);
     if (st == TIP_OK) st = run_tail(q);
     if (st != TIP_OK) return st;
     h->forward_count++;
     return TIP_OK;
 }
 
+int tip_forward_dropout(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, int flags,
+                        const float* keep_mask, float keep_scale, float p_state, unsigned long long state_seed, float p_drop,
+                        unsigned long long seed, void* workspace, size_t workspace_bytes, tip_stream_t stream) {
+    return live_impl(h, x_imu, x_s, y, B, T, nullptr, flags, keep_mask, keep_scale, p_state, state_seed, p_drop, seed, nullptr, workspace,
+                     workspace_bytes, stream, true);
+}
+
 int tip_forward_live(tip_handle* h, const float* x_imu, const float* x_s, float* y, int B, int T, const int* rows, int flags,
                      const float* keep_mask, float keep_scale, float p_state, unsigned long long state_seed, float p_drop,
                      unsigned long long seed, const unsigned long long* seeds_dev, void* workspace, size_t workspace_bytes,
                      tip_stream_t stream) {
-    if (!h || !x_imu || !x_s || !y || B < 0 || T < 1) return TIP_ERR_INVALID_ARG;
-    if (p_drop < 0.f || p_drop >= 1.f) return TIP_ERR_INVALID_ARG;
-    if (rows) flags |= TIP_FWD_LAST_ROW_ONLY;
-    unsigned mkey = 0, mthresh = 0;
-    if (!(flags & TIP_FWD_KEEP_MASK) && p_state > 0.f && !state_mask_params(p_state, state_seed, &mkey, &mthresh)) return TIP_ERR_INVALID_ARG;
-    if ((flags & TIP_FWD_KEEP_MASK) && !keep_mask) return TIP_ERR_INVALID_ARG;
-    const Dims& d = h->d;
-    if ((long long)B * T * (long long)std::max(std::max(3 * d.D, d.F), std::max(d.R, d.InPad)) * 4 > 0x7fffffffLL) return TIP_ERR_UNSUPPORTED_CONFIG;
-    if (!h->packed_dev) return TIP_ERR_NOT_READY;
-    if (tip_check(h, 0) != TIP_OK) return TIP_ERR_HANDOFF;
-    if (B == 0) return TIP_OK;
-    // the few-stream plan where tip_forward_dropout takes it; everything else — a demoted handle too: no cooperating encoder — on the
-    // one-window hybrid encoder's live mode, which serves what the hybrid training forward serves
-    const bool latency = !h->demoted && latency_supported(d, B, T);
-    if (!latency && !(fused_supported(d, T) && fused_has_rnn_ih(d))) return TIP_ERR_UNSUPPORTED_CONFIG;
-    const Workspace ws = carve_workspace(d, B, T);
-    if (!workspace || reinterpret_cast<uintptr_t>(workspace) % 256 || workspace_bytes < ws.total_bytes) return TIP_ERR_WORKSPACE;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    const int cus = effective_cus(h->num_cus, s);
-    int rnn_cluster = 0;
-    if (!latency) {   // (the recurrence variant as the forward pinned to the hybrid plan resolves it)
-        const Schedule sc = schedule_forward(ScheduleIn{d, B, T, cus, h->num_cus, TIP_PLAN_FUSEDH, h->rnn_cluster, h->f1s_parts, h->demoted != 0, false,
-                                                        workspace_bytes});
-        if (sc.status != TIP_OK) return sc.status;
-        rnn_cluster = sc.part[0].rnn_cluster;
-    }
-    CoopSerial serial(h->device, s);
-    if (serial.status != hipSuccess) return fail_hip(h, serial.status, "stream serialisation");
-    const float* mask = (flags & TIP_FWD_KEEP_MASK) ? keep_mask : nullptr;
-    if (!mask && !mthresh) keep_scale = 1.f;
-    TrainDropout td = make_train_dropout(p_drop, seed);
-    td.mkey = mkey;
-    td.mthresh = mthresh;
-    td.seeds_dev = seeds_dev;
-    td.state_seed = state_seed;
-    LiveTrain lt;
-    lt.sv = nullptr;
-    lt.x0 = lt.qkv = lt.ast = lt.att = lt.z1 = lt.st1 = lt.x1 = lt.hid = lt.z2 = lt.st2 = lt.xo = lt.layer_stride = 0;
-    lt.seed = seed; lt.thresh = td.thresh; lt.scale = td.scale;
-    lt.lv = LiveArgs{seeds_dev, state_seed, mask ? 0u : mthresh};
-    LaunchSeq q{h, s, cus, x_imu, x_s, mask, keep_scale, y, rows, B, T, flags, static_cast<float*>(workspace), ws, rnn_cluster, nullptr,
-                latency ? &td : nullptr, latency ? nullptr : &lt};
-    int st = run_encoder(q, SchedPart{0, B, latency ? TIP_PLAN_LATENCY : TIP_PLAN_FUSEDH, rnn_cluster}, 0);
-    if (st == TIP_OK) st = run_tail(q);
-    if (st != TIP_OK) return st;
-    h->forward_count++;
-    return TIP_OK;
+    return live_impl(h, x_imu, x_s, y, B, T, rows, flags, keep_mask, keep_scale, p_state, state_seed, p_drop, seed, seeds_dev, workspace,
+                     workspace_bytes, stream, false);
 }
 
 int tip_seeds_next(unsigned long long* seeds_dev, tip_stream_t stream) {

@@ -62,7 +62,7 @@ def combine_motions(files: Sequence[dict], down_sample_rates: Sequence[int], aug
     scratch = torch.empty(max(frames + [1]) * 18, dtype=torch.float64, device=dev)
     info, start, kept = [], 0, 0
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _lib.current_stream(dev)
         for i, f in enumerate(files):
             n = frames[i]
             if n == 0:
@@ -76,8 +76,8 @@ def combine_motions(files: Sequence[dict], down_sample_rates: Sequence[int], aug
             rc = L.tip_combine_sequence(imu.data_ptr(), s.data_ptr(), c.data_ptr(), len(imu), len(s), bias.data_ptr(), int(dip),
                                         IMU[start:].data_ptr(), SUM[start:].data_ptr(), S[start:].data_ptr(),
                                         scratch.data_ptr(), scratch.numel() * 8, stream)
-            if rc != n:
-                raise _lib.TipStatusError(rc, "tip_combine_sequence")
+            if _lib.check(rc) != n:
+                raise _lib.TipStatusError(rc, f"tip_combine_sequence wrote {rc} frames, not {n}")
             info.append([start, start + n, int(down_sample_rates[i])])
             start += n
             kept += 1
@@ -183,12 +183,9 @@ class TrainSubDataset(torch.utils.data.Dataset):
         x_s = torch.empty((n, T, ws), dtype=torch.float32, device=dev)
         y = torch.empty((n, T, ws), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = _lib.load().tip_gather_windows(self.IMU_c.data_ptr(), self.SUM_c.data_ptr() if self.SUM_c is not None else None,
-                                                self.S_c.data_ptr(), int(self.IMU_c.shape[0]), t.data_ptr(), n, T,
-                                                x_imu.data_ptr(), x_s.data_ptr(), y.data_ptr(),
-                                                torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            raise _lib.TipStatusError(rc, "tip_gather_windows")
+            _lib.check(_lib.load().tip_gather_windows(self.IMU_c.data_ptr(), self.SUM_c.data_ptr() if self.SUM_c is not None else None,
+                                                      self.S_c.data_ptr(), int(self.IMU_c.shape[0]), t.data_ptr(), n, T,
+                                                      x_imu.data_ptr(), x_s.data_ptr(), y.data_ptr(), _lib.current_stream(dev)))
         return x_imu, x_s, y
 
     def __getitem__(self, index):

@@ -191,9 +191,7 @@ def _lib():
 
 
 def _check(status):
-    if status < 0:
-        tlib, lib = _lib()
-        raise tlib.TipStatusError(status, lib.tip_strerror(status).decode())
+    return _lib()[0].check(status)
 
 
 def _dev_f32(x, device, shape_tail, who, what):
@@ -217,8 +215,7 @@ def _offsets(offsets, n_rows, who):
 
 
 def _stream(device):
-    import torch
-    return torch.cuda.current_stream(device).cuda_stream
+    return _lib()[0].current_stream(device)
 
 
 # ---- the wearer's body scale -----------------------------------------------------------------------------------------------------------

@@ -59,16 +59,12 @@ class _Loss(torch.autograd.Function):
             g, ldg = None, 0
         stats = torch.empty(_lib.TIP_LOSS_STATS, dtype=dt, device=dev)
         nbytes = ctypes.c_size_t()
-        rc = lib.tip_loss_ws_bytes(B, T, ctypes.byref(nbytes))
-        if rc < 0:
-            raise _lib.TipStatusError(rc, "tip_loss_ws_bytes")
+        _lib.check(lib.tip_loss_ws_bytes(B, T, ctypes.byref(nbytes)))
         ws = torch.empty(max(nbytes.value // 8, 1), dtype=torch.float64, device=dev)
         with torch.cuda.device(dev):
-            rc = (lib.tip_loss_forward_f64 if dt == torch.float64 else lib.tip_loss_forward)(p.data_ptr(), ldp, g.data_ptr() if g is not None else None, ldg, B, T, n_pose, n_vel,
-                                      n_sbp, terms, stats.data_ptr(), ws.data_ptr(), nbytes.value,
-                                      torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            raise _lib.TipStatusError(rc, "tip_loss_forward")
+            fn = lib.tip_loss_forward_f64 if dt == torch.float64 else lib.tip_loss_forward
+            _lib.check(fn(p.data_ptr(), ldp, g.data_ptr() if g is not None else None, ldg, B, T, n_pose, n_vel, n_sbp, terms, stats.data_ptr(),
+                          ws.data_ptr(), nbytes.value, _lib.current_stream(dev)))
         ctx.save_for_backward(p, g, stats)
         ctx.args = (ldp, ldg, B, T, n_pose, n_vel, n_sbp, terms, tuple(pred.shape))
         total, parts = stats[0].clone(), stats[1:4].clone()
@@ -85,11 +81,9 @@ class _Loss(torch.autograd.Function):
         go = g_total.detach().to(device=dev, dtype=p.dtype).reshape(1).contiguous()
         with torch.cuda.device(dev):
             lib = _lib.load()
-            rc = (lib.tip_loss_backward_f64 if p.dtype == torch.float64 else lib.tip_loss_backward)(p.data_ptr(), ldp, g.data_ptr() if g is not None else None, ldg, B, T, n_pose,
-                                               n_vel, n_sbp, terms, stats.data_ptr(), go.data_ptr(), dpred.data_ptr(), W,
-                                               torch.cuda.current_stream(dev).cuda_stream)
-        if rc < 0:
-            raise _lib.TipStatusError(rc, "tip_loss_backward")
+            fn = lib.tip_loss_backward_f64 if p.dtype == torch.float64 else lib.tip_loss_backward
+            _lib.check(fn(p.data_ptr(), ldp, g.data_ptr() if g is not None else None, ldg, B, T, n_pose, n_vel, n_sbp, terms, stats.data_ptr(),
+                          go.data_ptr(), dpred.data_ptr(), W, _lib.current_stream(dev)))
         return dpred, None, None, None, None, None, None, None
 
 

@@ -2,10 +2,15 @@
 load, everything that needs it raises TipLibraryError."""
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
 import subprocess
 from typing import List, Optional, Tuple
+
+# torch bundles its own libamdhip64.so.7; importing it first makes libtip_hip.so bind to that same HIP runtime
+# (two runtimes in one process do not share devices, streams or allocations).
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -28,6 +33,7 @@ TIP_OPT_NO_FLOW, TIP_OPT_HANDOFF_KIND = 10, 11   # few-stream plan without its o
 TIP_ABI_VERSION = 5
 TIP_RNN_CLUSTER_ROWS4 = 0x44   # TIP_OPT_RNN_CLUSTER value: 4-window tiles on 4-workgroup clusters (AUTO's choice for rnn_hidden 512)
 TIP_ERR_HANDOFF = -8
+TIP_ERR_HIP = -5
 TIP_ERR_UNSUPPORTED_CONFIG = -2
 TIP_LOSS_Q, TIP_LOSS_C, TIP_LOSS_J, TIP_LOSS_STATS = 1, 2, 4, 16
 TIP_SENSOR_HEADING, TIP_SENSOR_TPOSE = 1, 2   # tip_sensor_begin: which hold starts
@@ -116,9 +122,6 @@ def load() -> ctypes.CDLL:
     global _lib
     if _lib is not None:
         return _lib
-    # torch bundles its own libamdhip64.so.7; importing it first makes libtip_hip.so bind to that same HIP runtime
-    # (two runtimes in one process do not share devices, streams or allocations).
-    import torch  # noqa: F401
     if not os.path.exists(LIB_PATH):
         raise TipLibraryError(
             f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
@@ -274,6 +277,33 @@ def load() -> ctypes.CDLL:
     return lib
 
 
+def check(status: int, handle: Optional["Handle"] = None) -> int:
+    """The one way a status code of the library becomes an exception: `status` back when it is not an error; TipStatusError with the
+    tip_strerror text otherwise — plus the HIP runtime's own message when `handle` is given and the status is TIP_ERR_HIP — and its
+    subclass TipHandoffError for TIP_ERR_HANDOFF."""
+    if status >= 0:
+        return status
+    lib = load()
+    text = lib.tip_strerror(status).decode()
+    if status == TIP_ERR_HIP and handle is not None and handle._h:
+        text += " — " + lib.tip_last_hip_error(handle._h).decode()
+    raise (TipHandoffError if status == TIP_ERR_HANDOFF else TipStatusError)(status, text)
+
+
+def current_stream(device) -> int:
+    """The raw handle of torch's current stream on `device`: what every tip_stream_t argument takes."""
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+_SAME_DEVICE = contextlib.nullcontext()
+
+
+def on_device(device):
+    """Context in which `device` is the current one (the library launches on the CURRENT device).  Switches only when it is another one:
+    torch.cuda.device costs ~3 us."""
+    return _SAME_DEVICE if torch.cuda.current_device() == device.index else torch.cuda.device(device)
+
+
 class Handle:
     """Owns one tip_handle (one per GPU)."""
 
@@ -284,14 +314,7 @@ class Handle:
         self._check(self.lib.tip_create(ctypes.byref(cfg), ctypes.byref(self._h)))
 
     def _check(self, status: int) -> int:
-        if status < 0:
-            text = self.lib.tip_strerror(status).decode()
-            if status == -5 and self._h:
-                text += " — " + self.lib.tip_last_hip_error(self._h).decode()
-            if status == TIP_ERR_HANDOFF:
-                raise TipHandoffError(status, text)
-            raise TipStatusError(status, text)
-        return status
+        return status if status >= 0 else check(status, self)   # (no second call on the way every forward takes)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -470,9 +493,7 @@ class Handle:
 
 def draw_keep_mask(p_state: float, state_seed: int, mask_ptr: int, n: int, stream: int):
     """tip_draw_keep_mask: the past-state keep decisions of (p_state, state_seed) as n floats (0 / 1) at device pointer mask_ptr."""
-    st = load().tip_draw_keep_mask(p_state, state_seed, mask_ptr, n, stream)
-    if st < 0:
-        raise TipStatusError(st, load().tip_strerror(st).decode())
+    check(load().tip_draw_keep_mask(p_state, state_seed, mask_ptr, n, stream))
 
 
 _M64 = (1 << 64) - 1
@@ -488,15 +509,11 @@ def seed_successor(s: int) -> int:
 
 def seeds_next(seeds_ptr: int, stream: int):
     """tip_seeds_next: both words of the device uint64 [2] at seeds_ptr <- their successors (seed_successor), one tiny launch."""
-    st = load().tip_seeds_next(seeds_ptr, stream)
-    if st < 0:
-        raise TipStatusError(st, load().tip_strerror(st).decode())
+    check(load().tip_seeds_next(seeds_ptr, stream))
 
 
 def spin_timeouts() -> int:
     """Hand-off waits that gave up since the library was loaded (synchronises the device); must be 0."""
     n = ctypes.c_uint()
-    st = load().tip_spin_timeouts(ctypes.byref(n))
-    if st < 0:
-        raise TipStatusError(st, load().tip_strerror(st).decode())
+    check(load().tip_spin_timeouts(ctypes.byref(n)))
     return int(n.value)

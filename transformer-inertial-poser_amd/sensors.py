@@ -134,7 +134,7 @@ class SensorFrontEnd:
         self.lib = _lib.load()
         self.mirror = PhaseMirror(self.n)
         nbytes = ctypes.c_size_t()
-        self._check(self.lib.tip_sensor_state_bytes(self.n, ctypes.byref(nbytes)))
+        _lib.check(self.lib.tip_sensor_state_bytes(self.n, ctypes.byref(nbytes)))
         self.cal = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
         self.packets = torch.zeros((self.n, PACKET), dtype=torch.float32, device=self.device)
         self.r_gp_b0 = None
@@ -149,19 +149,15 @@ class SensorFrontEnd:
             raise ValueError("tip_amd.SensorFrontEnd: max_gap limits the fill; give it with fill=True")
         self.fill_state = self.filled = None
         with torch.cuda.device(self.device):
-            self._check(self.lib.tip_sensor_reset(self.cal.data_ptr(), self.n, self._stream()))
+            _lib.check(self.lib.tip_sensor_reset(self.cal.data_ptr(), self.n, self._stream()))
             if self.fill:
-                self._check(self.lib.tip_fill_state_bytes(self.n, ctypes.byref(nbytes)))
+                _lib.check(self.lib.tip_fill_state_bytes(self.n, ctypes.byref(nbytes)))
                 self.fill_state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
                 self.filled = torch.zeros((self.n, PARTS), dtype=torch.uint8, device=self.device)
-                self._check(self.lib.tip_fill_reset(self.fill_state.data_ptr(), self.n, None, 0, self._stream()))
-
-    def _check(self, status: int):
-        if status < 0:
-            raise _lib.TipStatusError(status, self.lib.tip_strerror(status).decode())
+                _lib.check(self.lib.tip_fill_reset(self.fill_state.data_ptr(), self.n, None, 0, self._stream()))
 
     def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+        return _lib.current_stream(self.device)
 
     def _to_dev(self, t):
         """The engines' rule: host -> device without a synchronising copy from pageable memory."""
@@ -182,10 +178,10 @@ class SensorFrontEnd:
         """One tip_sensor_transform launch: the packet buffer -> raw [n, 72] (a CUDA float32 tensor of this device, contiguous); with
         fill=True one tip_fill_live launch behind it, in place on raw."""
         with torch.cuda.device(self.device):
-            self._check(self.lib.tip_sensor_transform(self.cal.data_ptr(), self.packets.data_ptr(), self.n, self.max_acc, raw.data_ptr(),
+            _lib.check(self.lib.tip_sensor_transform(self.cal.data_ptr(), self.packets.data_ptr(), self.n, self.max_acc, raw.data_ptr(),
                                                       self._stream()))
             if self.fill:
-                self._check(self.lib.tip_fill_live(self.fill_state.data_ptr(), self.cal.data_ptr(), raw.data_ptr(), self.n, self.max_gap,
+                _lib.check(self.lib.tip_fill_live(self.fill_state.data_ptr(), self.cal.data_ptr(), raw.data_ptr(), self.n, self.max_gap,
                                                    self.filled.data_ptr(), self._stream()))
 
     # ---- missing readings (fill=True) ------------------------------------------------------------------------------------------------
@@ -195,7 +191,7 @@ class SensorFrontEnd:
             return
         with torch.cuda.device(self.device):
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
-            self._check(self.lib.tip_fill_reset(self.fill_state.data_ptr(), self.n, sl.data_ptr(), len(idx), self._stream()))
+            _lib.check(self.lib.tip_fill_reset(self.fill_state.data_ptr(), self.n, sl.data_ptr(), len(idx), self._stream()))
 
     def _needs_fill(self, who):
         if not self.fill:
@@ -215,7 +211,7 @@ class SensorFrontEnd:
         if idx:
             with torch.cuda.device(self.device):
                 sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
-                self._check(self.lib.tip_fill_get(self.fill_state.data_ptr(), self.n, sl.data_ptr(), len(idx), out.data_ptr(), self._stream()))
+                _lib.check(self.lib.tip_fill_get(self.fill_state.data_ptr(), self.n, sl.data_ptr(), len(idx), out.data_ptr(), self._stream()))
         return out[:, 0], out[:, 1], out[:, 2]
 
     # ---- the two holds ---------------------------------------------------------------------------------------------------------------
@@ -224,7 +220,7 @@ class SensorFrontEnd:
             return
         with torch.cuda.device(self.device):
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
-            self._check(self.lib.tip_sensor_begin(self.cal.data_ptr(), self.n, sl.data_ptr(), len(idx), which, self._stream()))
+            _lib.check(self.lib.tip_sensor_begin(self.cal.data_ptr(), self.n, sl.data_ptr(), len(idx), which, self._stream()))
 
     def begin_heading(self, slots=None):
         """Start the heading hold of the listed slots (None: all): sensors lying aligned with the body reference frame
@@ -245,7 +241,7 @@ class SensorFrontEnd:
         packets of the other slots are ignored and their blocks are not written."""
         self._fill(packets, "SensorFrontEnd.accumulate")
         with torch.cuda.device(self.device):
-            self._check(self.lib.tip_sensor_accumulate(self.cal.data_ptr(), self.packets.data_ptr(), self.n, self._stream()))
+            _lib.check(self.lib.tip_sensor_accumulate(self.cal.data_ptr(), self.packets.data_ptr(), self.n, self._stream()))
 
     def finish(self, slots=None):
         """End the hold of the listed slots (None: every slot that is in one): a heading hold leaves R_Gn_Gp (the mean matrices as they
@@ -260,7 +256,7 @@ class SensorFrontEnd:
         with torch.cuda.device(self.device):
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
             r = self.r_gp_b0.data_ptr() if self.r_gp_b0 is not None else None
-            self._check(self.lib.tip_sensor_finish(self.cal.data_ptr(), self.n, sl.data_ptr(), len(idx), r, self._stream()))
+            _lib.check(self.lib.tip_sensor_finish(self.cal.data_ptr(), self.n, sl.data_ptr(), len(idx), r, self._stream()))
         self._fill_reset(idx)
 
     # ---- saved calibrations ----------------------------------------------------------------------------------------------------------
@@ -278,7 +274,7 @@ class SensorFrontEnd:
         with torch.cuda.device(self.device):
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
             t = self._to_dev(t.contiguous()).contiguous()
-            self._check(self.lib.tip_sensor_set(self.cal.data_ptr(), self.n, sl.data_ptr(), len(idx), t.data_ptr(), self._stream()))
+            _lib.check(self.lib.tip_sensor_set(self.cal.data_ptr(), self.n, sl.data_ptr(), len(idx), t.data_ptr(), self._stream()))
         self._fill_reset(idx)
 
     def tables(self, slots=None):
@@ -288,7 +284,7 @@ class SensorFrontEnd:
         if idx:
             with torch.cuda.device(self.device):
                 sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
-                self._check(self.lib.tip_sensor_get(self.cal.data_ptr(), self.n, sl.data_ptr(), len(idx), out.data_ptr(), self._stream()))
+                _lib.check(self.lib.tip_sensor_get(self.cal.data_ptr(), self.n, sl.data_ptr(), len(idx), out.data_ptr(), self._stream()))
         return out
 
     def live(self, slots=None):
@@ -311,11 +307,6 @@ class SensorFrontEnd:
 
 
 # ---- recorded data: the real-IMU files, recorded frames with gaps, recorded packet sessions ------------------------------------------
-def _status(lib, status):
-    if status < 0:
-        raise _lib.TipStatusError(status, lib.tip_strerror(status).decode())
-
-
 def _device_of(arrays, device):
     if device is not None:
         dev = torch.device(device)
@@ -385,9 +376,9 @@ def real_imu_frames(ori_list, acc_list, rot, sel=SEL_DIP17, strict=True, device=
         N, R = int(ori.shape[0]), len(lens)
         out = torch.empty((N, 72), dtype=torch.float64, device=dev)
         unfilled = torch.zeros(R, dtype=torch.int32, device=dev)
-        _status(lib, lib.tip_fill_real(ori.data_ptr(), acc.data_ptr(), N, S, offs.data_ptr(), R, (ctypes.c_int * 6)(*sel),
+        _lib.check(lib.tip_fill_real(ori.data_ptr(), acc.data_ptr(), N, S, offs.data_ptr(), R, (ctypes.c_int * 6)(*sel),
                                        (ctypes.c_double * 9)(*rot.reshape(-1)), out.data_ptr(), unfilled.data_ptr(),
-                                       torch.cuda.current_stream(dev).cuda_stream))
+                                       _lib.current_stream(dev)))
         if strict:
             left = unfilled.cpu().numpy()
             if left.any():
@@ -413,8 +404,8 @@ def fill_sequences(frames_list, rule="live", max_gap=None, device=None, host=Fal
         frames, offs, lens = _stack(frames_list, torch.float32, 72, dev, who, "frames_list")
         out = torch.empty_like(frames)
         flags = torch.zeros((frames.shape[0], PARTS), dtype=torch.uint8, device=dev)
-        _status(lib, lib.tip_fill_rows(frames.data_ptr(), out.data_ptr(), int(frames.shape[0]), offs.data_ptr(), len(lens), gap,
-                                       flags.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+        _lib.check(lib.tip_fill_rows(frames.data_ptr(), out.data_ptr(), int(frames.shape[0]), offs.data_ptr(), len(lens), gap,
+                                       flags.data_ptr(), _lib.current_stream(dev)))
     return _recordings(out, flags, lens, host, return_flags)
 
 
@@ -453,10 +444,10 @@ def transform_sequences(packets_list, tables, fill=False, max_acc=10.0, max_gap=
         N = int(packets.shape[0])
         out = torch.empty((N, 72), dtype=torch.float32, device=dev)
         flags = torch.zeros((N, PARTS), dtype=torch.uint8, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _status(lib, lib.tip_fill_packets(t.data_ptr(), packets.data_ptr(), N, offs.data_ptr(), len(lens), max_acc, out.data_ptr(), stream))
+        stream = _lib.current_stream(dev)
+        _lib.check(lib.tip_fill_packets(t.data_ptr(), packets.data_ptr(), N, offs.data_ptr(), len(lens), max_acc, out.data_ptr(), stream))
         if fill:
-            _status(lib, lib.tip_fill_rows(out.data_ptr(), out.data_ptr(), N, offs.data_ptr(), len(lens), gap, flags.data_ptr(), stream))
+            _lib.check(lib.tip_fill_rows(out.data_ptr(), out.data_ptr(), N, offs.data_ptr(), len(lens), gap, flags.data_ptr(), stream))
     return _recordings(out, flags, lens, host, return_flags)
 
 
@@ -556,15 +547,15 @@ class PacketResampler:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.lib = _lib.load()
         nbytes = ctypes.c_size_t()
-        _status(self.lib, self.lib.tip_resample_state_bytes(self.n, self.depth, ctypes.byref(nbytes)))
+        _lib.check(self.lib.tip_resample_state_bytes(self.n, self.depth, ctypes.byref(nbytes)))
         self.state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
         self.t = torch.zeros(self.n, dtype=torch.float64, device=self.device)
         self.flags = torch.full((self.n,), EMPTY, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
-            _status(self.lib, self.lib.tip_resample_reset(self.state.data_ptr(), self.n, self.depth, None, 0, self._stream()))
+            _lib.check(self.lib.tip_resample_reset(self.state.data_ptr(), self.n, self.depth, None, 0, self._stream()))
 
     def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+        return _lib.current_stream(self.device)
 
     def _slots(self, slots, who):
         return list(range(self.n)) if slots is None else slot_list(slots, self.n, f"sensors.PacketResampler.{who}")
@@ -597,7 +588,7 @@ class PacketResampler:
                 t, p, s = dev[: 8 * m].view(torch.float64), dev[8 * m: 176 * m].view(torch.float32), dev[176 * m:].view(torch.int32)
             else:
                 p, s, t = (_to(a.to(d), self.device).contiguous() for a, d in zip(args, dtypes))
-            _status(self.lib, self.lib.tip_resample_push(self.state.data_ptr(), self.n, self.depth, p.data_ptr(), s.data_ptr(), t.data_ptr(),
+            _lib.check(self.lib.tip_resample_push(self.state.data_ptr(), self.n, self.depth, p.data_ptr(), s.data_ptr(), t.data_ptr(),
                                                          m, self._stream()))
 
     def emit(self, t, out=None):
@@ -628,7 +619,7 @@ class PacketResampler:
             else:                                                 # (a 0-d value is broadcast)
                 tq.copy_(h if h.is_cuda else h.contiguous().pin_memory(), non_blocking=True)
         with torch.cuda.device(self.device):
-            _status(self.lib, self.lib.tip_resample_emit(self.state.data_ptr(), self.n, self.depth, tq.data_ptr(), self.delay, self.max_hold,
+            _lib.check(self.lib.tip_resample_emit(self.state.data_ptr(), self.n, self.depth, tq.data_ptr(), self.delay, self.max_hold,
                                                          self.mode, out.data_ptr(), self.flags.data_ptr(), self._stream()))
         return out
 
@@ -639,7 +630,7 @@ class PacketResampler:
             return
         with torch.cuda.device(self.device):
             sl = _to(torch.tensor(idx, dtype=torch.int32), self.device)
-            _status(self.lib, self.lib.tip_resample_reset(self.state.data_ptr(), self.n, self.depth, sl.data_ptr(), len(idx), self._stream()))
+            _lib.check(self.lib.tip_resample_reset(self.state.data_ptr(), self.n, self.depth, sl.data_ptr(), len(idx), self._stream()))
 
     def counts(self, slots=None):
         """(have, dropped, total) of the listed slots (None: all), three CUDA int32 tensors [len(slots)]: packets in the ring
@@ -649,7 +640,7 @@ class PacketResampler:
         if idx:
             with torch.cuda.device(self.device):
                 sl = _to(torch.tensor(idx, dtype=torch.int32), self.device)
-                _status(self.lib, self.lib.tip_resample_get(self.state.data_ptr(), self.n, self.depth, sl.data_ptr(), len(idx), out.data_ptr(),
+                _lib.check(self.lib.tip_resample_get(self.state.data_ptr(), self.n, self.depth, sl.data_ptr(), len(idx), out.data_ptr(),
                                                             self._stream()))
         return out[:, 0], out[:, 1], out[:, 2]
 
@@ -736,7 +727,7 @@ def resample_sequences(packets_list, times_list, rate_hz=60.0, *, mode="slerp", 
         K = int(sum(out_lens))
         out = torch.empty((K, PACKET), dtype=torch.float32, device=dev)
         flags = torch.empty(K, dtype=torch.uint8, device=dev)
-        _status(lib, lib.tip_resample_rows(packets.data_ptr(), stamps.data_ptr(), in_off.data_ptr(), int(packets.shape[0]), t_out.data_ptr(),
+        _lib.check(lib.tip_resample_rows(packets.data_ptr(), stamps.data_ptr(), in_off.data_ptr(), int(packets.shape[0]), t_out.data_ptr(),
                                            out_off.data_ptr(), K, len(lens), delay, hold, mode_c, depth, out.data_ptr(), flags.data_ptr(),
-                                           torch.cuda.current_stream(dev).cuda_stream))
+                                           _lib.current_stream(dev)))
     return _recordings(out, flags, out_lens, host, True)

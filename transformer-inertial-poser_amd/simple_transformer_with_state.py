@@ -51,9 +51,6 @@ from torch import nn
 
 from . import lib as _lib
 
-
-import contextlib as _contextlib
-_NO_CTX = _contextlib.nullcontext()
 _req_grad = operator.attrgetter("requires_grad")
 _version = operator.attrgetter("_version")
 _data_ptr = torch.Tensor.data_ptr
@@ -84,6 +81,23 @@ class _EncoderLayerParams(nn.Module):
 def _uniform_(t: torch.Tensor, bound: float):
     with torch.no_grad():
         t.uniform_(-bound, bound)
+
+
+def _check_rows(rows, B, dev):
+    """The per-window row indices of forward_rows / forward_live, contiguous."""
+    if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_cuda or
+            rows.shape[0] != B or rows.device != dev):
+        raise RuntimeError("tip_amd: rows must be an int32 CUDA tensor [B] on the inputs' device")
+    return rows.contiguous()
+
+
+def _output(out, shape, dtype, dev):
+    """The caller's out= once it is known to be what the kernels write, or a fresh tensor."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if tuple(out.shape) != shape or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+        raise RuntimeError(f"tip_amd: out= must be a contiguous {dtype} tensor of shape {shape} on {dev}")
+    return out
 
 
 class TF_RNN_Past_State(nn.Module):
@@ -208,10 +222,7 @@ class TF_RNN_Past_State(nn.Module):
             raise RuntimeError("tip_amd: forward_rows runs the inference kernels only (.eval() under torch.no_grad())")
         if self.in_linear.weight.dtype != torch.float32:
             raise RuntimeError("tip_amd: forward_rows computes in fp32 only")
-        if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_cuda or
-                rows.shape[0] != x_imu.shape[0] or rows.device != x_imu.device):
-            raise RuntimeError("tip_amd: rows must be an int32 CUDA tensor [B] on the inputs' device")
-        return self._forward_hip(x_imu, x_s, True, workspace=workspace, out=out, rows=rows.contiguous())
+        return self._forward_hip(x_imu, x_s, True, workspace=workspace, out=out, rows=_check_rows(rows, x_imu.shape[0], x_imu.device))
 
     def forward_live(self, x_imu, x_s, *, rows=None, last_row_only=True, seeds=None, seeds_dev=None, workspace=None, out=None):
         """The forward as the reference DEPLOYS the model (every shipped loader builds it with past_state_dropout = 0.8 and never calls
@@ -230,22 +241,9 @@ class TF_RNN_Past_State(nn.Module):
         workspace= and out= serve a single launch sequence and raise beyond it.)  workspace / out as forward_last's."""
         if self.in_dropout > 0.0:
             raise RuntimeError("tip_amd: forward_live does not serve in_dropout > 0 (no shipped loader of the reference sets it)")
-        if not (x_imu.is_cuda and x_s.is_cuda) or x_imu.dtype != torch.float32 or x_s.dtype != torch.float32 or \
-                self.in_linear.weight.dtype != torch.float32:
-            raise RuntimeError("tip_amd: forward_live serves fp32 windows and parameters on the GPU")
-        if x_imu.dim() != 3 or x_s.dim() != 3 or x_imu.shape[:2] != x_s.shape[:2]:
-            raise RuntimeError("expected x_imu [B,T,n_imu] and x_s [B,T,size_s]")
-        B, T = int(x_imu.shape[0]), int(x_imu.shape[1])
-        n_imu = self.input_size_imu + (18 if self.with_acc_sum else 0)
-        if x_imu.shape[2] != n_imu or x_s.shape[2] != self.size_s:
-            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied: got feature widths "
-                               f"{x_imu.shape[2]}+{x_s.shape[2]}, in_linear expects {n_imu}+{self.size_s}")
-        dev = x_imu.device
+        B, T, dev = self._check_windows(x_imu, x_s, fp32_only="forward_live")
         if rows is not None:
-            if (not isinstance(rows, torch.Tensor) or rows.dtype != torch.int32 or rows.dim() != 1 or not rows.is_cuda or
-                    rows.shape[0] != B or rows.device != dev):
-                raise RuntimeError("tip_amd: rows must be an int32 CUDA tensor [B] on the inputs' device")
-            rows = rows.contiguous()
+            rows = _check_rows(rows, B, dev)
             last_row_only = True
         if seeds_dev is not None:
             if seeds is not None:
@@ -258,17 +256,16 @@ class TF_RNN_Past_State(nn.Module):
             seeds = self._draw_seeds()
         seeds = (int(seeds[0]) & _lib._M64, int(seeds[1]) & _lib._M64)
         h = self._ensure_handle()
-        max_b = self.chunk_batch(T)
-        if B > max_b:
-            if workspace is not None or out is not None or seeds_dev is not None:
-                raise RuntimeError("tip_amd: workspace= / out= / seeds_dev= serve a single launch sequence (batch within tip_max_batch)")
-            parts = []
-            for lo in range(0, B, max_b):
-                hi = min(B, lo + max_b)
-                parts.append(self.forward_live(x_imu[lo:hi], x_s[lo:hi], rows=None if rows is None else rows[lo:hi],
-                                               last_row_only=last_row_only, seeds=seeds))
-                seeds = (_lib.seed_successor(seeds[0]), _lib.seed_successor(seeds[1]))
-            return torch.cat(parts, dim=0)
+
+        def chunk(lo, hi):
+            nonlocal seeds
+            part = self.forward_live(x_imu[lo:hi], x_s[lo:hi], rows=None if rows is None else rows[lo:hi], last_row_only=last_row_only,
+                                     seeds=seeds)
+            seeds = (_lib.seed_successor(seeds[0]), _lib.seed_successor(seeds[1]))
+            return part
+        y = self._in_chunks(B, T, False, workspace is not None or out is not None or seeds_dev is not None, chunk)
+        if y is not None:
+            return y
         p_state = float(self.past_state_dropout)
         if not 0.0 <= p_state < 1.0:
             raise RuntimeError("tip_amd: forward_live needs 0 <= past_state_dropout < 1")
@@ -276,40 +273,16 @@ class TF_RNN_Past_State(nn.Module):
         scale = 1.0 / (1.0 - p_state) if p_state > 0.0 else 1.0
         flags = _lib.TIP_FWD_LAST_ROW_ONLY if last_row_only else 0
         shape = (B, self.size_s) if last_row_only else (B, T, self.size_s)
-        with torch.no_grad(), (torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _NO_CTX):
-            if self._packed_dev is None or self._packed_dev.device != dev or (not self._frozen and self._packed_key != self._param_key(dev)):
-                self.refresh_packed(dev)
+        with torch.no_grad(), _lib.on_device(dev):
+            self._packed_current(dev)
             xi, xs = x_imu.contiguous(), x_s.contiguous()
-            if out is not None:
-                if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-                    raise RuntimeError(f"tip_amd: out= must be a contiguous float32 tensor of shape {shape} on {dev}")
-                y = out
-            else:
-                y = torch.empty(shape, dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            need = self._ws_bytes_cache.get((B, T))
-            if need is None:
-                need = self._ws_bytes_cache[(B, T)] = h.workspace_bytes(B, T)
-            if workspace is not None:
-                if workspace.dtype != torch.uint8 or workspace.device != dev or workspace.numel() < need or workspace.data_ptr() % 256:
-                    raise RuntimeError(f"tip_amd: workspace= must be a 256-byte aligned uint8 tensor of >= {need} bytes on {dev}")
-                ws = workspace
-            else:
-                ws = self._stream_buffer(self._workspace, dev, stream, need)
-
-            def launch():
-                h.forward_live(xi.data_ptr(), xs.data_ptr(), y.data_ptr(), B, T, None if rows is None else rows.data_ptr(), flags, None, scale,
-                               p_state, seeds[1], p_drop, seeds[0], None if seeds_dev is None else seeds_dev.data_ptr(), ws.data_ptr(),
-                               ws.numel(), stream)
-            try:
-                launch()
-            except _lib.TipHandoffError:
-                # an EARLIER launch lost a hand-off: the host's answer is _forward_hip's (one-launch form off, or the handle demoted —
-                # tip_forward_live serves a demoted handle on the hybrid encoder's live mode), then THIS call runs
-                if self._answer_handoff(h) is None:
-                    raise
-                self._fast_state = None
-                launch()
+            y = _output(out, shape, torch.float32, dev)
+            stream = _lib.current_stream(dev)
+            ws = self._workspace_for(h, B, T, dev, stream, workspace)
+            # (a lost hand-off of an EARLIER launch: tip_forward_live serves a demoted handle on the hybrid encoder's live mode)
+            self._launch(h, lambda: h.forward_live(xi.data_ptr(), xs.data_ptr(), y.data_ptr(), B, T, None if rows is None else rows.data_ptr(),
+                                                   flags, None, scale, p_state, seeds[1], p_drop, seeds[0],
+                                                   None if seeds_dev is None else seeds_dev.data_ptr(), ws.data_ptr(), ws.numel(), stream))
         return y
 
     def reuse_cache(self, n_streams: int) -> torch.Tensor:
@@ -325,9 +298,7 @@ class TF_RNN_Past_State(nn.Module):
 
     def reuse_reset(self, cache: torch.Tensor):
         """Forget every frame in the ring (the streams restart, or the parameters changed: the rows in it belong to the old weights)."""
-        st = _lib.load().tip_reuse_reset(cache.data_ptr(), cache.numel(), torch.cuda.current_stream(cache.device).cuda_stream)
-        if st < 0:
-            raise _lib.TipStatusError(st, _lib.load().tip_strerror(st).decode())
+        _lib.check(_lib.load().tip_reuse_reset(cache.data_ptr(), cache.numel(), _lib.current_stream(cache.device)))
         if len(self._ring_epoch) > 64:
             self._ring_epoch.clear()
         self._ring_epoch[cache.data_ptr()] = None      # filled under whatever image the next forward_last_reuse runs on
@@ -344,18 +315,14 @@ class TF_RNN_Past_State(nn.Module):
             raise RuntimeError("tip_amd: forward_last_reuse caches per-frame rows across windows, which is exact only without the "
                                "stochastic parts: .eval() under torch.no_grad(), past_state_dropout = 0, in_dropout = 0 "
                                "(the reference's fresh nn.Dropout at :77 is live even in .eval())")
-        if not (x_imu.is_cuda and x_s.is_cuda) or x_imu.dtype != torch.float32 or x_s.dtype != torch.float32:
-            raise RuntimeError("tip_amd: forward_last_reuse serves fp32 windows on the GPU")
-        dev = x_imu.device
-        if x_imu.dim() != 3 or x_s.dim() != 3 or x_imu.shape[:2] != x_s.shape[:2]:
-            raise RuntimeError("expected x_imu [B,T,n_imu] and x_s [B,T,size_s]")
-        B, T = int(x_imu.shape[0]), int(x_imu.shape[1])
-        if x_imu.shape[2] != self.input_size_imu + (18 if self.with_acc_sum else 0) or x_s.shape[2] != self.size_s:
-            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied: got feature widths {x_imu.shape[2]}+{x_s.shape[2]}")
+        B, T, dev = self._check_windows(x_imu, x_s, fp32_only="forward_last_reuse")
         h = self._ensure_handle()
-        with (torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _NO_CTX):
-            if self._packed_dev is None or self._packed_dev.device != dev or (not self._frozen and self._packed_key != self._param_key(dev)):
-                self.refresh_packed(dev)
+        with _lib.on_device(dev):
+            # (out= and workspace= are checked here, before the ring is touched and before any launch)
+            y = _output(out, (B, self.size_s), torch.float32, dev)
+            stream = _lib.current_stream(dev)
+            ws = self._workspace_for(h, B, T, dev, stream, workspace)
+            self._packed_current(dev)
             # The ring's rows are functions of the WEIGHTS too: it is good for the packed image it was filled under and no other —
             # whoever re-packed in between (this call, a plain forward after an optimiser step, attach_packed of a broadcast image)
             ep = self._ring_epoch.get(cache.data_ptr())
@@ -366,12 +333,7 @@ class TF_RNN_Past_State(nn.Module):
                 raise RuntimeError("tip_amd: the parameters changed while the reuse ring held rows computed with the old ones — "
                                    "the ring was cleared; re-prime it with 40 consecutive frames (StreamingEngine.reset())")
             x_imu_c, x_s_c = x_imu.contiguous(), x_s.contiguous()
-            y = out if out is not None else torch.empty((B, self.size_s), dtype=torch.float32, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            need = self._ws_bytes_cache.get((B, T))
-            if need is None:
-                need = self._ws_bytes_cache[(B, T)] = h.workspace_bytes(B, T)
-            ws = workspace if workspace is not None else self._stream_buffer(self._workspace, dev, stream, need)
+            # (no hand-off answer here: the error goes to the caller unanswered — StreamingEngine(reuse=True) answers it itself)
             h.forward_reuse(x_imu_c.data_ptr(), x_s_c.data_ptr(), y.data_ptr(), B, T, _lib.TIP_FWD_LAST_ROW_ONLY, cache.data_ptr(),
                             cache.numel(), int(frame_idx), frame_ctr_ptr, ws.data_ptr(), ws.numel(), stream)
         return y
@@ -566,7 +528,9 @@ class TF_RNN_Past_State(nn.Module):
         h = self._ensure_handle()
         dev = x_imu.device
         T = int(x_imu.shape[1])
-        # (the library launches on the CURRENT device: switch only when it is another one — the context manager costs ~3 us)
+        # This is the one-window runner's path in front of the launch (_few_window_fast: ~11 us of host time the GPU waits for).  The
+        # shared helpers — lib.on_device, lib.current_stream, _keep_mask_args, _workspace_for, _launch — cost 1.2 us here, measured
+        # against the statements they stand for, so those statements are written out in this function and in _forward_dropout_hip.
         ctx = torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else None
         if ctx is not None:
             ctx.__enter__()
@@ -595,30 +559,23 @@ class TF_RNN_Past_State(nn.Module):
         demoted handle): the caller then runs tip_train_forward.  trusted: the packed image was validated by the caller's protocol
         (_few_window_fast checks the parameters AFTER the launch and discards the result if they changed)."""
         dev = xi.device
-        if not trusted and (self._packed_dev is None or self._packed_dev.device != dev or
-                            (not self._frozen and self._packed_key != self._param_key(dev))):
-            self.refresh_packed(dev)
+        if not trusted:
+            self._packed_current(dev)
+        need = self._ws_bytes_cache.get((B, T))           # (_workspace_for, written out: see _few_window_train_launch)
+        if need is None:
+            need = self._ws_bytes_cache[(B, T)] = h.workspace_bytes(B, T)
+        ws = self._stream_buffer(self._workspace, dev, stream, need)
+        args = (xi.data_ptr(), xs.data_ptr(), y.data_ptr(), B, T, _lib.TIP_FWD_KEEP_MASK if mask_ptr else 0, mask_ptr, scale, p_state,
+                state_seed, p_drop, seed, ws.data_ptr(), ws.numel(), stream)
         try:
-            need = self._ws_bytes_cache.get((B, T))
-            if need is None:
-                need = self._ws_bytes_cache[(B, T)] = h.workspace_bytes(B, T)
-            ws = self._stream_buffer(self._workspace, dev, stream, need)
-            h.forward_dropout(xi.data_ptr(), xs.data_ptr(), y.data_ptr(), B, T, _lib.TIP_FWD_KEEP_MASK if mask_ptr else 0, mask_ptr,
-                              scale, p_state, state_seed, p_drop, seed, ws.data_ptr(), ws.numel(), stream)
-        except _lib.TipHandoffError:
-            # An EARLIER launch of this handle lost an inter-workgroup hand-off (a co-tenant held CUs): same answer as _forward_hip's —
-            # the first time, clear the word, demote the handle to the plans without cooperating kernels and let THIS call run there
-            # (False: the caller takes tip_train_forward, whose recurrence then runs one workgroup per tile); with TIP_OPT_AUTO_DEMOTE
-            # off, or on a handle that is demoted already, report it.
-            how = self._answer_handoff(h)
-            if how is None:
-                raise
-            self._fast_state = None
-            if how == "chain":      # only the one-launch form is gone: the same entry point serves this call on the launch chain
-                h.forward_dropout(xi.data_ptr(), xs.data_ptr(), y.data_ptr(), B, T, _lib.TIP_FWD_KEEP_MASK if mask_ptr else 0, mask_ptr,
-                                  scale, p_state, state_seed, p_drop, seed, ws.data_ptr(), ws.numel(), stream)
-                return True
-            return False
+            try:
+                h.forward_dropout(*args)
+            except _lib.TipHandoffError:
+                # A lost hand-off of an EARLIER launch.  The word is sticky and refused before anything is queued, so the call is
+                # handed to _launch as it is: there it is refused once more and answered.  If only the one-launch form is gone, the
+                # same entry point serves this call on the launch chain; on a handle demoted by the answer — False — the caller
+                # takes tip_train_forward, whose recurrence then runs one workgroup per tile.
+                return self._launch(h, lambda: h.forward_dropout(*args), chain_only=True)
         except _lib.TipStatusError as e:
             if e.status == _lib.TIP_ERR_UNSUPPORTED_CONFIG:
                 return False
@@ -675,7 +632,7 @@ class TF_RNN_Past_State(nn.Module):
         """The past-state keep mask (:77) of (past_state_dropout, state_seed) as a tensor like x_s: tip_draw_keep_mask."""
         m = torch.empty(x_s.shape, dtype=torch.float32, device=x_s.device)
         with torch.cuda.device(x_s.device):
-            _lib.draw_keep_mask(self.past_state_dropout, state_seed, m.data_ptr(), m.numel(), torch.cuda.current_stream(x_s.device).cuda_stream)
+            _lib.draw_keep_mask(self.past_state_dropout, state_seed, m.data_ptr(), m.numel(), _lib.current_stream(x_s.device))
         return m if x_s.dtype == torch.float32 else m.to(x_s.dtype)
 
     def _draw_keep_mask(self, x_s):
@@ -728,8 +685,7 @@ class TF_RNN_Past_State(nn.Module):
         tensors = [p.detach().to(device, torch.float32).contiguous() for p in self.state_dict().values()]
         out = torch.empty(h.packed_bytes(), dtype=torch.uint8, device=device)
         with torch.cuda.device(device):
-            h.pack_weights_device([t.data_ptr() for t in tensors], out.data_ptr(), out.numel(),
-                                  torch.cuda.current_stream(device).cuda_stream)
+            h.pack_weights_device([t.data_ptr() for t in tensors], out.data_ptr(), out.numel(), _lib.current_stream(device))
         return out
 
     def refresh_packed(self, device=None):
@@ -843,7 +799,11 @@ class TF_RNN_Past_State(nn.Module):
         self._workspace.clear()
         self._train_scratch.clear()
 
-    def _forward_hip(self, x_imu, x_s, last_row_only: bool, keep_mask="draw", apply_in_dropout=True, workspace=None, out=None, rows=None):
+    # -- what every HIP call prepares: each written once, shared by _forward_hip, forward_live, forward_last_reuse and the few-window
+    #    .train()-mode launch ------------------------------------------------------------------------------------------------------
+    def _check_windows(self, x_imu, x_s, fp32_only=None):
+        """(B, T, device) of a window pair the kernels serve: CUDA tensors of the parameters' precision, [B, T, n_imu] and
+        [B, T, size_s].  fp32_only: the name of a caller that has no fp64 form."""
         if not (x_imu.is_cuda and x_s.is_cuda):
             raise RuntimeError("tip_amd.TF_RNN_Past_State: the inference forward runs on an MI355X through "
                                "libtip_hip.so only — move the module and its inputs to the GPU (.cuda()); "
@@ -853,86 +813,120 @@ class TF_RNN_Past_State(nn.Module):
             raise RuntimeError("tip_amd.TF_RNN_Past_State: the HIP path computes in fp32 (or, for a module built under "
                                "train_model.py's --double, in fp64) and never converts tensors silently; got inputs "
                                f"{x_imu.dtype}/{x_s.dtype} for {pdt} parameters")
-        f64 = pdt == torch.float64          # train_model.py:84-85: the whole model in double -> tip_forward_f64
-        dev = x_imu.device
+        if fp32_only and pdt != torch.float32:
+            raise RuntimeError(f"tip_amd: {fp32_only} computes in fp32 only")
         if x_imu.dim() != 3 or x_s.dim() != 3 or x_imu.shape[:2] != x_s.shape[:2]:
             raise RuntimeError("expected x_imu [B,T,n_imu] and x_s [B,T,size_s]")
-        B, T = int(x_imu.shape[0]), int(x_imu.shape[1])
         n_imu = self.input_size_imu + (18 if self.with_acc_sum else 0)
         if x_imu.shape[2] != n_imu or x_s.shape[2] != self.size_s:
             raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied: got feature widths "
                                f"{x_imu.shape[2]}+{x_s.shape[2]}, in_linear expects {n_imu}+{self.size_s}")
-        h = self._ensure_handle()
-        # The kernels address their activations through 32-bit buffer descriptors (tip_forward) / 32-bit element offsets and grid
-        # limits (tip_forward_f64): the library says how many windows one call serves (tip_max_batch; TIP_ERR_UNSUPPORTED_CONFIG
-        # beyond: B > 13 107 at T = 40 for the paper configuration).  Streams are independent (no op in :60-102 crosses batch
-        # elements), so a larger batch is run in chunks — same numbers, one launch sequence per chunk.  (The past-state keep
-        # mask and the input dropout are drawn per chunk, like any two calls.)
+        return int(x_imu.shape[0]), int(x_imu.shape[1]), x_imu.device
+
+    def _packed_current(self, dev):
+        """Make the packed image current on `dev`: re-packed when there is none there or — unless frozen — a parameter moved or changed."""
+        if self._packed_dev is None or self._packed_dev.device != dev or (not self._frozen and self._packed_key != self._param_key(dev)):
+            self.refresh_packed(dev)
+
+    def _workspace_for(self, h, B, T, dev, stream, workspace, f64=False):
+        """The caller's workspace= once it is known to serve (B, T), or the module's buffer of (device, stream)."""
+        if f64:
+            need = h.forward_f64_bytes(B, T)
+        else:
+            need = self._ws_bytes_cache.get((B, T))
+            if need is None:
+                need = self._ws_bytes_cache[(B, T)] = h.workspace_bytes(B, T)
+        if workspace is None:
+            return self._stream_buffer(self._workspace, dev, stream, need)
+        if workspace.dtype != torch.uint8 or workspace.device != dev or workspace.numel() < need or workspace.data_ptr() % 256:
+            raise RuntimeError(f"tip_amd: workspace= must be a 256-byte aligned uint8 tensor of >= {need} bytes on {dev}")
+        return workspace
+
+    def _launch(self, h, launch, chain_only=False) -> bool:
+        """launch(), and the host's answer when it raises TipHandoffError: an EARLIER launch of this handle lost an inter-workgroup
+        hand-off (a co-tenant held CUs) — its outputs were NaN-poisoned and flagged.  _answer_handoff gives up the one-launch few-stream
+        form or demotes the handle to the plans that need no co-residency and clears the word, and THIS call is launched once more: a
+        co-tenant then costs throughput, not every following frame.  With TIP_OPT_AUTO_DEMOTE off, or nothing left to give up, the
+        error is reported.  chain_only (tip_forward_dropout, which a demoted handle does not serve): once more only when the answer
+        was "chain".  True when the call was launched."""
+        try:
+            launch()
+        except _lib.TipHandoffError:
+            how = self._answer_handoff(h)
+            if how is None:
+                raise
+            self._fast_state = None
+            if chain_only and how != "chain":
+                return False
+            launch()
+        return True
+
+    def _in_chunks(self, B, T, f64, single, chunk):
+        """None when one launch sequence serves B windows of length T; else chunk(lo, hi) over pieces of chunk_batch(T) windows, joined.
+        The kernels address their activations through 32-bit buffer descriptors (tip_forward) / 32-bit element offsets and grid
+        limits (tip_forward_f64): the library says how many windows one call serves (tip_max_batch; TIP_ERR_UNSUPPORTED_CONFIG
+        beyond: B > 13 107 at T = 40 for the paper configuration).  Streams are independent (no op in :60-102 crosses batch
+        elements), so a larger batch is run in chunks — same numbers, one launch sequence per chunk.  (The past-state keep
+        mask and the input dropout are drawn per chunk, like any two calls.)  single: the caller passed what serves one sequence only."""
         max_b = self.chunk_batch(T, f64)
-        if B > max_b:
-            if workspace is not None or out is not None:
-                raise RuntimeError("tip_amd: workspace= / out= serve a single launch sequence (batch within tip_max_batch)")
-            km = None if isinstance(keep_mask, str) else keep_mask
-            parts = []
-            for lo in range(0, B, max_b):
-                hi = min(B, lo + max_b)
-                parts.append(self._forward_hip(x_imu[lo:hi], x_s[lo:hi], last_row_only,
-                                               keep_mask if km is None else km[lo:hi], apply_in_dropout,
-                                               rows=None if rows is None else rows[lo:hi]))
-            return torch.cat(parts, dim=0)
-        # (the library launches on the CURRENT device: switch only when it is another one — the context manager costs ~3 us)
-        with (torch.cuda.device(dev) if torch.cuda.current_device() != dev.index else _NO_CTX):
+        if B <= max_b:
+            return None
+        if single:
+            raise RuntimeError("tip_amd: workspace= / out= / seeds_dev= serve a single launch sequence (batch within tip_max_batch)")
+        return torch.cat([chunk(lo, min(B, lo + max_b)) for lo in range(0, B, max_b)], dim=0)
+
+    def _keep_mask_args(self, mask, dtype):
+        """The past-state keep mask as the entry points take it.  mask: a tensor, the seed the library draws it from (int), or None ->
+        (contiguous tensor of `dtype` or None, its pointer or None, scale, seed or None)."""
+        if mask is None:
+            return None, None, 1.0, None
+        pd = self.past_state_dropout
+        scale = 1.0 / (1.0 - pd) if pd < 1.0 else 0.0
+        if isinstance(mask, int):
+            return None, None, scale, mask
+        mask = mask.to(dtype).contiguous()
+        return mask, mask.data_ptr(), scale, None
+
+    def _forward_hip(self, x_imu, x_s, last_row_only: bool, keep_mask="draw", apply_in_dropout=True, workspace=None, out=None, rows=None):
+        B, T, dev = self._check_windows(x_imu, x_s)
+        pdt = x_imu.dtype
+        f64 = pdt == torch.float64          # train_model.py:84-85: the whole model in double -> tip_forward_f64
+        h = self._ensure_handle()
+        km = None if isinstance(keep_mask, str) else keep_mask
+        y = self._in_chunks(B, T, f64, workspace is not None or out is not None,
+                            lambda lo, hi: self._forward_hip(x_imu[lo:hi], x_s[lo:hi], last_row_only, keep_mask if km is None else km[lo:hi],
+                                                             apply_in_dropout, rows=None if rows is None else rows[lo:hi]))
+        if y is not None:
+            return y
+        with _lib.on_device(dev):
             # A few streams (the runners' call, the latency benchmark): the kernels are queued FIRST and the ~8 us "did a parameter
             # change since the image was packed" walk runs beside the GPU; if it did, the image is re-packed and the forward queued
             # again behind the stale one (stream order: `y` is overwritten before anybody can read it).
             est = self._eval_state
             trusted = (not f64 and not self._frozen and B <= self.LAZY_STASH_MAX_BATCH and est is not None and est[0] == dev and
                        self._packed_dev is not None and self._packed_dev.device == dev)
-            if not trusted and not f64 and (self._packed_dev is None or self._packed_dev.device != dev or
-                                            (not self._frozen and self._packed_key != self._param_key(dev))):
-                self.refresh_packed(dev)
+            if not trusted and not f64:
+                self._packed_current(dev)
             x_imu_c = x_imu.contiguous()
             x_s_c = x_s.contiguous()
             if apply_in_dropout and self.in_dropout > 0.0:  # :73 — a fresh nn.Dropout is always in training mode
                 x_imu_c = F.dropout(x_imu_c, self.in_dropout, training=True)
-            flags = 0
-            mask_ptr, scale = None, 1.0
             mask = self._draw_keep_mask(x_s_c) if isinstance(keep_mask, str) else keep_mask   # :77
-            if mask is not None:
-                p = self.past_state_dropout
-                mask = mask.to(pdt).contiguous()
-                mask_ptr, scale = mask.data_ptr(), (1.0 / (1.0 - p) if p < 1.0 else 0.0)
-                flags |= _lib.TIP_FWD_KEEP_MASK
-            if last_row_only:
-                flags |= _lib.TIP_FWD_LAST_ROW_ONLY
-            shape = (B, self.size_s) if last_row_only else (B, T, self.size_s)
-            if out is not None:
-                if tuple(out.shape) != shape or out.dtype != pdt or out.device != dev or not out.is_contiguous():
-                    raise RuntimeError(f"tip_amd: out= must be a contiguous {pdt} tensor of shape {shape} on {dev}")
-                y = out
-            else:
-                y = torch.empty(shape, dtype=pdt, device=dev)
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            mask, mask_ptr, scale, _ = self._keep_mask_args(mask, pdt)
+            flags = (_lib.TIP_FWD_KEEP_MASK if mask is not None else 0) | (_lib.TIP_FWD_LAST_ROW_ONLY if last_row_only else 0)
+            y = _output(out, (B, self.size_s) if last_row_only else (B, T, self.size_s), pdt, dev)
+            stream = _lib.current_stream(dev)
             if rows is not None and f64:
                 raise RuntimeError("tip_amd: forward_rows computes in fp32 only")
+            ws = self._workspace_for(h, B, T, dev, stream, workspace, f64)
             if f64:
                 params = [p.detach() for p in self.state_dict().values()]
                 if any(p.dtype != torch.float64 or p.device != dev for p in params):
                     raise RuntimeError("tip_amd.TF_RNN_Past_State: fp64 forward needs every parameter in fp64 on the inputs' GPU")
                 params = [p.contiguous() for p in params]
-                ws = workspace if workspace is not None else self._stream_buffer(self._workspace, dev, stream, h.forward_f64_bytes(B, T))
                 h.forward_f64([p.data_ptr() for p in params], x_imu_c.data_ptr(), x_s_c.data_ptr(), y.data_ptr(), B, T,
                               flags & _lib.TIP_FWD_LAST_ROW_ONLY, mask_ptr, scale, ws.data_ptr(), ws.numel(), stream)
                 return y
-            need = self._ws_bytes_cache.get((B, T))
-            if need is None:
-                need = self._ws_bytes_cache[(B, T)] = h.workspace_bytes(B, T)
-            if workspace is not None:
-                if workspace.dtype != torch.uint8 or workspace.device != dev or workspace.numel() < need or workspace.data_ptr() % 256:
-                    raise RuntimeError(f"tip_amd: workspace= must be a 256-byte aligned uint8 tensor of >= {need} bytes on {dev}")
-                ws = workspace
-            else:
-                ws = self._stream_buffer(self._workspace, dev, stream, need)
             if rows is not None:     # tip_forward_rows: the same launch sequence, one chosen row per window out of the projection
                 def launch():
                     h.forward_rows(x_imu_c.data_ptr(), x_s_c.data_ptr(), y.data_ptr(), B, T, rows.data_ptr(), flags, mask_ptr, scale,
@@ -941,16 +935,7 @@ class TF_RNN_Past_State(nn.Module):
                 def launch():
                     h.forward(x_imu_c.data_ptr(), x_s_c.data_ptr(), y.data_ptr(), B, T, flags, mask_ptr, scale,
                               ws.data_ptr(), ws.numel(), stream)
-            try:
-                launch()
-            except _lib.TipHandoffError:
-                # An EARLIER launch of this handle lost an inter-workgroup hand-off (a co-tenant held CUs): its outputs were
-                # NaN-poisoned and flagged.  First time: demote the handle to the plans that need no co-residency (hybrid
-                # encoder + single-workgroup recurrence tiles), clear the word and run THIS call — a co-tenant then costs
-                # throughput, not every following frame.  TIP_OPT_AUTO_DEMOTE = 0 (or a second loss) reports the error.
-                if self._answer_handoff(h) is None:
-                    raise
-                launch()
+            self._launch(h, launch)
             if not self._frozen and B <= self.LAZY_STASH_MAX_BATCH:
                 plist = self._plist()
                 ptrs, vsum = list(map(_data_ptr, plist)), sum(map(_version, plist))
@@ -1019,6 +1004,38 @@ def _hip_input_grads(module, h, want_imu, want_s, bwd_inputs, pc, scratch, B, T,
     return dxi, dxs
 
 
+def _hip_train_forward(module, h, params, xi, xs, mask_ptr, scale, p_drop, seed, stream):
+    """tip_train_forward (the _f64 form for fp64 windows) into a fresh activation stash: (y, saved)."""
+    B, T, pdt, dev = int(xi.shape[0]), int(xi.shape[1]), xi.dtype, xi.device
+    f64 = pdt == torch.float64
+    saved = torch.empty(h.train_bytes(B, T, fp64=f64)[0], dtype=torch.uint8, device=dev)
+    y = torch.empty((B, T, module.size_s), dtype=pdt, device=dev)
+    pc = [p.detach().contiguous() for p in params]
+    h.train_forward([p.data_ptr() for p in pc], xi.data_ptr(), xs.data_ptr(), mask_ptr, scale, p_drop, seed, y.data_ptr(), saved.data_ptr(),
+                    saved.numel(), B, T, stream, fp64=f64)
+    return y, saved
+
+
+def _hip_train_backward(module, h, params, g, saved, p_drop, seed, B, T, want_inputs, want_params, bwd_inputs, stream):
+    """tip_train_backward on the stash `saved` for the cotangent g [B, T, size_s], then tip_train_input_grads where wanted:
+    (d x_imu, d x_s, [gradient of params[i] — a view of one flat buffer — or None where want_params[i] is False])."""
+    pdt, dev = g.dtype, g.device
+    f64 = pdt == torch.float64
+    scratch = module._stream_buffer(module._train_scratch, dev, stream, h.train_bytes(B, T, fp64=f64)[1])
+    total = sum(p.numel() for p in params)
+    flat = torch.empty(total, dtype=pdt, device=dev)
+    pc = [p.detach().contiguous() for p in params]
+    h.train_backward([p.data_ptr() for p in pc], g.data_ptr(), saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(),
+                     flat.data_ptr(), total, p_drop, seed, B, T, stream, fp64=f64)
+    dxi, dxs = _hip_input_grads(module, h, want_inputs[0], want_inputs[1], bwd_inputs, pc, scratch, B, T, stream)
+    out, off = [], 0
+    for p, want in zip(params, want_params):
+        n = p.numel()
+        out.append(flat[off:off + n].view(p.shape) if want else None)
+        off += n
+    return dxi, dxs, out
+
+
 class _HipTrainFunction(torch.autograd.Function):
     """The model call of the reference training loop (train_model.py:175 forward, :192 backward) on the HIP kernels.
     forward: tip_train_forward (activations stashed in `saved`, encoder dropout from a counter-based hash of `seed`);
@@ -1027,20 +1044,17 @@ class _HipTrainFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, module, x_imu, x_s, mask, p_drop, seed, *params):
         h = module._ensure_handle()
-        dev = x_imu.device
-        B, T = int(x_imu.shape[0]), int(x_imu.shape[1])
-        n_imu = module.input_size_imu + (18 if module.with_acc_sum else 0)
-        if x_imu.shape[2] != n_imu or x_s.shape[2] != module.size_s:
-            raise RuntimeError(f"mat1 and mat2 shapes cannot be multiplied: got feature widths "
-                               f"{x_imu.shape[2]}+{x_s.shape[2]}, in_linear expects {n_imu}+{module.size_s}")
+        B, T, dev = int(x_imu.shape[0]), int(x_imu.shape[1]), x_imu.device
         pdt = x_imu.dtype                                  # fp32, or fp64 for a module built under --double (_hip_train_ok: no mixes)
-        f64 = pdt == torch.float64
         # a few windows: already on the GPU's queue (module._few_window_train_launch, called by _dispatch in front of this apply;
         # False = tried, not served that way)
         pre, module._pre_launched = module._pre_launched, None
         if pre is None:
             pre = module._few_window_train_launch(x_imu, x_s, mask, p_drop, seed)
         lazy = bool(pre)
+        if not lazy:
+            module._check_windows(x_imu, x_s)              # (_hip_train_ok has let the call through: the widths are what is left;
+                                                           #  a launched few-window call has them right)
         saved = None
         if lazy:
             y, xi, xs, lazy_mask, scale = pre
@@ -1049,23 +1063,12 @@ class _HipTrainFunction(torch.autograd.Function):
         else:
             with torch.cuda.device(dev):
                 xi, xs = x_imu.contiguous(), x_s.contiguous()
-                pd = module.past_state_dropout
-                mask_ptr, scale = None, (1.0 / (1.0 - pd) if pd < 1.0 else 0.0) if mask is not None else 1.0
-                state_seed = mask if isinstance(mask, int) else None     # the keep mask as (p, seed): drawn by the library
-                if state_seed is not None:
+                mask, mask_ptr, scale, state_seed = module._keep_mask_args(mask, pdt)
+                if state_seed is not None:                   # the keep mask as (p, seed): written out by the library
                     mask = module._hash_keep_mask(xs, state_seed)
                     mask_ptr = mask.data_ptr()
-                elif mask is not None:
-                    mask = mask.to(pdt).contiguous()
-                    mask_ptr = mask.data_ptr()
-                y = torch.empty((B, T, module.size_s), dtype=pdt, device=dev)
-                stream = torch.cuda.current_stream(dev).cuda_stream
-                saved_bytes, _ = h.train_bytes(B, T, fp64=f64)
-                saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
-                pc = [p.detach().contiguous() for p in params]
-                h.train_forward([p.data_ptr() for p in pc], xi.data_ptr(), xs.data_ptr(), mask_ptr, scale, p_drop, seed,
-                                y.data_ptr(), saved.data_ptr(), saved.numel(), B, T, stream, fp64=f64)
-        ctx.module, ctx.dims, ctx.p_drop, ctx.seed, ctx.f64 = module, (B, T), p_drop, seed, f64
+                y, saved = _hip_train_forward(module, h, params, xi, xs, mask_ptr, scale, p_drop, seed, _lib.current_stream(dev))
+        ctx.module, ctx.dims, ctx.p_drop, ctx.seed = module, (B, T), p_drop, seed
         ctx.saved_stash = saved
         # no stash yet: backward re-runs the forward on (xi, xs, keep mask or its seed) — the tensors go through save_for_backward, so
         # an in-place edit of the inputs between forward and backward is an autograd error, not a silently different gradient
@@ -1097,42 +1100,23 @@ class _HipTrainFunction(torch.autograd.Function):
         dev = gy.device
         with torch.cuda.device(dev):
             saved = ctx.saved_stash
-            f64 = ctx.f64
-            pdt = torch.float64 if f64 else torch.float32
-            stream = torch.cuda.current_stream(dev).cuda_stream
+            stream = _lib.current_stream(dev)
             if saved is None and lazy_in is not None and not getattr(ctx, "lazy_done", False):
                 # the forward ran without a stash (few windows, tip_forward_dropout): produce it now — tip_train_forward with the same
                 # inputs, keep mask, dropout probability and seed evaluates the same function with the same keep decisions
                 xi, xs, mask, scale = lazy_in
                 if isinstance(mask, int):
                     mask = module._hash_keep_mask(xs, mask)
-                saved_bytes, _ = h.train_bytes(B, T, fp64=f64)
-                saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
-                y2 = torch.empty((B, T, module.size_s), dtype=pdt, device=dev)
-                pc0 = [p.detach().contiguous() for p in params]
-                h.train_forward([p.data_ptr() for p in pc0], xi.data_ptr(), xs.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                scale, ctx.p_drop, ctx.seed, y2.data_ptr(), saved.data_ptr(), saved.numel(), B, T, stream, fp64=f64)
+                _, saved = _hip_train_forward(module, h, params, xi, xs, mask.data_ptr() if mask is not None else None, scale, ctx.p_drop,
+                                              ctx.seed, stream)
                 ctx.lazy_done = True
             if saved is None:
                 raise RuntimeError("tip_amd: backward through the HIP training step a second time — the activation stash "
                                    "is released after the first backward (retain_graph=True is not supported; run the "
                                    "forward again)")
-            _, scratch_bytes = h.train_bytes(B, T, fp64=f64)
-            scratch = module._stream_buffer(module._train_scratch, dev, stream, scratch_bytes)
-            total = sum(p.numel() for p in params)
-            flat = torch.empty(total, dtype=pdt, device=dev)
-            pc = [p.detach().contiguous() for p in params]
-            g = gy.to(pdt).contiguous()
-            h.train_backward([p.data_ptr() for p in pc], g.data_ptr(), saved.data_ptr(), saved.numel(),
-                             scratch.data_ptr(), scratch.numel(), flat.data_ptr(), total,
-                             ctx.p_drop, ctx.seed, B, T, stream, fp64=f64)
-            dxi, dxs = _hip_input_grads(module, h, ctx.needs_input_grad[1], ctx.needs_input_grad[2], ctx.bwd_inputs, pc, scratch, B, T, stream)
+            dxi, dxs, out = _hip_train_backward(module, h, params, gy.to(params[0].dtype).contiguous(), saved, ctx.p_drop, ctx.seed, B, T,
+                                                ctx.needs_input_grad[1:3], ctx.needs_input_grad[6:], ctx.bwd_inputs, stream)
         ctx.saved_stash = None
-        out, off = [], 0
-        for i, p in enumerate(params):
-            n = p.numel()
-            out.append(flat[off:off + n].view(p.shape) if ctx.needs_input_grad[6 + i] else None)
-            off += n
         return (None, dxi, dxs, None, None, None, *out)
 
 
@@ -1161,21 +1145,10 @@ class _HipForwardHipBackward(torch.autograd.Function):
         dev = gy.device
         B, T = int(xi.shape[0]), int(xi.shape[1])
         pdt = xi.dtype
-        f64 = pdt == torch.float64
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            mask_ptr, scale = None, 1.0
-            if mask is not None:
-                pd = module.past_state_dropout
-                mask = mask.to(pdt).contiguous()
-                mask_ptr, scale = mask.data_ptr(), (1.0 / (1.0 - pd) if pd < 1.0 else 0.0)
-            saved_bytes, scratch_bytes = h.train_bytes(B, T, fp64=f64)
-            saved = torch.empty(saved_bytes, dtype=torch.uint8, device=dev)
-            y2 = torch.empty((B, T, module.size_s), dtype=pdt, device=dev)
-            pc = [p.detach().contiguous() for p in params]
-            ptrs = [p.data_ptr() for p in pc]
-            h.train_forward(ptrs, xi.data_ptr(), xs.data_ptr(), mask_ptr, scale, 0.0, 0, y2.data_ptr(), saved.data_ptr(), saved.numel(),
-                            B, T, stream, fp64=f64)
+            stream = _lib.current_stream(dev)
+            mask, mask_ptr, scale, _ = module._keep_mask_args(mask, pdt)
+            _, saved = _hip_train_forward(module, h, params, xi, xs, mask_ptr, scale, 0.0, 0, stream)
             if module.keep_train_stash:
                 module.last_train_stash = (saved, B, T)
             if ctx.last:      # the cotangent of row T-1 only: zero everywhere else
@@ -1183,17 +1156,8 @@ class _HipForwardHipBackward(torch.autograd.Function):
                 g[:, -1] = gy.to(pdt)
             else:
                 g = gy.to(pdt).contiguous()
-            scratch = module._stream_buffer(module._train_scratch, dev, stream, scratch_bytes)
-            total = sum(p.numel() for p in params)
-            flat = torch.empty(total, dtype=pdt, device=dev)
-            h.train_backward(ptrs, g.data_ptr(), saved.data_ptr(), saved.numel(), scratch.data_ptr(), scratch.numel(), flat.data_ptr(),
-                             total, 0.0, 0, B, T, stream, fp64=f64)
-            dxi, dxs = _hip_input_grads(module, h, ctx.needs_input_grad[2], ctx.needs_input_grad[3], (xs, mask, scale), pc, scratch, B, T, stream)
-        out, off = [], 0
-        for i, p in enumerate(params):
-            n = p.numel()
-            out.append(flat[off:off + n].view(p.shape) if ctx.needs_input_grad[5 + i] else None)
-            off += n
+            dxi, dxs, out = _hip_train_backward(module, h, params, g, saved, 0.0, 0, B, T, ctx.needs_input_grad[2:4], ctx.needs_input_grad[5:],
+                                                (xs, mask, scale), stream)
         return (None, None, dxi, dxs, None, *out)
 
 

@@ -248,11 +248,10 @@ class _StreamBase:
         self.reset()
 
     def _check(self, status: int):
-        if status < 0:
-            raise _lib.TipStatusError(status, self.lib.tip_strerror(status).decode())
+        return _lib.check(status)
 
     def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+        return _lib.current_stream(self.device)
 
     def _call(self, name: str, *args):
         """tip_stream_<name>(*args, stream) on the current stream at window 40 — the 40-row entry points, as ever — and
