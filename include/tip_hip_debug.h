@@ -5,16 +5,16 @@
  * switch was set at launch) and returns 0, -1 for a bad `n`, -5 for a HIP error.
  *
  * Environment switches of the MEASUREMENT BUILD (csrc: `make measure` -> libtip_hip_measure.so, -DTIP_MEASURE; the default library
- * reads none of them — its kernel selection depends on tip_set_option only):
+ * reads none of them — its kernel selection depends on tip_set_option only).  csrc/tip_measure.h is the table (name, type, default,
+ * meaning, one line each) and the library reads it in one place; this list repeats exactly its names:
  *   traces (fill the arrays the readers below copy): TIP_FUSEDH_TRACE, TIP_FUSED2_TRACE, TIP_BWD_TRACE, TIP_RNN_TRACE, TIP_HEAD_TRACE,
- *     TIP_S16_TRACE
- *   ablations (wrong results, timing only): TIP_FUSED_ABLATE, TIP_RNN_ABLATE (bits: 1 polls never wait, 2 no MFMAs, 4 no row touches,
+ *     TIP_FLOW_TRACE
+ *   ablation (wrong results, timing only): TIP_RNN_ABLATE (bits: 1 polls never wait, 2 no MFMAs, 4 no row touches,
  *     16 A fragments of the first two batches only — a quarter of the LDS reads, 32 clamp instead of tanh; 128+ trace stamp selection)
- *   A/B selections: TIP_AUTO_SPLIT=0 (no rounds + remainder split), TIP_AUTO_MERGE=0 (no shared tail), TIP_RNN_ROWS4=0 / TIP_RNN_W4=0|1 / TIP_RNN_C16=4 / TIP_RNN_HANDOFF=0 /
- *     TIP_RNN_PREPOLL=0 / TIP_RNN_ROTATE=0 (recurrence variants), TIP_HEAD=old (streaming projection kernel), TIP_GENERAL_PGEMM=0 /
- *     TIP_GENERAL_GEMM=32 / TIP_GENERAL_ATTN=v (general plan), TIP_TRAIN_FUSED=0 / TIP_TRAIN_FUSED_BWD=0 / TIP_TRAIN_FWD_PADDED /
- *     TIP_TRAIN_WIN_GEMM=0 / TIP_TRAIN_PGEMM=0 / TIP_TGEMM_TILE / TIP_TGEMM16_TILE / TIP_DW_KERNEL / TIP_DW_SPLITS / TIP_DW_SPLITDIV /
- *     TIP_DW_GROUP / TIP_DW_NB (training step)
+ *   A/B selections: TIP_AUTO_SPLIT=0 (no rounds + remainder split), TIP_AUTO_MERGE=0 (no shared tail), TIP_RNN_ROWS4=0 / TIP_RNN_W4=0|1
+ *     (recurrence variants), TIP_HEAD=old (streaming projection kernel), TIP_LAT_FLOW=n (largest batch of the few-stream plan's
+ *     one-launch form; 0: launch chain), TIP_DW_GROUP=0 (training step: one launch per weight gradient)
+ * A boolean switch is off exactly when its value starts with '0'; TIP_RNN_ABLATE, TIP_RNN_W4 and TIP_LAT_FLOW are read with atoi.
  */
 #ifndef TIP_HIP_DEBUG_H
 #define TIP_HIP_DEBUG_H

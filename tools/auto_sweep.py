@@ -1,5 +1,6 @@
 """AUTO plan over a batch sweep: step time, frames/s, fraction of fp32-MFMA peak (run on the GPU box).
-TIP_AUTO_SPLIT=0 TIP_PLAN_BASE=1 reproduces the round-3 selection (no remainder split, no window-split plan) for comparison."""
+TIP_AUTO_SPLIT=0 TIP_PLAN_BASE=1 reproduces the round-3 selection (no remainder split, no window-split plan) for comparison:
+TIP_AUTO_SPLIT is a switch of the measurement build (csrc/tip_measure.h; TIP_LIB=measure is set here), TIP_PLAN_BASE is this script's own."""
 import contextlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """B = 1 (few-stream) forward: p50 of the .eval() forward (full / last row), of the .train()-mode call with dropout live (what the unedited
 runner pays on the device) and the back-to-back period of 300 queued forwards.  Environment switches of the measurement build apply
-(TIP_LIB=measure is set here).  usage: [TIP_LAT_XCD=1 ...] python tools/b1_chain.py [B = 1] [T = 40]"""
-import contextlib, os, sys, warnings
+(TIP_LIB=measure is set here; csrc/tip_measure.h lists them): TIP_LAT_FLOW=0 keeps the launch chain at every batch, TIP_LAT_FLOW=64 the
+one-launch form up to 64 windows; both give the same outputs (the line ends with a digest of the .eval() output).  usage: [TIP_LAT_FLOW=0 ...] python tools/b1_chain.py [B = 1] [T = 40]"""
+import contextlib, hashlib, os, sys, warnings
 os.environ.setdefault("TIP_LIB", "measure")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -46,10 +47,11 @@ with torch.no_grad():
         me.forward_last(xi, xs)
     e1.record(); e1.synchronize()
     period = e0.elapsed_time(e1) / 300
+    digest = hashlib.sha256(me(xi, xs).cpu().numpy().tobytes()).hexdigest()[:16]
 for _ in range(50):
     mt(xi, xs)
 c = p50(lambda: mt(xi, xs))
 me.check_handoffs(); mt.check_handoffs()
 tags = " ".join(f"{k}={v}" for k, v in sorted(os.environ.items()) if k.startswith("TIP_") and k != "TIP_LIB")
 print(f"B={B} T={T} [{tags}] eval full p50 {a[0]*1e3:.1f} p95 {a[1]*1e3:.1f} us | last row p50 {b[0]*1e3:.1f} p95 {b[1]*1e3:.1f} | back-to-back {period*1e3:.1f} | "
-      f".train() dropout p50 {c[0]*1e3:.1f} p95 {c[1]*1e3:.1f}")
+      f".train() dropout p50 {c[0]*1e3:.1f} p95 {c[1]*1e3:.1f} | y sha256 {digest}")

@@ -143,12 +143,10 @@ struct StageScope {
 // has one and the batch is big enough, else the LDS-tiled GEMM on the row-major copy
 static hipError_t linear_gemm(const float* P, const tip::PackedLinear& p, const float* A, int lda, const float* res, int ldres,
                               float* C, int ldc, int M, int flags, hipStream_t s) {
-    static int use_pg = -1;   // TIP_GENERAL_PGEMM=0 keeps the LDS-tiled kernel (measurement)
-    if (use_pg < 0) use_pg = (tip_env("TIP_GENERAL_PGEMM") && tip_env("TIP_GENERAL_PGEMM")[0] == '0') ? 0 : 1;
     // (the panel kernel's epilogue moves 16 bytes per lane: bias / residual / output rows must be 16-byte aligned — they are for
     //  every buffer the library carves out itself)
     auto al16 = [](const void* q, int ld) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0 && (ld & 3) == 0; };
-    if (use_pg && p.f_off && tip::pgemm_shape_ok(M, p.N, p.K) && al16(P + p.b_off, 0) && al16(C, ldc) && (!(flags & 2) || al16(res, ldres)))
+    if (p.f_off && tip::pgemm_shape_ok(M, p.N, p.K) && al16(P + p.b_off, 0) && al16(C, ldc) && (!(flags & 2) || al16(res, ldres)))
         return tip::launch_pgemm(A, lda, P + p.f_off, (size_t)p.N * p.K, P + p.b_off, res, ldres, C, ldc, M, p.N, p.K, flags, s);
     return tip::launch_gemm(A, lda, P + p.w_off, p.Kpad, P + p.b_off, res, ldres, C, ldc, M, p.N, p.Npad, flags, s);
 }

@@ -245,13 +245,7 @@ int tip_combine_sequence(const double* imu, const double* s, const double* c, in
     hipStream_t st = static_cast<hipStream_t>(stream);
     double* la = static_cast<double*>(scratch);
     constexpr size_t comb_lds = (size_t)kCombLdsDoubles * sizeof(double);
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(combine_imu_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)comb_lds) != hipSuccess)
-            return TIP_ERR_HIP;
-        attr_set = true;
-    }
+    if (dynamic_lds<combine_imu_kernel>((int)comb_lds) != hipSuccess) return TIP_ERR_HIP;
     hipLaunchKernelGGL(combine_imu_kernel, dim3((Lp + kCombFrames - 1) / kCombFrames), dim3(kCombThreads), comb_lds, st, imu, bias, Lp,
                        imu_out, la);
     hipLaunchKernelGGL(acc_sum_kernel, dim3((Lp + kSumFrames - 1) / kSumFrames), dim3(256), 0, st, la, Lp, sum_out);

@@ -176,7 +176,7 @@ __device__ __forceinline__ void ring_prefetch(WRing<NBW>& g, __amdgpu_buffer_rsr
 //   loop => counted vmcnt waits); for the LAST pair it is redirected to k-blocks 0,1 of the NEXT phase
 //   (nsoff / nnstride_b), so on exit the ring is already primed for a following phase of the same width.
 //   Callers without such a successor pass their own soff (a harmless in-bounds reload).
-template <int NBW, int KB, bool NOMMA = false, int SWAPN = 0, bool PIN = true>
+template <int NBW, int KB, int SWAPN = 0, bool PIN = true>
 __device__ __forceinline__ void gemm_phase(f32x4 (&acc)[fz::RB][NBW], const float* As, int lda, __amdgpu_buffer_rsrc_t rsrc,
                                            int voff, int soff, int nstride_b, WRing<NBW>& g, int nsoff, int nnstride_b) {
     static_assert(KB % 2 == 0, "k-blocks are processed in pairs");
@@ -192,8 +192,7 @@ __device__ __forceinline__ void gemm_phase(f32x4 (&acc)[fz::RB][NBW], const floa
         const int st = last ? nnstride_b : nstride_b;
 #pragma unroll
         for (int r = 0; r < fz::RB; ++r) a1[r] = *reinterpret_cast<const float4*>(As + r * 16 * lda + (kb + 1) * 16);
-        if (!NOMMA) mfma_block<NBW, SWAPN>(acc, a0, g.w0);
-        else { asm volatile("" :: "v"(a0[0].x), "v"(g.w0[0].x)); }
+        mfma_block<NBW, SWAPN>(acc, a0, g.w0);
 #pragma unroll
         for (int n = 0; n < NBW; ++n) g.w0[n] = load_frag(rsrc, voff, o + n * st);
         // PIN: keep the refill here (the scheduler may sink it towards its use).  Measured: helps the training forward and the
@@ -201,8 +200,7 @@ __device__ __forceinline__ void gemm_phase(f32x4 (&acc)[fz::RB][NBW], const floa
         if (PIN) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int r = 0; r < fz::RB; ++r) a0[r] = *reinterpret_cast<const float4*>(As + r * 16 * lda + (kb + 2) * 16);
-        if (!NOMMA) mfma_block<NBW, SWAPN>(acc, a1, g.w1);
-        else { asm volatile("" :: "v"(a1[0].x), "v"(g.w1[0].x)); }
+        mfma_block<NBW, SWAPN>(acc, a1, g.w1);
 #pragma unroll
         for (int n = 0; n < NBW; ++n) g.w1[n] = load_frag(rsrc, voff, o + n * st + 1024);
         if (PIN) __builtin_amdgcn_sched_barrier(0);
@@ -227,18 +225,10 @@ __device__ __forceinline__ int opaque(int v) {
     return v;
 }
 
-// rows 0..T-1 of an LDS tile [rows][ld] (cols floats wide) -> HBM rows of stride dst_ld, 16-byte stores
-__device__ __forceinline__ void rows_to_hbm(const float* lds, int ld, int cols, float* dst, int dst_ld, int T, int tid) {
-    const int c4n = cols >> 2;
-    for (int i = tid; i < T * c4n; i += fz::THREADS) {
-        const int r = i / c4n, c4 = i - r * c4n;
-        // streaming stores: the stash (2 MB per window) is read next by the backward, the weights it would push out of L2 in 0.1 us
-        __builtin_nontemporal_store(*reinterpret_cast<const f32x4*>(lds + r * ld + c4 * 4), reinterpret_cast<f32x4*>(dst + (size_t)r * dst_ld + c4 * 4));
-    }
-}
-
-// The same with a FIXED number of stores per thread (T <= 40: the hybrid kernel), rows >= T dropped by the buffer's range check instead
-// of by the loop bound.  With the run-time trip count above the compiler cannot count the stores in flight, and the `s_waitcnt vmcnt(N)`
+// rows 0..T-1 of an LDS tile [rows][ld] (COLS floats wide) -> HBM rows of stride dst_ld, 16-byte streaming stores (the stash, 2 MB per
+// window, is read next by the backward; the weights it would push out of L2 in 0.1 us), with a FIXED number of stores per thread
+// (T <= 40: the hybrid kernel), rows >= T dropped by the buffer's range check instead of by a loop bound.  With a run-time trip count
+// the compiler cannot count the stores in flight, and the `s_waitcnt vmcnt(N)`
 // of the weight ring behind such a loop (vector memory retires in order, stores included) degenerates to "all but the last few":
 // every stash point waited for its own stores' acknowledgement before the next phase's first MFMA.
 template <int COLS>
@@ -254,57 +244,41 @@ __device__ __forceinline__ void rows_to_hbm_fixed(const float* lds, int ld, floa
     }
 }
 
-// The training forward's hidden chunk [T][256] (after ReLU and dropout): rows to HBM as rows_to_hbm does, plus the chunk's gates
+// The training forward's hidden chunk [T][256] (after ReLU and dropout): rows to HBM as rows_to_hbm_fixed does, plus the chunk's gates
 // (hidden > 0) as BITS for the fused FFN backward.  gb points at row 0 of the window in the gate-bit array [M][32 dwords]:
 //   dword (row, f*8 + 2*e + (c4 >> 5)), bit (c4 & 31)  =  hidden[row][f*256 + 4*c4 + e] > 0      (c4 = 0..63: column quad)
 // One wave iteration is one row (64 lanes = its 64 column quads): four ballots, 32 bytes stored by lane 0.  Round 5: ffn_bwd_kernel
 // read the gates as the saved fp32 hidden rows — 42 MB per layer that arrive cold from HBM in front of each chunk's weight ring
 // (vector memory returns in order: every chunk stalled ~4 000 cycles behind them); as bits they are 1.3 MB, staged into LDS once per window.
-template <bool FIXED>   // FIXED: five stores per thread whatever T <= 40 is (rows_to_hbm_fixed), lanes other than 0 drop the bit stores
+// Five stores per thread whatever T <= 40 is (as rows_to_hbm_fixed); lanes other than 0 drop the bit stores.
 __device__ __forceinline__ void hidden_to_hbm(const float* lds, int ld, float* dst, int dst_ld, unsigned* gb, int f, int T, int tid) {
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     const int lane = tid & 63;
-    if (FIXED) {
-        const __amdgpu_buffer_rsrc_t rs = tip_rows_buffer(dst, T * dst_ld * 4);
-        const __amdgpu_buffer_rsrc_t gs = tip_rows_buffer(reinterpret_cast<const float*>(gb), T * 128);
+    const __amdgpu_buffer_rsrc_t rs = tip_rows_buffer(dst, T * dst_ld * 4);
+    const __amdgpu_buffer_rsrc_t gs = tip_rows_buffer(reinterpret_cast<const float*>(gb), T * 128);
 #pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            const int r = (tid >> 6) + 8 * j;
-            const f32x4 v = *reinterpret_cast<const f32x4*>(lds + r * ld + lane * 4);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ln_u32x4, v), rs, (r * dst_ld + lane * 4) * 4, 0, kTipNT);
-            const unsigned long long b0 = __builtin_amdgcn_ballot_w64(v[0] > 0.f), b1 = __builtin_amdgcn_ballot_w64(v[1] > 0.f);
-            const unsigned long long b2 = __builtin_amdgcn_ballot_w64(v[2] > 0.f), b3 = __builtin_amdgcn_ballot_w64(v[3] > 0.f);
-            const int off = lane == 0 ? r * 128 + f * 32 : 0x7fffff00;      // one lane writes the row's 32 bytes; the others fall outside the buffer
-            const u32x4 lo = {(unsigned)b0, (unsigned)(b0 >> 32), (unsigned)b1, (unsigned)(b1 >> 32)};
-            const u32x4 hi = {(unsigned)b2, (unsigned)(b2 >> 32), (unsigned)b3, (unsigned)(b3 >> 32)};
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ln_u32x4, lo), gs, off, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ln_u32x4, hi), gs, off, 16, 0);
-        }
-        return;
-    }
-    for (int i = tid; i < T * 64; i += fz::THREADS) {
-        const int r = i >> 6;
+    for (int j = 0; j < 5; ++j) {
+        const int r = (tid >> 6) + 8 * j;
         const f32x4 v = *reinterpret_cast<const f32x4*>(lds + r * ld + lane * 4);
-        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(dst + (size_t)r * dst_ld + lane * 4));
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ln_u32x4, v), rs, (r * dst_ld + lane * 4) * 4, 0, kTipNT);
         const unsigned long long b0 = __builtin_amdgcn_ballot_w64(v[0] > 0.f), b1 = __builtin_amdgcn_ballot_w64(v[1] > 0.f);
         const unsigned long long b2 = __builtin_amdgcn_ballot_w64(v[2] > 0.f), b3 = __builtin_amdgcn_ballot_w64(v[3] > 0.f);
-        if (lane == 0) {
-            u32x4* o = reinterpret_cast<u32x4*>(gb + (size_t)r * 32 + f * 8);
-            o[0] = (u32x4){(unsigned)b0, (unsigned)(b0 >> 32), (unsigned)b1, (unsigned)(b1 >> 32)};
-            o[1] = (u32x4){(unsigned)b2, (unsigned)(b2 >> 32), (unsigned)b3, (unsigned)(b3 >> 32)};
-        }
+        const int off = lane == 0 ? r * 128 + f * 32 : 0x7fffff00;      // one lane writes the row's 32 bytes; the others fall outside the buffer
+        const u32x4 lo = {(unsigned)b0, (unsigned)(b0 >> 32), (unsigned)b1, (unsigned)(b1 >> 32)};
+        const u32x4 hi = {(unsigned)b2, (unsigned)(b2 >> 32), (unsigned)b3, (unsigned)(b3 >> 32)};
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ln_u32x4, lo), gs, off, 0, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ln_u32x4, hi), gs, off, 16, 0);
     }
 }
 
-// ABL != 0 builds are MEASUREMENT-ONLY ablations (wrong results): 1 = no attention, 2 = no LayerNorm, 4 = no MFMA,
-// 8 = no epilogue LDS traffic.  Selected with TIP_FUSED_ABLATE=<mask>; the product path always runs ABL = 0.
-template <int ABL>
+// TIP_PLAN_FUSED: the 48-row inference kernel.  (The training, live and traced forwards are fused_encoder_h_kernel's.)
+// The last argument is not read.  It holds the place of the hybrid kernel's FusedTrain in the kernel-argument block: the implicit
+// arguments (gridDim) sit behind it, and their offset is a constant in the code, which is the code the plan's tests and figures are of.
 __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
     const float* __restrict__ wts, const float* __restrict__ x_imu, const float* __restrict__ x_s,
     const float* __restrict__ keep_mask, float keep_scale, float* __restrict__ xout, float* __restrict__ ih_out,
-    unsigned* __restrict__ hall_sentinel, int B, int T, int NI, int S, int L, int wbytes, int ih_off_b, FusedTrain tr) {
+    unsigned* __restrict__ hall_sentinel, int B, int T, int NI, int S, int L, int wbytes, int ih_off_b, FusedTrain) {
     using namespace fz;
-    constexpr bool TR = (ABL & 8) != 0;   // training forward: stash activations, apply the encoder's dropout
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* X = smem;
     float* C = smem + X_FLOATS;
@@ -345,7 +319,7 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
         {
             f32x4 acc[RB][2];
             zero_acc<2>(acc);
-            gemm_phase<2, KIN / 16, (ABL & 4) != 0, 0, TR>(acc, U + l15 * LDU + lg * 4, LDU, rsrc, voff, in_soff, (KIN / 16) * 1024, g_in, in_soff,
+            gemm_phase<2, KIN / 16, 0, false>(acc, U + l15 * LDU + lg * 4, LDU, rsrc, voff, in_soff, (KIN / 16) * 1024, g_in, in_soff,
                                     (KIN / 16) * 1024);
             // layer 0, chunk 0 QKV fragments fly during the epilogue + barrier
             ring_prefetch<3>(g_qkv, rsrc, voff, (int)(LAYER0 * 4) + (int)(QKV_W * 4) + wave * 16 * 1024, 16 * 16 * 1024);
@@ -360,18 +334,11 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
             }
         }
         __syncthreads();
-        const size_t grow0 = (size_t)win * T;           // first global row (b*T + t) of this window
-        if (TR) rows_to_hbm(X, LDX, D, tr.sv + (size_t)tr.x0 * 64 + grow0 * D, D, T, tid);
 
 #pragma unroll 1
         for (int layer = 0; layer < L; ++layer) {
             const float* LW = wts + LAYER0 + (size_t)layer * LAYER_FLOATS;
             const int lbase = (int)((LAYER0 + (size_t)layer * LAYER_FLOATS) * 4);
-            float* svl = TR ? tr.sv + (size_t)layer * tr.layer_stride * 64 : nullptr;   // this layer's stash
-            // dropout keys of this layer's sites 1..3 (site 0, the attention probabilities, is keyed inside attention_head_regs)
-            const unsigned dk1 = TR ? tip_drop_key_s(tr.seed, (unsigned)(layer * 4 + 1)) : 0u;
-            const unsigned dk2 = TR ? tip_drop_key_s(tr.seed, (unsigned)(layer * 4 + 2)) : 0u;
-            const unsigned dk3 = TR ? tip_drop_key_s(tr.seed, (unsigned)(layer * 4 + 3)) : 0u;
             float* Qc = C;   // attention output of one 8-head chunk [48 rows][128 channels]: the out-projection's A operand
             // ---- self-attention block: two chunks of 8 heads; wave w owns head 8c + w end to end -----------------
             f32x4 acc_o[RB][2];
@@ -389,7 +356,7 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
                     // Q and K are projected with swapped MFMA operands: their accumulators come out as (channels 4*lg + e,
                     // row l15) — the fragments S^T = K Q^T wants — and V in the plain layout P V wants, so this wave's head
                     // runs projection -> scores -> softmax -> P V entirely in registers: no Q/K/V planes, no barrier here.
-                    gemm_phase<3, 16, (ABL & 4) != 0, 2, TR>(acc, X + l15 * LDX + lg * 4, LDX, rsrc, voff, qsoff, 16 * 16 * 1024, g_qkv,
+                    gemm_phase<3, 16, 2, false>(acc, X + l15 * LDX + lg * 4, LDX, rsrc, voff, qsoff, 16 * 16 * 1024, g_qkv,
                                                          qsoff, 16 * 16 * 1024);
                     // out-projection fragments of this chunk fly during the attention
                     ring_prefetch<2>(g_o, rsrc, voff, lbase + (int)(WO_W * 4) + ((wave * 2) * 16 + c * 8) * 1024, 16 * 1024);
@@ -403,31 +370,9 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
                         kt[r] = acc[r][1] + bk;
                         vv[r] = acc[r][2] + bv;
                     }
-                    if (TR) {
-                        // raw q (the packed W_q carries the 1/sqrt(d_head) fold: undo it exactly), k, v -> [M, 3D]
-                        float* qp = svl + (size_t)tr.qkv * 64 + grow0 * (3 * D) + head * 16;
-#pragma unroll
-                        for (int r = 0; r < RB; ++r) {
-                            const int row = r * 16 + l15;
-                            if (row < T) {
-                                __builtin_nontemporal_store(qt[r] * 4.0f, reinterpret_cast<f32x4*>(qp + (size_t)row * (3 * D) + lg * 4));
-                                __builtin_nontemporal_store(kt[r], reinterpret_cast<f32x4*>(qp + (size_t)row * (3 * D) + D + lg * 4));
-                            }
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                const int vr = r * 16 + lg * 4 + e;
-                                if (vr < T) __builtin_nontemporal_store(vv[r][e], qp + (size_t)vr * (3 * D) + 2 * D + l15);
-                            }
-                        }
-                        attention_head_regs<LDC, true>(qt, kt, vv, Qc, wave * 16, lane, 48, svl + (size_t)tr.ast * 64,
-                                                       (unsigned long long)win * H + head, T, tr.seed, (unsigned)(layer * 4 + 0),
-                                                       tr.thresh, tr.scale);
-                    } else if (!(ABL & 1)) {
-                        attention_head_regs<LDC>(qt, kt, vv, Qc, wave * 16, lane);
-                    }
+                    attention_head_regs<LDC>(qt, kt, vv, Qc, wave * 16, lane);
                 }
                 __syncthreads();
-                if (TR) rows_to_hbm(Qc, LDC, 128, svl + (size_t)tr.att * 64 + grow0 * D + c * 128, D, T, tid);
                 // the next consumer's fragments go out before this phase's MFMAs: chunk 1's QKV, or the first FFN chunk
                 if (c == 0)
                     ring_prefetch<3>(g_qkv, rsrc, voff, lbase + (int)(QKV_W * 4) + (8 + wave) * 16 * 1024, 16 * 16 * 1024);
@@ -436,7 +381,7 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
                 // out-projection partial: acc_o += O_chunk[48 x 128] * Wo[:, 128c .. 128c+127]^T
                 {
                     const int osoff = lbase + (int)(WO_W * 4) + ((wave * 2) * 16 + c * 8) * 1024;
-                    gemm_phase<2, 8, (ABL & 4) != 0, 0, TR>(acc_o, Qc + l15 * LDC + lg * 4, LDC, rsrc, voff, osoff, 16 * 1024, g_o, osoff, 16 * 1024);
+                    gemm_phase<2, 8, 0, false>(acc_o, Qc + l15 * LDC + lg * 4, LDC, rsrc, voff, osoff, 16 * 1024, g_o, osoff, 16 * 1024);
                 }
                 __syncthreads();
             }
@@ -448,19 +393,10 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
 #pragma unroll
                 for (int r = 0; r < RB; ++r)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = acc_o[r][n][e] + bv;
-                        if (TR && tr.thresh)
-                            v = tip_drop_hash_k(dk1, (grow0 + r * 16 + lg * 4 + e) * D + col) >= tr.thresh
-                                    ? v * tr.scale : 0.f;
-                        X[(r * 16 + lg * 4 + e) * LDX + col] += v;
-                    }
+                    for (int e = 0; e < 4; ++e) X[(r * 16 + lg * 4 + e) * LDX + col] += acc_o[r][n][e] + bv;
             }
             __syncthreads();
-            if (TR)
-                layernorm_rows16<fz::RP, fz::LDX, true>(X, LW + G1, LW + BE1, wave, lane, svl + (size_t)tr.z1 * 64 + grow0 * D, svl + (size_t)tr.st1 * 64 + grow0 * 2,
-                                     svl + (size_t)tr.x1 * 64 + grow0 * D, T);
-            else if (!(ABL & 2)) layernorm_rows16<fz::RP, fz::LDX>(X, LW + G1, LW + BE1, wave, lane);
+            layernorm_rows16<fz::RP, fz::LDX>(X, LW + G1, LW + BE1, wave, lane);
             __syncthreads();
             // ---- feed-forward block: hidden processed in 4 chunks of 256, second GEMM accumulates in registers -----
             float* Hc = C;
@@ -475,7 +411,7 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
                     const int w1off = lbase + (int)(W1_W * 4) + nb0 * 16 * 1024;
                     const int w2off = lbase + (int)(W2_W * 4) + ((wave * 2) * 64 + f * 16) * 1024;
                     // chained: the tail of linear1(f) primes the ring with linear2(f)'s first fragments
-                    gemm_phase<2, 16, (ABL & 4) != 0, 0, TR>(acc, X + l15 * LDX + lg * 4, LDX, rsrc, voff, w1off, 16 * 1024, g_f, w2off, 64 * 1024);
+                    gemm_phase<2, 16, 0, false>(acc, X + l15 * LDX + lg * 4, LDX, rsrc, voff, w1off, 16 * 1024, g_f, w2off, 64 * 1024);
 #pragma unroll
                     for (int n = 0; n < 2; ++n) {
                         const int col = (wave * 2 + n) * 16 + l15;
@@ -483,23 +419,15 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
 #pragma unroll
                         for (int r = 0; r < RB; ++r)
 #pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                float v = fmaxf(acc[r][n][e] + bv, 0.f);
-                                if (TR && tr.thresh)
-                                    v = tip_drop_hash_k(dk2, (grow0 + r * 16 + lg * 4 + e) * F + f * 256 + col) >= tr.thresh ? v * tr.scale : 0.f;
-                                Hc[(r * 16 + lg * 4 + e) * LDX + col] = v;
-                            }
+                            for (int e = 0; e < 4; ++e) Hc[(r * 16 + lg * 4 + e) * LDX + col] = fmaxf(acc[r][n][e] + bv, 0.f);
                     }
                 }
                 __syncthreads();
-                if (TR)
-                    hidden_to_hbm<false>(Hc, LDX, svl + (size_t)tr.hid * 64 + grow0 * F + f * 256, F,
-                                  reinterpret_cast<unsigned*>(svl + (size_t)tr.hid * 64 + (size_t)B * T * F) + grow0 * 32, f, T, opaque(tid));
                 {
                     const int w2off = lbase + (int)(W2_W * 4) + ((wave * 2) * 64 + f * 16) * 1024;
                     // ... and the tail of linear2(f) primes it with linear1(f+1)'s (its own again after the last chunk)
                     const int nxt = f < 3 ? lbase + (int)(W1_W * 4) + ((f + 1) * 16 + wave * 2) * 16 * 1024 : w2off;
-                    gemm_phase<2, 16, (ABL & 4) != 0, 0, TR>(acc_f, Hc + l15 * LDX + lg * 4, LDX, rsrc, voff, w2off, 64 * 1024, g_f, nxt,
+                    gemm_phase<2, 16, 0, false>(acc_f, Hc + l15 * LDX + lg * 4, LDX, rsrc, voff, w2off, 64 * 1024, g_f, nxt,
                                       f < 3 ? 16 * 1024 : 64 * 1024);
                 }
                 __syncthreads();
@@ -515,19 +443,10 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
 #pragma unroll
                 for (int r = 0; r < RB; ++r)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = acc_f[r][n][e] + bv;
-                        if (TR && tr.thresh)
-                            v = tip_drop_hash_k(dk3, (grow0 + r * 16 + lg * 4 + e) * D + col) >= tr.thresh
-                                    ? v * tr.scale : 0.f;
-                        X[(r * 16 + lg * 4 + e) * LDX + col] += v;
-                    }
+                    for (int e = 0; e < 4; ++e) X[(r * 16 + lg * 4 + e) * LDX + col] += acc_f[r][n][e] + bv;
             }
             __syncthreads();
-            if (TR)
-                layernorm_rows16<fz::RP, fz::LDX, true>(X, LW + G2, LW + BE2, wave, lane, svl + (size_t)tr.z2 * 64 + grow0 * D, svl + (size_t)tr.st2 * 64 + grow0 * 2,
-                                     svl + (size_t)tr.xo * 64 + grow0 * D, T);
-            else if (!(ABL & 2)) layernorm_rows16<fz::RP, fz::LDX>(X, LW + G2, LW + BE2, wave, lane);
+            layernorm_rows16<fz::RP, fz::LDX>(X, LW + G2, LW + BE2, wave, lane);
             __syncthreads();
         }
         // ---- RNN input projection (:99, first half of nn.RNN): IH = X W_ih^T + (b_ih + b_hh), rows 0..T-1 -> HBM ----
@@ -538,7 +457,7 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_kernel(
             WRing<4> g_ih;   // once per window: primed in place (one exposed L2 round trip per window)
             ring_prefetch<4>(g_ih, rsrc, voff, isoff, 16 * 1024);
 
-            gemm_phase<4, 16, (ABL & 4) != 0, 0, TR>(acc, X + l15 * LDX + lg * 4, LDX, rsrc, voff, isoff, 16 * 1024, g_ih, isoff, 16 * 1024);
+            gemm_phase<4, 16, 0, false>(acc, X + l15 * LDX + lg * 4, LDX, rsrc, voff, isoff, 16 * 1024, g_ih, isoff, 16 * 1024);
             float* io = ih_out + (size_t)win * T * R;
 #pragma unroll
             for (int n = 0; n < 4; ++n) {
@@ -574,56 +493,12 @@ hipError_t launch_fused_encoder(const Dims& d, const float* fused_w, const float
                                 const float* keep_mask, float keep_scale, float* xout, float* ih_out, float* hall_sentinel,
                                 int B, int T, int num_cus, hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    static int abl = -1;
-    if (abl < 0) {
-        const char* e = tip_env("TIP_FUSED_ABLATE");   // measurement-only (profiles/): never set in production
-        abl = e ? atoi(e) : 0;
-    }
+    if (hipError_t e = dynamic_lds<fused_encoder_kernel>(fz::LDS_BYTES)) return e;
     const int grid = B < num_cus ? B : num_cus;
     float* iho = fused_has_rnn_ih(d) ? ih_out : nullptr;
-    const int wb = (int)(fused_packed_floats(d) * 4), iob = (int)(fused_ih_off(d) * 4);
-#define TIP_FUSED_LAUNCH(A)                                                                                              \
-    {                                                                                                                    \
-        static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();                                                                                    \
-        if (!attr_set) {                                                                                                 \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_encoder_kernel<A>),                   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, fz::LDS_BYTES);               \
-            if (e != hipSuccess) return e;                                                                               \
-            attr_set = true;                                                                                             \
-        }                                                                                                                \
-        hipLaunchKernelGGL(fused_encoder_kernel<A>, dim3(grid), dim3(fz::THREADS), fz::LDS_BYTES, s, fused_w, x_imu, x_s, \
-                           keep_mask, keep_scale, xout, iho, reinterpret_cast<unsigned*>(hall_sentinel), B, T, d.n_imu_total, d.S, d.L, wb, \
-                           iob, FusedTrain{});                    \
-    }
-    switch (abl) {
-        case 0: TIP_FUSED_LAUNCH(0) break;
-        case 1: TIP_FUSED_LAUNCH(1) break;
-        case 2: TIP_FUSED_LAUNCH(2) break;
-        case 3: TIP_FUSED_LAUNCH(3) break;
-        case 4: TIP_FUSED_LAUNCH(4) break;
-        case 7: TIP_FUSED_LAUNCH(7) break;
-        default: return hipErrorInvalidValue;
-    }
-#undef TIP_FUSED_LAUNCH
-    return hipGetLastError();
-}
-
-hipError_t launch_fused_train(const Dims& d, const float* fused_w, const float* x_imu, const float* x_s, const float* keep_mask,
-                              float keep_scale, float* ih_out, float* hall_sentinel, const FusedTrain& tr, int B, int T,
-                              int num_cus, hipStream_t s) {
-    if (B <= 0) return hipSuccess;
-    if (!fused_supported(d, T) || !fused_has_rnn_ih(d)) return hipErrorInvalidValue;
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_encoder_kernel<8>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, fz::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
-    const int grid = B < num_cus ? B : num_cus;
-    hipLaunchKernelGGL(fused_encoder_kernel<8>, dim3(grid), dim3(fz::THREADS), fz::LDS_BYTES, s, fused_w, x_imu, x_s, keep_mask,
-                       keep_scale, (float*)nullptr, ih_out, reinterpret_cast<unsigned*>(hall_sentinel), B, T, d.n_imu_total, d.S, d.L,
-                       (int)(fused_packed_floats(d) * 4), (int)(fused_ih_off(d) * 4), tr);
+    hipLaunchKernelGGL(fused_encoder_kernel, dim3(grid), dim3(fz::THREADS), fz::LDS_BYTES, s, fused_w, x_imu, x_s, keep_mask, keep_scale,
+                       xout, iho, reinterpret_cast<unsigned*>(hall_sentinel), B, T, d.n_imu_total, d.S, d.L,
+                       (int)(fused_packed_floats(d) * 4), (int)(fused_ih_off(d) * 4), FusedTrain{});
     return hipGetLastError();
 }
 
@@ -1085,7 +960,7 @@ __global__ __launch_bounds__(fz::THREADS) void fused_encoder_h_kernel(
                 __syncthreads();
                 FH_STAMP(20 + 3 * f);
                 if (TR)   // (the gate bits sit behind the layer's [M][F] hidden rows: saved_layout, tip_train.hip)
-                    hidden_to_hbm<true>(Hc, LDX, svl + (size_t)tr.hid * 64 + grow0 * F + f * 256, F,
+                    hidden_to_hbm(Hc, LDX, svl + (size_t)tr.hid * 64 + grow0 * F + f * 256, F,
                                   reinterpret_cast<unsigned*>(svl + (size_t)tr.hid * 64 + (size_t)B * T * F) + grow0 * 32, f, T, opaque(tid));
                 {
                     const int w2off = lbase + (int)(W2_W * 4) + ((wave * 2) * 64 + f * 16) * 1024;
@@ -1204,19 +1079,10 @@ hipError_t launch_fused_encoder_h(const Dims& d, const float* fused_w, const flo
                                   const float* keep_mask, float keep_scale, float* xout, float* ih_out, float* hall_sentinel,
                                   int B, int T, int num_cus, hipStream_t s) {
     if (B <= 0) return hipSuccess;
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        for (const void* f : {reinterpret_cast<const void*>(fused_encoder_h_kernel<false, false>), reinterpret_cast<const void*>(fused_encoder_h_kernel<true, false>)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, fz::LDS_BYTES);
-            if (e != hipSuccess) return e;
-        }
-        attr_set = true;
-    }
-    static int trace = -1;
-    if (trace < 0) trace = tip_env("TIP_FUSEDH_TRACE") ? 1 : 0;
+    if (hipError_t e = dynamic_lds<fused_encoder_h_kernel<false, false>, fused_encoder_h_kernel<true, false>>(fz::LDS_BYTES)) return e;
     const int grid = B < num_cus ? B : num_cus;
     float* iho = fused_has_rnn_ih(d) ? ih_out : nullptr;
-    if (trace)
+    if (measure_switches().fusedh_trace)
         hipLaunchKernelGGL((fused_encoder_h_kernel<true, false>), dim3(grid), dim3(fz::THREADS), fz::LDS_BYTES, s, fused_w, x_imu, x_s, keep_mask,
                            keep_scale, xout, iho, reinterpret_cast<unsigned*>(hall_sentinel), B, T, d.n_imu_total, d.S, d.L,
                            (int)(fused_packed_floats(d) * 4), (int)(fused_ih_off(d) * 4), FusedTrain{});
@@ -1227,24 +1093,15 @@ hipError_t launch_fused_encoder_h(const Dims& d, const float* fused_w, const flo
     return hipGetLastError();
 }
 
-// training forward on the hybrid tiling (TIP_TRAIN_FWD_PADDED=1 selects fused_encoder_kernel<8>, the 48-row kernel, for A/B runs)
+// training forward on the hybrid tiling
 hipError_t launch_fused_train_h(const Dims& d, const float* fused_w, const float* x_imu, const float* x_s, const float* keep_mask,
                                 float keep_scale, float* ih_out, float* hall_sentinel, const FusedTrain& tr, int B, int T,
                                 int num_cus, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (!fused_supported(d, T) || !fused_has_rnn_ih(d)) return hipErrorInvalidValue;
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        for (const void* f : {reinterpret_cast<const void*>(fused_encoder_h_kernel<false, true>), reinterpret_cast<const void*>(fused_encoder_h_kernel<true, true>)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, fz::LDS_BYTES);
-            if (e != hipSuccess) return e;
-        }
-        attr_set = true;
-    }
+    if (hipError_t e = dynamic_lds<fused_encoder_h_kernel<false, true>, fused_encoder_h_kernel<true, true>>(fz::LDS_BYTES)) return e;
     const int grid = B < num_cus ? B : num_cus;
-    static int trace = -1;
-    if (trace < 0) trace = tip_env("TIP_FUSEDH_TRACE") ? 1 : 0;
-    if (trace) {   // measurement: the same phase stamps as the inference kernel (tools/fh_trace.py --train)
+    if (measure_switches().fusedh_trace) {   // measurement: the same phase stamps as the inference kernel (tools/fh_trace.py --train)
         hipLaunchKernelGGL((fused_encoder_h_kernel<true, true>), dim3(grid), dim3(fz::THREADS), fz::LDS_BYTES, s, fused_w, x_imu, x_s,
                            keep_mask, keep_scale, (float*)nullptr, ih_out, reinterpret_cast<unsigned*>(hall_sentinel), B, T, d.n_imu_total,
                            d.S, d.L, (int)(fused_packed_floats(d) * 4), (int)(fused_ih_off(d) * 4), tr);
@@ -1262,13 +1119,7 @@ hipError_t launch_fused_live_h(const Dims& d, const float* fused_w, const float*
                                const LiveArgs& lv, int B, int T, int num_cus, hipStream_t s) {
     if (B <= 0) return hipSuccess;
     if (!fused_supported(d, T) || !fused_has_rnn_ih(d)) return hipErrorInvalidValue;
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_encoder_h_kernel<false, false, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, fz::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = dynamic_lds<fused_encoder_h_kernel<false, false, true>>(fz::LDS_BYTES)) return e;
     const int grid = B < num_cus ? B : num_cus;
     LiveTrain lt;
     static_cast<FusedTrain&>(lt) = tr;
@@ -1565,18 +1416,10 @@ hipError_t launch_ffn_bwd(const Dims& d, const FfnBwdArgs& a, int B, int T, int 
     if (!fused_supported(d, T) || (long long)B * T * d.F * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
     constexpr int lds = (3 * fz::RP * fz::LDX + fz::RP * kGateLd) * 4;
     static_assert(lds <= 160 * 1024, "LDS of one CU");
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ffn_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(ffn_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = dynamic_lds<ffn_bwd_kernel<false>, ffn_bwd_kernel<true>>(lds)) return e;
     FfnBwdArgs aa = a;
     aa.hid_bytes = (int)((long long)B * T * d.F * 4);
-    static int trace = -1;
-    if (trace < 0) trace = tip_env("TIP_BWD_TRACE") ? 1 : 0;
-    aa.trace = trace;
+    aa.trace = measure_switches().bwd_trace ? 1 : 0;
     if (aa.gbits) hipLaunchKernelGGL(ffn_bwd_kernel<true>, dim3(B < num_cus ? B : num_cus), dim3(fz::THREADS), lds, s, aa, B, T);
     else hipLaunchKernelGGL(ffn_bwd_kernel<false>, dim3(B < num_cus ? B : num_cus), dim3(fz::THREADS), lds, s, aa, B, T);
     return hipGetLastError();
@@ -1930,18 +1773,10 @@ hipError_t launch_attn_bwd(const Dims& d, const AttnBwdArgs& a, int B, int T, in
     constexpr int lds = (fz::RP * fz::LDX + 8 * 3 * fz::RP * 20) * 4;   // datt_o + per-wave Q / K / dO transposition tiles
     static_assert(8 * 3 * fz::RP * 20 >= 8 * 3 * fz::D, "the LayerNorm partial scratch lives in the per-wave scratch region");
     if ((long long)B * T * 3 * d.D * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = dynamic_lds<attn_bwd_kernel<false>, attn_bwd_kernel<true>>(lds)) return e;
     AttnBwdArgs aa = a;
     aa.dqkv_bytes = (int)((long long)B * T * 3 * d.D * 4);
-    static int trace = -1;
-    if (trace < 0) trace = tip_env("TIP_BWD_TRACE") ? 1 : 0;
-    aa.trace = trace;
+    aa.trace = measure_switches().bwd_trace ? 1 : 0;
     if (aa.thresh) hipLaunchKernelGGL(attn_bwd_kernel<true>, dim3(B < num_cus ? B : num_cus), dim3(fz::THREADS), lds, s, aa, B, T);
     else hipLaunchKernelGGL(attn_bwd_kernel<false>, dim3(B < num_cus ? B : num_cus), dim3(fz::THREADS), lds, s, aa, B, T);
     return hipGetLastError();
@@ -2012,12 +1847,7 @@ __global__ __launch_bounds__(fz::THREADS) void win_gemm_kernel(WinGemmArgs a, in
 template <int NBW, int KB>
 static hipError_t launch_win_gemm_t(const WinGemmArgs& a, int B, int T, int num_cus, hipStream_t s) {
     constexpr int lds = fz::RP * (KB * 16 + 8) * 4;
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(win_gemm_kernel<NBW, KB>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = dynamic_lds<win_gemm_kernel<NBW, KB>>(lds)) return e;
     hipLaunchKernelGGL((win_gemm_kernel<NBW, KB>), dim3(B < num_cus ? B : num_cus), dim3(fz::THREADS), lds, s, a, B, T);
     return hipGetLastError();
 }

@@ -1163,17 +1163,8 @@ hipError_t launch_fused_encoder2(const Dims& d, const float* fused_w, const floa
                                  const float* keep_mask, float keep_scale, float* ih_out, float* hall_sentinel, int B,
                                  int num_cus, hipStream_t s, const float* reuse_cache, const int* frame_ctr, int frame_idx) {
     if (B <= 0) return hipSuccess;
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        for (const void* f : {reinterpret_cast<const void*>(fused_encoder2_kernel<false>), reinterpret_cast<const void*>(fused_encoder2_kernel<true>),
-                              reinterpret_cast<const void*>(fused_encoder2_kernel<false, true>)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, f2::LDS_BYTES);
-            if (e != hipSuccess) return e;
-        }
-        attr_set = true;
-    }
-    static int trace = -1;
-    if (trace < 0) trace = tip_env("TIP_FUSED2_TRACE") ? 1 : 0;
+    if (hipError_t e = dynamic_lds<fused_encoder2_kernel<false>, fused_encoder2_kernel<true>, fused_encoder2_kernel<false, true>>(f2::LDS_BYTES))
+        return e;
     const int npairs = (B + 1) / 2;
     const int grid = npairs < num_cus ? npairs : num_cus;
     const size_t ih_off = f2::LAYER0 + (size_t)d.L * f2::LAYER_FLOATS;
@@ -1183,7 +1174,7 @@ hipError_t launch_fused_encoder2(const Dims& d, const float* fused_w, const floa
         hipLaunchKernelGGL((fused_encoder2_kernel<false, true>), dim3(grid), dim3(f2::THREADS), f2::LDS_BYTES, s, fused_w, x_imu, x_s, keep_mask,
                            keep_scale, ih_out, reinterpret_cast<unsigned*>(hall_sentinel), B, d.n_imu_total, d.S, d.L,
                            (int)(fused_packed_floats(d) * 4), (int)(ih_off * 4), rua);
-    else if (trace)
+    else if (measure_switches().fused2_trace)
         hipLaunchKernelGGL(fused_encoder2_kernel<true>, dim3(grid), dim3(f2::THREADS), f2::LDS_BYTES, s, fused_w, x_imu, x_s, keep_mask,
                            keep_scale, ih_out, reinterpret_cast<unsigned*>(hall_sentinel), B, d.n_imu_total, d.S, d.L,
                            (int)(fused_packed_floats(d) * 4), (int)(ih_off * 4), rua);
@@ -1207,13 +1198,7 @@ static hipError_t launch_fused_encoder_split(const Dims& d, const float* fused_w
     if (B <= 0) return hipSuccess;
     static_assert(NWIN == 1, "the window-pair form was retired (round 6)");
     if (!(NPART == 4 ? fused1s_quad_fits(B, num_cus) : fused1s_fits(B, num_cus))) return hipErrorInvalidValue;   // every workgroup must be resident: partners wait for each other
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(fused_encoder2s_kernel<NWIN, NPART>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, f2::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        attr_set = true;
-    }
+    if (hipError_t e = dynamic_lds<fused_encoder2s_kernel<NWIN, NPART>>(f2::LDS_BYTES)) return e;
     constexpr int RBK = NWIN == 2 ? 5 : 3;
     constexpr size_t PAIR_IMG = (size_t)2 * NPART * RBK * 16 * f2::D;
     const int npairs = (B + NWIN - 1) / NWIN;
@@ -1291,15 +1276,7 @@ hipError_t launch_pgemm(const float* A, int lda, const float* wfrag, size_t wfra
     if (M <= 0) return hipSuccess;
     if (!pgemm_ok(M, N, K) || wfrag_floats * 4 > 0x7fffffffULL) return hipErrorInvalidValue;
     ++g_pgemm_launches;
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        for (const void* f : {reinterpret_cast<const void*>(pgemm_kernel<0>), reinterpret_cast<const void*>(pgemm_kernel<1>),
-                              reinterpret_cast<const void*>(pgemm_kernel<2>), reinterpret_cast<const void*>(pgemm_kernel<3>)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, pg::LDS_BYTES);
-            if (e != hipSuccess) return e;
-        }
-        attr_set = true;
-    }
+    if (hipError_t e = dynamic_lds<pgemm_kernel<0>, pgemm_kernel<1>, pgemm_kernel<2>, pgemm_kernel<3>>(pg::LDS_BYTES)) return e;
     const dim3 grid(N / pg::COLS, (M + pg::ROWS - 1) / pg::ROWS), block(pg::THREADS);
     const int wb = (int)(wfrag_floats * 4);
     switch (flags & 3) {

@@ -25,7 +25,6 @@
 namespace tip {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // every bounded hand-off spin that gives up bumps this counter (read with tip_spin_timeouts()): a non-zero value
@@ -71,127 +70,13 @@ hipError_t launch_prologue(const Dims& d, const float* x_imu, const float* x_s, 
     return hipGetLastError();
 }
 
-// ------------------------------------------------------------------------------------------------
-// GEMM: C[M,N] = epi(A[M,K] * W[Npad,K]^T + bias (+res)).  128x128x16 block tile, 4 waves as 2x2, each wave
-// 64x64 = 2x2 tiles of v_mfma_f32_32x32x2_f32.  A and W tiles are staged through LDS k-major
-// ([k][row], row stride 130 floats) so both the transposing ds_write_b32 and the fragment ds_read_b32 are
-// bank-conflict free; global->register prefetch of tile k+1 overlaps the MFMAs of tile k.
-// ------------------------------------------------------------------------------------------------
-constexpr int LDT = kGemmBM + 2;
-
-template <int FLAGS>
-__global__ __launch_bounds__(256) void gemm_kernel(const float* __restrict__ A, int lda, const float* __restrict__ W,
-                                                   int K, const float* __restrict__ bias,
-                                                   const float* __restrict__ res, int ldres, float* __restrict__ C,
-                                                   int ldc, int M, int N) {
-    __shared__ float As[2][kGemmBK][LDT];
-    __shared__ float Bs[2][kGemmBK][LDT];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const int bm = blockIdx.y, bn = blockIdx.x;
-    const int lr = tid >> 2;         // 0..63
-    const int lk = (tid & 3) * 4;    // 0,4,8,12
-
-    const int arow0 = bm * kGemmBM + lr, arow1 = arow0 + 64;
-    const bool av0 = arow0 < M, av1 = arow1 < M;
-    const float* ap0 = A + (size_t)(av0 ? arow0 : 0) * lda + lk;
-    const float* ap1 = A + (size_t)(av1 ? arow1 : 0) * lda + lk;
-    const float* wp0 = W + (size_t)(bn * kGemmBN + lr) * K + lk;   // packed W is padded: always in range
-    const float* wp1 = wp0 + (size_t)64 * K;
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 ra0, ra1, rb0, rb1;
-    ra0 = av0 ? *reinterpret_cast<const float4*>(ap0) : zero4;
-    ra1 = av1 ? *reinterpret_cast<const float4*>(ap1) : zero4;
-    rb0 = *reinterpret_cast<const float4*>(wp0);
-    rb1 = *reinterpret_cast<const float4*>(wp1);
-
-    auto stage = [&](int buf) {
-        As[buf][lk + 0][lr] = ra0.x; As[buf][lk + 1][lr] = ra0.y; As[buf][lk + 2][lr] = ra0.z; As[buf][lk + 3][lr] = ra0.w;
-        As[buf][lk + 0][lr + 64] = ra1.x; As[buf][lk + 1][lr + 64] = ra1.y; As[buf][lk + 2][lr + 64] = ra1.z; As[buf][lk + 3][lr + 64] = ra1.w;
-        Bs[buf][lk + 0][lr] = rb0.x; Bs[buf][lk + 1][lr] = rb0.y; Bs[buf][lk + 2][lr] = rb0.z; Bs[buf][lk + 3][lr] = rb0.w;
-        Bs[buf][lk + 0][lr + 64] = rb1.x; Bs[buf][lk + 1][lr + 64] = rb1.y; Bs[buf][lk + 2][lr + 64] = rb1.z; Bs[buf][lk + 3][lr + 64] = rb1.w;
-    };
-    stage(0);
-    __syncthreads();
-
-    const int nk = K / kGemmBK;
-    const int l31 = lane & 31, lhi = lane >> 5;
-    for (int kt = 0; kt < nk; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < nk) {
-            const int ko = (kt + 1) * kGemmBK;
-            ra0 = av0 ? *reinterpret_cast<const float4*>(ap0 + ko) : zero4;
-            ra1 = av1 ? *reinterpret_cast<const float4*>(ap1 + ko) : zero4;
-            rb0 = *reinterpret_cast<const float4*>(wp0 + ko);
-            rb1 = *reinterpret_cast<const float4*>(wp1 + ko);
-        }
-#pragma unroll
-        for (int kk = 0; kk < kGemmBK / 2; ++kk) {
-            const int k = kk * 2 + lhi;
-            float a[2], b[2];
-            a[0] = As[cur][k][wm * 64 + l31];
-            a[1] = As[cur][k][wm * 64 + 32 + l31];
-            b[0] = Bs[cur][k][wn * 64 + l31];
-            b[1] = Bs[cur][k][wn * 64 + 32 + l31];
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-        if (kt + 1 < nk) stage(cur ^ 1);
-        __syncthreads();
-    }
-
-    // epilogue.  C/D layout of 32x32: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5).
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = bn * kGemmBN + wn * 64 + j * 32 + l31;
-            if (col >= N) continue;
-            const float bv = bias[col];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = bm * kGemmBM + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhi;
-                if (row < M) {
-                    float v = acc[i][j][r] + bv;
-                    if (FLAGS & 2) v += res[(size_t)row * ldres + col];
-                    if (FLAGS & 1) v = v > 0.f ? v : 0.f;
-                    C[(size_t)row * ldc + col] = v;
-                }
-            }
-        }
-    }
-}
-
+// GEMM of the general plan: C[M,N] = epi(A[M,K] * W[Npad,K]^T + bias (+res)) on the 16x16x4 / 64x64-tile kernel of tip_train.hip
+// (measured against a 128x128 tile of 32x32x2 MFMAs: paper B=256 general plan 1.27 vs 1.59 ms, scaled B=128 32.3 vs 35.5 ms).
 hipError_t launch_gemm(const float* A, int lda, const float* W, int Kpad, const float* bias, const float* res,
                        int ldres, float* C, int ldc, int M, int N, int Npad, int flags, hipStream_t s) {
+    (void)Npad;
     if (M <= 0) return hipSuccess;
-    // default: the 16x16x4 / 64x64-tile kernel of tip_train.hip (measured: paper B=256 general plan 1.27 vs 1.59 ms, scaled
-    // B=128 32.3 vs 35.5 ms, scaled B=512 equal); TIP_GENERAL_GEMM=32 selects the 128x128 32x32x2 kernel below
-    static int use16 = -1;
-    if (use16 < 0) use16 = (tip_env("TIP_GENERAL_GEMM") && atoi(tip_env("TIP_GENERAL_GEMM")) == 32) ? 0 : 1;
-    if (use16) return launch_gemm16(A, lda, W, Kpad, bias, res, ldres, C, ldc, M, N, Kpad, flags, s);
-    dim3 grid(Npad / kGemmBN, (M + kGemmBM - 1) / kGemmBM);
-    dim3 block(256);
-    switch (flags & 3) {
-        case 0: hipLaunchKernelGGL(gemm_kernel<0>, grid, block, 0, s, A, lda, W, Kpad, bias, res, ldres, C, ldc, M, N); break;
-        case 1: hipLaunchKernelGGL(gemm_kernel<1>, grid, block, 0, s, A, lda, W, Kpad, bias, res, ldres, C, ldc, M, N); break;
-        case 2: hipLaunchKernelGGL(gemm_kernel<2>, grid, block, 0, s, A, lda, W, Kpad, bias, res, ldres, C, ldc, M, N); break;
-        default: hipLaunchKernelGGL(gemm_kernel<3>, grid, block, 0, s, A, lda, W, Kpad, bias, res, ldres, C, ldc, M, N); break;
-    }
-    return hipGetLastError();
+    return launch_gemm16(A, lda, W, Kpad, bias, res, ldres, C, ldc, M, N, Kpad, flags, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -428,13 +313,12 @@ __global__ __launch_bounds__(256) void attention_kernel(const float* __restrict_
 }
 
 hipError_t launch_attention(const Dims& d, const float* qkv, float* out, int B, int T, hipStream_t s) {
-    static int valu = -1;   // TIP_GENERAL_ATTN=valu keeps the one-thread-per-query kernel below (measurement / fallback)
-    if (valu < 0) valu = (tip_env("TIP_GENERAL_ATTN") && tip_env("TIP_GENERAL_ATTN")[0] == 'v') ? 1 : 0;
-    if (!valu && mattn_supported(d.dh, T)) {
+    if (mattn_supported(d.dh, T)) {
         Drop off;
         off.seed = 0; off.site = 0; off.thresh = 0; off.scale = 1.f;
         return launch_mattn_fwd(qkv, out, nullptr, B, T, d.H, d.dh, d.q_scale, off, s);
     }
+    // shapes the matrix-core kernel does not serve: one thread per query
     // key tile per wave: the whole window when it fits 16 KB per wave (4 waves = 64 KB, no opt-in needed), else 16 KB worth of keys
     const int waves = 4;
     int TK = (16 * 1024) / (2 * d.dh * (int)sizeof(float));
@@ -695,7 +579,8 @@ __global__ __launch_bounds__(256) void rnn_kernel(const float* __restrict__ ih, 
 // HALL -> per-(tile,step) arrival counter -> the other members poll it and pull the tile back with sc1 loads
 // (agent-scope coherent across the 8 XCD L2s; no fences on the critical path).
 // ------------------------------------------------------------------------------------------------
-// HANDOFF = 0: arrival counter (stores -> drain -> barrier -> counter; consumers poll the counter, then pull).
+// HANDOFF = 0: arrival counter (stores -> drain -> barrier -> counter; consumers poll the counter, then pull).  No launcher
+//              instantiates it; the parameter is part of every instantiation's symbol name.
 // HANDOFF = 1: the data is the flag — HALL is pre-filled with an all-ones sentinel (a NaN bit pattern no arithmetic
 //              produces), producers just store, consumers re-pull until no sentinel word is left: two memory round
 //              trips (drain + counter) leave the per-step critical path.
@@ -747,7 +632,7 @@ __global__ __launch_bounds__(WAVES * 64) void rnn_resident_kernel(const float* _
     if (HANDOFF == 0 && tid == 0) s_poison0 = 0;
     const unsigned spin_big = guard_spin_limit(gd.fault, 1u << 22), spin_pull = guard_spin_limit(gd.fault, 1u << 20);
     // Every member pulls the same 32-KB tile at the same moment: started at the same row they would queue behind each other at
-    // every L2 line.  Member cid starts its sweep at row cid (TIP_RNN_ROTATE=0 switches it off for measurement).
+    // every L2 line.  Member cid starts its sweep at row cid (bit 1 of `prepoll`: the launcher always sets it).
     const int rot = prepoll & 2 ? cid : 0;
 
     // Same-XCD fast path, VERIFIED at run time (placement is never assumed): every member publishes the XCC id it
@@ -1381,17 +1266,8 @@ unsigned next_rnn_launch_tag() {
     return launch_tag.fetch_add(1u) & 0x7FFFFFu;   // 23 bits: fits the int kernel argument above the option bits
 }
 
-static int rnn_handoff_mode() {
-    static int handoff = -1;
-    if (handoff < 0) {
-        const char* e = tip_env("TIP_RNN_HANDOFF");   // 0 = arrival counter, 1 = sentinel polling (default)
-        handoff = e ? atoi(e) : 1;
-    }
-    return handoff;
-}
-
 bool rnn_uses_sentinel(const Dims& d, int B, int T, int cluster) {
-    return d.R == 512 && (long long)B * T * 512 * 4 <= 0x7fffffffLL && cluster >= 4 && rnn_handoff_mode() == 1;
+    return d.R == 512 && (long long)B * T * 512 * 4 <= 0x7fffffffLL && cluster >= 4;
 }
 
 template <int WAVES, int KSPLIT>
@@ -1402,7 +1278,6 @@ static hipError_t launch_rnn_resident(const float* ih, const float* whh_frag, fl
     int groups = ntiles;
     const int maxg = num_cus * wg_per_cu / CLUSTER > 0 ? num_cus * wg_per_cu / CLUSTER : 1;   // keep every cluster co-resident
     if (groups > maxg) groups = maxg;
-    const int handoff = rnn_handoff_mode();
     const size_t smem = ((size_t)kRnnTile * (512 + 4) + (size_t)(KSPLIT - 1) * (WAVES / KSPLIT) * 256) * sizeof(float);
     {
         // every member of a cluster must be resident while its partners wait for it: ask the runtime, do not assume
@@ -1412,40 +1287,23 @@ static hipError_t launch_rnn_resident(const float* ih, const float* whh_frag, fl
     }
     const long long hb = (long long)B * T * 512 * 4;
     if (hb > 0x7fffffffLL) return hipErrorInvalidValue;
-    if (handoff == 0) {
-        const int prepoll = 0;
-        hipError_t e = hipMemsetAsync(flags, 0, (size_t)ntiles * T * sizeof(unsigned), s);
+    if (!hall_armed) {
+        hipError_t e = hipMemsetAsync(hall, 0xFF, (size_t)hb, s);   // every word = kRnnSentinel
         if (e != hipSuccess) return e;
-        if (gate)
-            hipLaunchKernelGGL((rnn_resident_kernel<WAVES, KSPLIT, 0, false, true>), dim3(groups * CLUSTER), dim3(WAVES * 64), smem,
-                               s, ih, whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, prepoll);
-        else
-            hipLaunchKernelGGL((rnn_resident_kernel<WAVES, KSPLIT, 0>), dim3(groups * CLUSTER), dim3(WAVES * 64), smem, s, ih,
-                               whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, prepoll);
-    } else {
-        if (!hall_armed) {
-            hipError_t e = hipMemsetAsync(hall, 0xFF, (size_t)hb, s);   // every word = kRnnSentinel
-            if (e != hipSuccess) return e;
-        }
-        // XCC-id exchange words: tagged with a per-launch number instead of being zeroed (see the kernel)
-        const unsigned etag = next_rnn_launch_tag();
-        static int trace = -1;
-        if (trace < 0) trace = tip_env("TIP_RNN_TRACE") ? 1 : 0;
-        static int prepoll_env = -1;   // TIP_RNN_PREPOLL=0: no arrival probe before the tile pull (measurement)
-        if (prepoll_env < 0) prepoll_env = (tip_env("TIP_RNN_PREPOLL") && tip_env("TIP_RNN_PREPOLL")[0] == '0') ? 0 : 1;
-        static int rot_env = -1;       // TIP_RNN_ROTATE=0: every member sweeps the tile from row 0 (measurement)
-        if (rot_env < 0) rot_env = (tip_env("TIP_RNN_ROTATE") && tip_env("TIP_RNN_ROTATE")[0] == '0') ? 0 : 2;
-        const int prepoll = prepoll_env | rot_env | (int)(etag << 8);
-        if (gate)
-            hipLaunchKernelGGL((rnn_resident_kernel<WAVES, KSPLIT, 1, false, true>), dim3(groups * CLUSTER), dim3(WAVES * 64), smem,
-                               s, ih, whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, prepoll);
-        else if (trace)
-            hipLaunchKernelGGL((rnn_resident_kernel<WAVES, KSPLIT, 1, true>), dim3(groups * CLUSTER), dim3(WAVES * 64), smem, s,
-                               ih, whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, prepoll);
-        else
-            hipLaunchKernelGGL((rnn_resident_kernel<WAVES, KSPLIT, 1>), dim3(groups * CLUSTER), dim3(WAVES * 64), smem, s, ih,
-                               whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, prepoll);
     }
+    // XCC-id exchange words: tagged with a per-launch number instead of being zeroed (see the kernel)
+    const unsigned etag = next_rnn_launch_tag();
+    // bit 0: arrival probe before the tile pull; bit 1: member cid starts its sweep of the tile at row cid; bits 8..: the launch tag
+    const int prepoll = 1 | 2 | (int)(etag << 8);
+    if (gate)
+        hipLaunchKernelGGL((rnn_resident_kernel<WAVES, KSPLIT, 1, false, true>), dim3(groups * CLUSTER), dim3(WAVES * 64), smem,
+                           s, ih, whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, prepoll);
+    else if (measure_switches().rnn_trace)
+        hipLaunchKernelGGL((rnn_resident_kernel<WAVES, KSPLIT, 1, true>), dim3(groups * CLUSTER), dim3(WAVES * 64), smem, s,
+                           ih, whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, prepoll);
+    else
+        hipLaunchKernelGGL((rnn_resident_kernel<WAVES, KSPLIT, 1>), dim3(groups * CLUSTER), dim3(WAVES * 64), smem, s, ih,
+                           whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, prepoll);
     return hipGetLastError();
 }
 
@@ -1456,18 +1314,10 @@ static hipError_t launch_rnn_rows4_nt(const float* ih, const float* whh_frag, fl
                                       int groups, long long hb, const Guard& gd, hipStream_t s, const float* gate, unsigned etag, int num_cus) {
     constexpr int smem = 2 * NT * kQ4Rows * kQ4LD * (int)sizeof(float);
     constexpr int CLUSTER = 32 / WAVES, THREADS = WAVES * 64;
-    static int trace = -1, abl = -1;
-    if (trace < 0) trace = tip_env("TIP_RNN_TRACE") ? 1 : 0;
-    if (abl < 0) abl = tip_env("TIP_RNN_ABLATE") ? atoi(tip_env("TIP_RNN_ABLATE")) : 0;   // measurement only (profiles/): never set in production
-    static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-    if (!attr_set) {
-        for (const void* f : {reinterpret_cast<const void*>(rnn_rows4_kernel<NT, false, false, WAVES>), reinterpret_cast<const void*>(rnn_rows4_kernel<NT, true, false, WAVES>),
-                              reinterpret_cast<const void*>(rnn_rows4_kernel<NT, false, true, WAVES>)}) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-            if (e != hipSuccess) return e;
-        }
-        attr_set = true;
-    }
+    const int abl = measure_switches().rnn_ablate;   // measurement only (profiles/): 0 in production
+    if (hipError_t e = dynamic_lds<rnn_rows4_kernel<NT, false, false, WAVES>, rnn_rows4_kernel<NT, true, false, WAVES>,
+                                   rnn_rows4_kernel<NT, false, true, WAVES>>(smem))
+        return e;
     static PerDeviceInt occ_dev; int& occ = occ_dev.cur();   // every member of a cluster must be resident while its partners wait for it: ask the runtime
     hipError_t ce = check_coresident(rnn_rows4_kernel<NT, false, false, WAVES>, THREADS, smem, groups * CLUSTER, num_cus, &occ);
     if (ce != hipSuccess) return ce;
@@ -1476,7 +1326,7 @@ static hipError_t launch_rnn_rows4_nt(const float* ih, const float* whh_frag, fl
     const dim3 grid((groups + 7) / 8 * 8 * CLUSTER), block(THREADS);
     if (gate)
         hipLaunchKernelGGL((rnn_rows4_kernel<NT, false, true, WAVES>), grid, block, smem, s, ih, whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, etag, abl, groups);
-    else if (trace)
+    else if (measure_switches().rnn_trace)
         hipLaunchKernelGGL((rnn_rows4_kernel<NT, true, false, WAVES>), grid, block, smem, s, ih, whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, etag, abl, groups);
     else
         hipLaunchKernelGGL((rnn_rows4_kernel<NT, false, false, WAVES>), grid, block, smem, s, ih, whh_frag, hall, flags, B, T, ntiles, (int)hb, gate, gd, etag, abl, groups);
@@ -1490,9 +1340,8 @@ static hipError_t launch_rnn_rows4(const float* ih, const float* whh_frag, float
     // gets a CU of its own with half the matrix work per step: 62 vs 76 us at B = 100.  With two members per CU (B = 256) the hoped-for
     // overlap of one's hand-off with the other's MFMAs does not happen: 84 vs 78 us (profiles/r04/rnn_w4.txt), so the 8-wave members
     // stay there.  Bit-identical either way.  TIP_RNN_W4=0 / 1 forces one (measurement).
-    static int w4 = -2;
-    if (w4 == -2) w4 = tip_env("TIP_RNN_W4") ? (tip_env("TIP_RNN_W4")[0] == '1' ? 1 : 0) : -1;
-    const bool use_w4 = (w4 == 1 || (w4 == -1 && ntiles * 8 <= num_cus));
+    const int w4 = measure_switches().rnn_w4;
+    const bool use_w4 = w4 < 0 ? ntiles * 8 <= num_cus : w4 == 1;
     int groups = ntiles;
     const int maxg = num_cus / kQ4Cluster > 0 ? num_cus / kQ4Cluster : 1;   // keep every cluster co-resident (W4: 8 members, two per CU: the same count)
     if (groups > maxg) groups = maxg;
@@ -1559,10 +1408,7 @@ hipError_t launch_rnn_bwd(const Dims& d, const float* dH, const float* whh_t_fra
         return launch_rnn_stream<true>(dH, whh_t_frag, delta, flags, B, T, d.R, cluster == kRnnRows4 ? 1 : cluster, num_cus, gd, h_fwd, s);
     if ((long long)B * T * 512 * 4 > 0x7fffffffLL) return hipErrorInvalidValue;
     const int ntiles = (B + kRnnTile - 1) / kRnnTile;
-    if (cluster == kRnnRows4) {
-        if (rnn_handoff_mode() == 1) return launch_rnn_rows4(dH, whh_t_frag, delta, flags, B, T, num_cus, false, gd, s, h_fwd);
-        cluster = 16;
-    }
+    if (cluster == kRnnRows4) return launch_rnn_rows4(dH, whh_t_frag, delta, flags, B, T, num_cus, false, gd, s, h_fwd);
     if (cluster >= 16) return launch_rnn_resident<8, 4>(dH, whh_t_frag, delta, flags, B, T, ntiles, num_cus, false, gd, s, h_fwd);
     if (cluster == 8) return launch_rnn_resident<4, 1>(dH, whh_t_frag, delta, flags, B, T, ntiles, num_cus, false, gd, s, h_fwd);
     return launch_rnn_resident<8, 1>(dH, whh_t_frag, delta, flags, B, T, ntiles, num_cus, false, gd, s, h_fwd);
@@ -1575,19 +1421,11 @@ hipError_t launch_rnn(const Dims& d, const float* ih, const float* whh_frag, flo
     const int ntiles = (B + kRnnTile - 1) / kRnnTile;
     if (cluster < 1) cluster = 1;
     if (R == 512 && (long long)B * T * 512 * 4 <= 0x7fffffffLL) {
-        if (cluster == kRnnRows4) {
-            if (rnn_handoff_mode() == 1) return launch_rnn_rows4(ih, whh_frag, hall, flags, B, T, num_cus, hall_armed, gd, s, nullptr);
-            cluster = 16;   // (TIP_RNN_HANDOFF=0, measurement: the counter protocol exists for the 16-row kernels only)
-        }
+        if (cluster == kRnnRows4) return launch_rnn_rows4(ih, whh_frag, hall, flags, B, T, num_cus, hall_armed, gd, s, nullptr);
         // register-resident clustered kernel: W_hh slice lives in VGPRs, 4/8/16 workgroups per window tile
         if (cluster >= 32)   // two 4-wave workgroups per CU, each one column block of a tile: one computes while the other waits
             return launch_rnn_resident<4, 4>(ih, whh_frag, hall, flags, B, T, ntiles, num_cus, hall_armed, gd, s, nullptr, 2);
-        if (cluster >= 16) {
-            static int w8 = -1;   // TIP_RNN_C16=4 selects the 4-wave variant (measurement)
-            if (w8 < 0) w8 = (tip_env("TIP_RNN_C16") && tip_env("TIP_RNN_C16")[0] == '4') ? 0 : 1;
-            return w8 ? launch_rnn_resident<8, 4>(ih, whh_frag, hall, flags, B, T, ntiles, num_cus, hall_armed, gd, s)
-                      : launch_rnn_resident<4, 2>(ih, whh_frag, hall, flags, B, T, ntiles, num_cus, hall_armed, gd, s);
-        }
+        if (cluster >= 16) return launch_rnn_resident<8, 4>(ih, whh_frag, hall, flags, B, T, ntiles, num_cus, hall_armed, gd, s);
         if (cluster == 8) return launch_rnn_resident<4, 1>(ih, whh_frag, hall, flags, B, T, ntiles, num_cus, hall_armed, gd, s);
         if (cluster == 4) return launch_rnn_resident<8, 1>(ih, whh_frag, hall, flags, B, T, ntiles, num_cus, hall_armed, gd, s);
     }

@@ -77,17 +77,8 @@ hipError_t launch_head_ksplit(const float* A, long long lda, const float* wfrag,
         if (rows_T < 1 || rows_T % 40 || lda * 4 > 0x7fffffffLL || ((long long)M * rows_T - 1) * lda + K > 0x1fffffffLL ||
             (long long)M * ldy * 4 > 0x7fffffffLL)
             return hipErrorInvalidValue;
-        static PerDeviceFlag rows_flag[2];
         const unsigned a_bytes = (unsigned)((((long long)M * rows_T - 1) * lda + K) * 4);
-        const void* fns[2] = {reinterpret_cast<const void*>(head_rows_kernel<1>), reinterpret_cast<const void*>(head_rows_kernel<2>)};
-        for (int i = 0; i < 2; ++i) {
-            bool& done = rows_flag[i].cur();
-            if (!done) {
-                const hipError_t e2 = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, hd::LDS_BYTES);
-                if (e2 != hipSuccess) return e2;
-                done = true;
-            }
-        }
+        if (hipError_t e = dynamic_lds<head_rows_kernel<1>, head_rows_kernel<2>>(hd::LDS_BYTES)) return e;
         const HdGather g1{rows, rows_T, M, 0, (unsigned)(lda * 4)}, g2{rows, rows_T, M, 1, (unsigned)(lda * 4)};
         const int ng1 = (M + 15) / 16, ng2 = (M + 3) / 4;
         hipLaunchKernelGGL(head_rows_kernel<1>, dim3(std::min(ng1, num_cus)), dim3(hd::THREADS), hd::LDS_BYTES, s, A, a_bytes, wfrag,
@@ -101,19 +92,8 @@ hipError_t launch_head_ksplit(const float* A, long long lda, const float* wfrag,
     if (lda * 4 > 0x7fffffffLL || ((long long)(M - 1) * lda + K) * 4 > 0xffffffffLL || (long long)M * ldy * 4 > 0x7fffffffLL)
         return hipErrorInvalidValue;
     const unsigned a_bytes = (unsigned)(((long long)(M - 1) * lda + K) * 4);
-    hipError_t e = hipSuccess;
-    static PerDeviceFlag attr_flag[2];
-    auto prep = [&](const void* fn, int slot) -> hipError_t {
-        bool& done = attr_flag[slot].cur();
-        if (done) return hipSuccess;
-        hipError_t e2 = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, hd::LDS_BYTES);
-        if (e2 == hipSuccess) done = true;
-        return e2;
-    };
-    static const bool trace = tip_env("TIP_HEAD_TRACE") && tip_env("TIP_HEAD_TRACE")[0] == '1';
-    if (trace && !last_only && M % 40 == 0) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(head_ksplit_kernel<0, true>), hipFuncAttributeMaxDynamicSharedMemorySize, hd::LDS_BYTES);
-        if (e != hipSuccess) return e;
+    if (measure_switches().head_trace && !last_only && M % 40 == 0) {
+        if (hipError_t e = dynamic_lds<head_ksplit_kernel<0, true>>(hd::LDS_BYTES)) return e;
         hipLaunchKernelGGL((head_ksplit_kernel<0, true>), dim3(std::min(M / 40, num_cus)), dim3(hd::THREADS), hd::LDS_BYTES, s, A,
                            (unsigned)(lda * 4), a_bytes, wfrag, bias, Y, ldy, M, N, M / 40);
         return hipGetLastError();
@@ -121,14 +101,12 @@ hipError_t launch_head_ksplit(const float* A, long long lda, const float* wfrag,
     if (!last_only) {
         if (M % 40) return hipErrorInvalidValue;
         const int ngroups = M / 40;
-        e = prep(reinterpret_cast<const void*>(head_ksplit_kernel<0>), 0);
-        if (e != hipSuccess) return e;
+        if (hipError_t e = dynamic_lds<head_ksplit_kernel<0>>(hd::LDS_BYTES)) return e;
         hipLaunchKernelGGL(head_ksplit_kernel<0>, dim3(std::min(ngroups, num_cus)), dim3(hd::THREADS), hd::LDS_BYTES, s, A,
                            (unsigned)(lda * 4), a_bytes, wfrag, bias, Y, ldy, M, N, ngroups);
     } else {
         const int ngroups = (M + 3) / 4;
-        e = prep(reinterpret_cast<const void*>(head_ksplit_kernel<2>), 1);
-        if (e != hipSuccess) return e;
+        if (hipError_t e = dynamic_lds<head_ksplit_kernel<2>>(hd::LDS_BYTES)) return e;
         hipLaunchKernelGGL(head_ksplit_kernel<2>, dim3(std::min(ngroups, num_cus)), dim3(hd::THREADS), hd::LDS_BYTES, s, A,
                            (unsigned)(lda * 4), a_bytes, wfrag, bias, Y, ldy, M, N, ngroups);
     }

@@ -17,7 +17,8 @@ namespace tip {
 // Measurement switches.  The launchers' A/B selections, in-kernel traces and ablations are driven by TIP_* environment variables —
 // in a build with -DTIP_MEASURE only (`make measure` -> libtip_hip_measure.so, loaded by the tools under tools/ through
 // TIP_LIB=measure).  In the default build tip_env() is a constant nullptr: every switch sits at its default and the kernels a handle
-// launches depend on tip_set_option alone, never on the process environment.  The switches are listed in include/tip_hip_debug.h.
+// launches depend on tip_set_option alone, never on the process environment.  tip_measure.h is the table of the switches and
+// measure_switches() (below) its one reader: nothing else calls tip_env.
 inline const char* tip_env(const char* name) {
 #ifdef TIP_MEASURE
     return getenv(name);
@@ -221,13 +222,23 @@ struct Workspace {
 
 Workspace carve_workspace(const Dims& d, int B, int T);   // tip_abi.hip
 
-// ---- the forward's schedule (tip_schedule.hip): which plan(s) a batch takes.  Pure host arithmetic, no HIP call ----
-// The four measurement switches of the decision (-DTIP_MEASURE only; all true in the default build), read once:
-// TIP_AUTO_SPLIT=0, TIP_AUTO_MERGE=0, TIP_RNN_ROWS4=0, TIP_HEAD=old
+// B up to which the stages run as roles of ONE launch (lat_flow_kernel, tip_latency.hip): a window's roles share the 32 CUs of one XCD, so windows
+// beyond 8 queue behind each other on their XCD; the launch chain spreads every stage over the whole device instead.
+// Measured back to back on one box (tools/b1_chain.py; one launch / chain, us per forward): B = 1 147 / 158, 8 149 / 173, 12 180 / 191,
+// 16 181 / 199, 24 241 / 262, 32 298 / 286.  Both forms give the same bits (same stage bodies, same summation orders).
+constexpr int kFlowMaxBatch = 24;   // (the default of TIP_LAT_FLOW)
+
+// Every measurement switch, as a field at its default (tip_measure.h is the table).  measure_switches() answers the defaults in the
+// default build and, in the measurement build, what the environment said when it was first asked: launchers ask it, nothing else
+// reads a TIP_* variable.
 struct MeasureSwitches {
-    bool split, merge, rows4, head_ksplit;
+#define TIP_SWITCH(env, type, field, parse, def, doc) type field = def;
+#include "tip_measure.h"
+#undef TIP_SWITCH
 };
-const MeasureSwitches& measure_switches();
+const MeasureSwitches& measure_switches();   // tip_schedule.hip
+
+// ---- the forward's schedule (tip_schedule.hip): which plan(s) a batch takes.  Pure host arithmetic, no HIP call ----
 struct ScheduleIn {
     const Dims& d;
     int B, T;
@@ -294,6 +305,19 @@ struct PerDeviceFlag {
     bool v[kMaxDevices] = {};
     bool& cur() { return v[tip_cur_device()]; }
 };
+// Raise the dynamic-LDS limit of the kernel(s) to `bytes`, once per device and set of kernels (the flag is the instantiation's):
+//   if (hipError_t e = dynamic_lds<kernel_a, kernel_b<true>>(bytes)) return e;
+// Every caller passes the same byte count for a kernel each time (the largest it launches it with).
+template <auto... Kernels>
+inline hipError_t dynamic_lds(int bytes) {
+    static PerDeviceFlag flag;
+    bool& set = flag.cur();
+    if (set) return hipSuccess;
+    hipError_t e = hipSuccess;
+    ((e = e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(Kernels), hipFuncAttributeMaxDynamicSharedMemorySize, bytes)), ...);
+    set = e == hipSuccess;
+    return e;
+}
 struct PerDeviceInt {
     int v[kMaxDevices];
     PerDeviceInt() { for (int& x : v) x = -1; }
@@ -510,11 +534,7 @@ struct WinGemmArgs {
     int ldo;
 };
 hipError_t launch_win_gemm(int N, int K, const WinGemmArgs& a, int B, int T, int num_cus, hipStream_t s);
-// the same kernel as the training forward: activations stashed per `tr`, encoder dropout live (tip_train.hip)
-hipError_t launch_fused_train(const Dims& d, const float* fused_w, const float* x_imu, const float* x_s, const float* keep_mask,
-                              float keep_scale, float* ih_out, float* hall_sentinel, const FusedTrain& tr, int B, int T,
-                              int num_cus, hipStream_t s);
-// ... on the hybrid row tiling (rows 0-31 on 16x16x4, rows 32-39 on 4x4x1 MFMAs: no matrix-core work on the pad rows)
+// the training forward (tip_train.hip): the hybrid kernel with activations stashed per `tr` and the encoder dropout live
 hipError_t launch_fused_train_h(const Dims& d, const float* fused_w, const float* x_imu, const float* x_s, const float* keep_mask,
                                 float keep_scale, float* ih_out, float* hall_sentinel, const FusedTrain& tr, int B, int T,
                                 int num_cus, hipStream_t s);

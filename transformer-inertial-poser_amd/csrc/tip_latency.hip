@@ -1122,12 +1122,6 @@ size_t latency_workspace_floats(int B, int T) {
            (size_t)B * kRnnGemvMaxMembers + 1024 + 128;
 }
 
-// B up to which the stages run as roles of ONE launch (lat_flow_kernel): a window's roles share the 32 CUs of one XCD, so windows
-// beyond 8 queue behind each other on their XCD; the launch chain spreads every stage over the whole device instead.
-// Measured back to back on one box (tools/b1_chain.py; one launch / chain, us per forward): B = 1 147 / 158, 8 149 / 173, 12 180 / 191,
-// 16 181 / 199, 24 241 / 262, 32 298 / 286.  Both forms give the same bits (same stage bodies, same summation orders).
-constexpr int kFlowMaxBatch = 24;
-
 hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float* whh_frag, const float* x_imu,
                                const float* x_s, const float* keep_mask, float keep_scale, float* ws, float* hall, int B,
                                int T, int num_cus, const Guard& gd, hipStream_t s, const TrainDropout* td, const LatencyHead* head) {
@@ -1151,20 +1145,13 @@ hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float*
     constexpr size_t G1 = W2_B + D, BE1 = G1 + D, G2 = BE1 + D, BE2 = G2 + D, LAYER_FLOATS = BE2 + D;
     const bool drop = td && td->thresh;
     // measurement: TIP_LAT_FLOW=0 keeps the launch chain at every batch size, =N moves the switch-over to N windows
-    static const int flow_max = tip_env("TIP_LAT_FLOW") ? atoi(tip_env("TIP_LAT_FLOW")) : kFlowMaxBatch;
+    const int flow_max = measure_switches().lat_flow;
     const size_t ws_bytes = latency_workspace_floats(B, T) * sizeof(float);
     if (head && head->done) *head->done = false;
     // (fault bit 3 = "partners on different XCDs": the chain's territory)
     if (head && head->flags && B <= flow_max && !(gd.fault & 8) && num_cus % 8 == 0 && num_cus >= 64 && 6 + 4 * d.L <= kFlowMaxStages &&
         ws_bytes < 0x7fffffffull && (head->N + 15) / 16 <= 64 && (size_t)T * R * 4 < 0x7fffffffull) {
-        static PerDeviceFlag attr_flag; bool& attr_set = attr_flag.cur();
-        if (!attr_set) {
-            for (const void* f : {reinterpret_cast<const void*>(lat_flow_kernel<false>), reinterpret_cast<const void*>(lat_flow_kernel<true>)}) {
-                hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kFlowSmem * (int)sizeof(float));
-                if (e != hipSuccess) return e;
-            }
-            attr_set = true;
-        }
+        if (hipError_t e = dynamic_lds<lat_flow_kernel<false>, lat_flow_kernel<true>>(kFlowSmem * (int)sizeof(float))) return e;
         LatFlowArgs fa;
         fa.wts = fused_w; fa.wbytes = wbytes;
         fa.x_imu = x_imu; fa.x_s = x_s; fa.keep_mask = keep_mask; fa.keep_scale = keep_scale;
@@ -1190,8 +1177,7 @@ hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float*
         fa.dr = LatDrop{};
         if (td) { fa.dr.seed = td->seed; fa.dr.thresh = td->thresh; fa.dr.scale = td->scale; fa.dr.sdev = td->seeds_dev; }
         fa.gd = gd;
-        static const int trace_on = (tip_env("TIP_FLOW_TRACE") && tip_env("TIP_FLOW_TRACE")[0] == '1') ? 1 : 0;
-        fa.trace = trace_on;
+        fa.trace = measure_switches().flow_trace ? 1 : 0;
         const int per_win = 8 + 16 + d.L * 112 + 32 + kFlowRnnMembers + (head->N + 15) / 16;   // workgroups of one window
         const int grid = 8 * per_win * ((B + 7) / 8);
         if (drop) hipLaunchKernelGGL(lat_flow_kernel<true>, dim3(grid), dim3(256), kFlowSmem * sizeof(float), s, fa);
@@ -1233,11 +1219,8 @@ hipError_t launch_latency_plan(const Dims& d, const float* fused_w, const float*
         hipLaunchKernelGGL((lat_ln_gemm_kernel<false, false>), dim3(32, B), dim3(256), 0, s,
                            LatLnArgs{fused_w, wbytes, xa, pg, pb, (int)(ih_off * 4), (int)(ih_off + (size_t)R * D), ihb, R, nullptr, T, LatDrop{}});
     }
-    // members per stream: 8 while they all fit (8 B <= #CUs), else 4 — same bits either way (one canonical summation order);
-    // measurement: TIP_RNN_GEMV_NM=4 pins the round-5 form
-    static const int nm_env = tip_env("TIP_RNN_GEMV_NM") ? atoi(tip_env("TIP_RNN_GEMV_NM")) : 0;
-    const int nm = nm_env == 4 || nm_env == 8 ? nm_env : (8 * B <= num_cus ? 8 : 4);
-    if (nm == 8) {
+    // members per stream: 8 while they all fit (8 B <= #CUs), else 4 — same bits either way (one canonical summation order)
+    if (8 * B <= num_cus) {
         static PerDeviceInt occ_dev; int& occ = occ_dev.cur();   // the workgroups of every stream's cluster must be resident together
         hipError_t ce = check_coresident(rnn_gemv_kernel<8>, 512, (size_t)0, 8 * B, num_cus, &occ);
         if (ce != hipSuccess) return ce;

@@ -1,13 +1,25 @@
 // tip_schedule.hip — which plan(s) a forward takes: AUTO's cost model, the split of a batch into whole rounds + a remainder, the
 // recurrence variant.  Pure host arithmetic on (Dims, B, T, #CUs, options): no HIP call, no handle mutation, no allocation.
 // tip_abi.hip (forward_impl) runs what schedule_forward answers; tip_debug_schedule shows it without a device.
+#include <string.h>
+
 #include "tip_internal.h"
 
 namespace tip {
 
+// The parsing rules of tip_measure.h: e = the variable's value, null when it is unset (always, in the default build).
+static bool sw_bool(const char* e, bool def) { return e ? e[0] != '0' : def; }
+static int sw_int(const char* e, int def) { return e ? atoi(e) : def; }
+static bool sw_not_old(const char* e, bool def) { return e ? strcmp(e, "old") != 0 : def; }
+
 const MeasureSwitches& measure_switches() {
-    auto off = [](const char* name, char c) { return tip_env(name) && tip_env(name)[0] == c; };
-    static const MeasureSwitches sw{!off("TIP_AUTO_SPLIT", '0'), !off("TIP_AUTO_MERGE", '0'), !off("TIP_RNN_ROWS4", '0'), !off("TIP_HEAD", 'o')};
+    static const MeasureSwitches sw = [] {
+        MeasureSwitches m;
+#define TIP_SWITCH(env, type, field, parse, def, doc) m.field = parse(tip_env(env), def);
+#include "tip_measure.h"
+#undef TIP_SWITCH
+        return m;
+    }();
     return sw;
 }
 
