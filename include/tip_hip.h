@@ -141,6 +141,13 @@ typedef enum tip_status {
 #define TIP_OPT_HANDOFF_KIND 11 /* READ ONLY (tip_get_option): what the sticky hand-off word of tip_check says.  0: nothing pending; 1: a
                                  cooperating kernel's wait gave up (co-residency lost: the answer is TIP_OPT_DEMOTED); 2: only the
                                  one-launch few-stream form found a producer on another XCD (the answer is TIP_OPT_NO_FLOW). */
+#define TIP_OPT_NO_ROUND_LAUNCH 12 /* 1: a batch of at most one window per CU on the hybrid encoder (TIP_PLAN_FUSEDH chosen or pinned, rnn_hidden 512,
+                                 state width 129..131, T <= 40) runs as the three launches encoder / recurrence / projection; 0: as ONE
+                                 launch whose workgroups stay on as recurrence members and projection (same bits; needs the whole
+                                 grid co-resident, else the three launches are taken; never on a demoted handle, and not under
+                                 TIP_OPT_PROFILE = 1: a stage is a launch.  Under TIP_OPT_PROFILE = 2 / 3 the "fused_encoder" pair then
+                                 brackets the whole launch, recurrence and projection phases included).  Default 0: B = 256, T = 40
+                                 0.613-0.616 ms per step against 0.621-0.623 (CHANGELOG.md). */
 #define TIP_OPT_F1S_PARTS   9 /* workgroups that share ONE window under TIP_PLAN_FUSED1S: 2, 4, or 0 (default) = four while 4 B <= #CUs and
                                  B <= 64, two otherwise.  An explicit 4 outside that range is TIP_ERR_UNSUPPORTED_CONFIG at the forward. */
 

@@ -25,7 +25,10 @@
 extern "C" {
 #endif
 
-TIP_API int tip_debug_read_fh_wg(unsigned long long* out, int n);      /* hybrid encoder: per-workgroup start / end stamps (tools/fh_trace.py) */
+TIP_API int tip_debug_read_fh_wg(unsigned long long* out, int n);      /* hybrid encoder: per-workgroup start / end stamps (tools/fh_trace.py), n <= 2048.
+                                                                          2048 < n <= 7168: behind those words the one-launch round's table (same switch;
+                                                                          tools/round_trace.py) — [4 wg] entry, encoder published, recurrence done, exit in
+                                                                          100-MHz ticks, then [4096 + wg] the workgroup's XCC id */
 TIP_API int tip_debug_read_fh_trace(unsigned long long* out, int n);   /* hybrid encoder: phase stamps of workgroup 0 */
 TIP_API int tip_debug_read_bwd_trace(unsigned long long* out, int n);  /* fused backward kernels: phase stamps (tools/bwd_trace.py) */
 TIP_API int tip_debug_pgemm_launches(unsigned long long* out);         /* panel-GEMM launches since load, inference (pgemm_kernel) and
@@ -41,7 +44,7 @@ TIP_API int tip_debug_read_head_trace(unsigned long long* out, int n); /* output
 /* The schedule tip_forward would take for B windows of length T on `cus` CUs (<= 0: the handle's own count; a handle made without
  * a GPU reports 256), under the handle's options and a workspace of `workspace_bytes`; reuse_full: as tip_forward_reuse on full
  * windows.  Touches no device.  out (cap >= 9): nparts, shared_tail, rnn_cluster, then first / count / plan of part 0 and part 1
- * (zeros for an absent part); plan is resolved (never TIP_PLAN_AUTO).  nparts = 2: whole rounds + remainder, as two launch sequences,
+ * (zeros for an absent part), then (cap >= 10) 1 when the batch would run as the one-launch round; plan is resolved (never TIP_PLAN_AUTO).  nparts = 2: whole rounds + remainder, as two launch sequences,
  * or (shared_tail) two encoders with one recurrence and one output projection.  Returns the schedule's status (TIP_OK, or
  * TIP_ERR_UNSUPPORTED_CONFIG for a pinned plan that does not serve the shape), TIP_ERR_INVALID_ARG for bad arguments. */
 TIP_API int tip_debug_schedule(const tip_handle* h, int B, int T, int cus, int reuse_full, size_t workspace_bytes, int* out, int cap);

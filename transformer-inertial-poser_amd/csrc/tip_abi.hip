@@ -325,6 +325,10 @@ int tip_set_option(tip_handle* h, int option, int value) {
             if (value < 0 || value > 1) return TIP_ERR_INVALID_ARG;
             h->no_flow = value;
             return TIP_OK;
+        case TIP_OPT_NO_ROUND_LAUNCH:
+            if (value < 0 || value > 1) return TIP_ERR_INVALID_ARG;
+            h->no_round_launch = value;
+            return TIP_OK;
         default: return TIP_ERR_INVALID_ARG;
     }
 }
@@ -350,6 +354,7 @@ int tip_get_option(const tip_handle* h, int option, int* value) {
         case TIP_OPT_DEMOTED: *value = h->demoted; return TIP_OK;
         case TIP_OPT_F1S_PARTS: *value = h->f1s_parts; return TIP_OK;
         case TIP_OPT_NO_FLOW: *value = h->no_flow; return TIP_OK;
+        case TIP_OPT_NO_ROUND_LAUNCH: *value = h->no_round_launch; return TIP_OK;
         case TIP_OPT_HANDOFF_KIND: {
             const volatile unsigned* w = const_cast<const volatile unsigned*>(h->err_host);
             *value = !w ? 0 : w[0] ? 1 : w[1] ? 2 : 0;
@@ -448,11 +453,11 @@ int tip_profile_read(tip_handle* h, const char** names, float* ms, int* launches
 
 int tip_spin_timeouts(unsigned* count) {
     if (!count) return TIP_ERR_INVALID_ARG;
-    unsigned a = 0, b = 0, c = 0;
+    unsigned a = 0, b = 0, c = 0, r = 0;
     if (read_spin_timeouts_general(&a) != hipSuccess || read_spin_timeouts_latency(&b) != hipSuccess ||
-        read_spin_timeouts_fused2(&c) != hipSuccess)
+        read_spin_timeouts_fused2(&c) != hipSuccess || read_spin_timeouts_round(&r) != hipSuccess)
         return TIP_ERR_HIP;
-    *count = a + b + c;
+    *count = a + b + c + r;
     return TIP_OK;
 }
 
@@ -487,6 +492,7 @@ struct LaunchSeq {
     bool ih_done = false;       // the RNN input projection is in `big` already
     bool hall_armed = false;    // ... and the HALL rows are pre-filled for the sentinel-polling recurrence
     bool rnn_done = false, head_done = false;
+    bool round_launch = false;  // in: one round on the hybrid encoder may run as ONE launch (Schedule::round_launch and nothing of this call against it)
 };
 
 #define TIP_TRY(expr, what)                                     \
@@ -500,6 +506,32 @@ struct LaunchSeq {
         StageScope stage_(q.h, q.s, name); \
         TIP_TRY(expr, name);               \
     } while (0)
+
+// One round on the hybrid encoder as ONE launch (tip_round.hip): encoder, recurrence and — at T = 40, where the register-resident
+// projection serves — the output projection.  1: launched; a status < 0: failed; 0: the launch would not be co-resident (or the shape is
+// not the form's): the caller launches the three kernels.
+static int launch_round(LaunchSeq& q, const float* x_imu, const float* x_s, const float* mask, float* ih, float* hall) {
+    tip_handle* h = q.h;
+    const Dims& d = h->d;
+    const float* P = h->packed_dev;
+    const PackedLayout& L = h->lay;
+    const bool last_only = (q.flags & TIP_FWD_LAST_ROW_ONLY) != 0;
+    const int head = q.T == 40 && measure_switches().head_ksplit ? (last_only ? 2 : 1) : 0;
+    // TIP_OPT_PROFILE = 2 / 3: the dominant stage is the launch that holds the encoder — here the whole round, recurrence and
+    // projection phases included (alternating with three launches on the timed forwards was measured 3 % slower than either form)
+    StageScope sc(h, q.s, "fused_encoder");
+    const hipError_t e = launch_forward_round(d, P + L.fused_off, x_imu, x_s, mask, q.keep_scale, ih, hall,
+                                              reinterpret_cast<unsigned*>(q.W0 + q.ws.flags), P + L.whh_frag_off, P + L.out_frag_off,
+                                              P + L.out_lin.b_off, q.y, q.n, q.T, head, q.cus, h->guard(), q.s);
+    if (e == hipErrorCooperativeLaunchTooLarge || e == hipErrorInvalidValue) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    if (e != hipSuccess) return fail_hip(h, e, "forward_round");
+    q.ih_done = q.hall_armed = q.rnn_done = true;
+    q.head_done = head != 0;
+    return 1;
+}
 
 // The encoder of windows [off, off + p.count) of the sequence.  (A sequence of two parts is the shared tail's: both parts are on plans
 // that emit the RNN input term — only those write at a window offset.)
@@ -524,6 +556,7 @@ static int run_encoder(LaunchSeq& q, const SchedPart& p, int off) {
     const Guard gd = h->guard();
     auto arm_hall = [&]() { return rnn_uses_sentinel(d, q.n, T, q.rnn_cluster); };
     q.plan = p.plan;
+    int round_st = 0;
     if (p.plan == TIP_PLAN_LATENCY) {
         StageScope sc(h, s, "latency_chain");
         LatencyHead lh{P + L.out_frag_off, P + L.out_lin.b_off, q.y, d.S, d.S, (q.flags & TIP_FWD_LAST_ROW_ONLY) != 0, h->flow_epoch, &q.head_done,
@@ -545,6 +578,8 @@ static int run_encoder(LaunchSeq& q, const SchedPart& p, int off) {
         TIP_TRY(launch_fused_encoder2(d, P + L.fused_off, x_imu, x_s, mask, keep_scale, ih, q.hall_armed ? hall : nullptr, B,
                                       cus, s, q.reuse ? q.reuse->cache : nullptr, q.reuse ? q.reuse->frame_ctr : nullptr,
                                       q.reuse ? q.reuse->frame_idx : 0), "fused_encoder2");
+    } else if (p.plan == TIP_PLAN_FUSEDH && q.round_launch && (round_st = launch_round(q, x_imu, x_s, mask, ih, hall)) != 0) {
+        if (round_st < 0) return round_st;
     } else if (p.plan == TIP_PLAN_FUSEDH || p.plan == TIP_PLAN_FUSED) {
         StageScope sc(h, s, "fused_encoder");
         q.ih_done = fused_has_rnn_ih(d);
@@ -685,7 +720,7 @@ static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, flo
     // still grow, T < 40, the ring update below is all the reuse form does and the forward is tip_forward's)
     const bool reuse_full = reuse && T == 40;
     const Schedule sc = schedule_forward(ScheduleIn{d, B, T, f.cus, h->num_cus, h->plan, h->rnn_cluster, h->f1s_parts, h->demoted != 0, reuse_full,
-                                                    workspace_bytes});
+                                                    workspace_bytes, h->no_round_launch != 0});
     if (sc.status != TIP_OK) return sc.status;
     const size_t row_i = (size_t)T * d.n_imu_total, row_s = (size_t)T * d.S;
     const size_t row_y = (flags & TIP_FWD_LAST_ROW_ONLY) ? (size_t)d.S : row_s;
@@ -697,6 +732,9 @@ static int forward_impl(tip_handle* h, const float* x_imu, const float* x_s, flo
         LaunchSeq q{h, s, f.cus, x_imu + first * row_i, x_s + first * row_s, f.mask ? f.mask + first * row_s : nullptr, f.keep_scale,
                     y + first * row_y, rows ? rows + first : nullptr, n, T, flags, static_cast<float*>(workspace),
                     n == B ? f.ws : carve_workspace(d, n, T), sc.part[i].rnn_cluster, reuse_full ? reuse : nullptr, nullptr};
+        // (a stage of TIP_OPT_PROFILE = 1 is a launch: three launches then; under 2 and 3 the pair of the dominant stage brackets the
+        // launch that holds the encoder, launch_round.  tip_forward_rows gathers its rows in launches of its own)
+        q.round_launch = sc.round_launch && h->profile != 1 && !rows;
         CoopSerial serial(h->device, s);   // forwards of different streams do not overlap on the device (cooperating kernels)
         if (serial.status != hipSuccess) return fail_hip(h, serial.status, "stream serialisation");
         if (reuse) {

@@ -14,51 +14,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "tip_internal.h"
-#include "tip_attention.h"
-#include "tip_layernorm.h"
+#include "tip_fused_h.h"   // namespace fz, the device pieces, the hybrid encoder's body
 
 namespace tip {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-namespace fz {
-constexpr int D = 256, H = 16, DH = 16, F = 1024, RP = 48, RB = 3, TMAX = 40, R = 512;
-constexpr int KIN = 224;            // in_linear K, zero padded (221 with acc-sum, 203 without)
-// Row strides of the A-operand planes are = 8 (mod 64) dwords, not the usual "+ 4".  An A fragment is one ds_read_b128 per lane: row
-// l15, dwords 4 lg .. 4 lg + 3 of the k-block.  The LDS serves a b128 read in four groups of 16 lanes that are NOT contiguous —
-// {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ... (MI355X_MICROARCH.md, LDS) — i.e. rows {0-3, 12-15} at one k offset together with rows
-// {4-11} at the NEXT k offset.  In units of 16-byte slots (16 per LDS line) lane (l15, lg) hits slot (s * l15 + lg) mod 16, s = stride / 4
-// mod 16: with s = 1 (stride 260) the two row sets land on {0-3, 12-15} and {5-12} — slot 12 twice, every read 5 LDS cycles instead of
-// 4; with s = 2 (stride 264) on the even and the odd slots.  SQ_LDS_BANK_CONFLICT of the hybrid encoder: 26.4 M -> 3.6 M cycles per
-// launch (the tail fragments' four rows x two k offsets likewise: {0-3} and {1-4} -> {0, 2, 4, 6} and {1, 3, 5, 7}).
-constexpr int LDX = D + 8;          // 264
-constexpr int LDC = 128 + 4;        // 132: one Q / K plane of an 8-head chunk, [48 rows][128 channels]
-constexpr int LDV = RP + 4;         // 52: V is kept TRANSPOSED, [128 channels][48 keys], so P.V reads B fragments as b128
-constexpr int LDU = KIN + 8;        // 232
-constexpr int X_FLOATS = RP * LDX;              // 12480
-constexpr int C_FLOATS = 2 * RP * LDC + 128 * LDV;   // 19328
-constexpr int LDS_BYTES = (X_FLOATS + C_FLOATS) * 4;
-constexpr int THREADS = 512;
-// packed section (floats)
-constexpr size_t IN_W = 0;
-constexpr size_t IN_B = IN_W + (size_t)D * KIN;
-constexpr size_t LAYER0 = IN_B + D;
-constexpr size_t QKV_W = 0;
-constexpr size_t QKV_B = QKV_W + (size_t)3 * D * D;
-constexpr size_t WO_W = QKV_B + 3 * D;
-constexpr size_t WO_B = WO_W + (size_t)D * D;
-constexpr size_t W1_W = WO_B + D;
-constexpr size_t W1_B = W1_W + (size_t)F * D;
-constexpr size_t W2_W = W1_B + F;
-constexpr size_t W2_B = W2_W + (size_t)D * F;
-constexpr size_t G1 = W2_B + D;
-constexpr size_t BE1 = G1 + D;
-constexpr size_t G2 = BE1 + D;
-constexpr size_t BE2 = G2 + D;
-constexpr size_t LAYER_FLOATS = BE2 + D;
-constexpr size_t TAIL_PAD = 4096;      // the k-loop prefetches up to 2 blocks (2 KiB) past a wave's last block
-}  // namespace fz
 
 bool fused_supported(const Dims& d, int T) {
     return d.D == fz::D && d.H == fz::H && d.F == fz::F && d.In <= fz::KIN && T >= 1 && T <= fz::TMAX && d.L >= 1;
@@ -119,157 +77,6 @@ void fused_pack_ops(const Dims& d, const float* const* t, size_t base, std::vect
     }
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// device pieces
-// ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ float wsum(float v) { return wave64_sum(v); }   // DPP + permlane swaps, no LDS round trips
-
-// acc[r][n] += A(rows of block r) x W(block n).  For the first SWAPN column blocks the MFMA operands are swapped (weights
-// as A, activations as B): the accumulator then holds the TRANSPOSED tile — (channels 4*lg + e, row l15) — which is the
-// fragment layout a following MFMA wants for Q and K (tip_attention.h, attention_head_regs).
-template <int NBW, int SWAPN = 0>
-__device__ __forceinline__ void mfma_block(f32x4 (&acc)[fz::RB][NBW], const float4 (&a)[fz::RB], const float4 (&w)[NBW]) {
-#define TIP_MFMA_STEP(c)                                                                                             \
-    _Pragma("unroll") for (int r = 0; r < fz::RB; ++r) _Pragma("unroll") for (int n = 0; n < NBW; ++n)                \
-        acc[r][n] = n < SWAPN ? __builtin_amdgcn_mfma_f32_16x16x4f32(w[n].c, a[r].c, acc[r][n], 0, 0, 0)              \
-                              : __builtin_amdgcn_mfma_f32_16x16x4f32(a[r].c, w[n].c, acc[r][n], 0, 0, 0);
-    TIP_MFMA_STEP(x)
-    TIP_MFMA_STEP(y)
-    TIP_MFMA_STEP(z)
-    TIP_MFMA_STEP(w)
-#undef TIP_MFMA_STEP
-}
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// One 1-KiB fragment block: lane l gets bytes [16 l, 16 l + 16) of the block at byte offset `soff`.
-// raw buffer loads (SGPR descriptor + scalar offset) instead of flat loads: the optimiser treats them as opaque
-// calls, so the software-pipelined prefetch below survives (flat loads from __restrict__ memory were re-sunk to
-// their use, exposing the L2 latency every k-step), and addresses cost one VGPR.
-__device__ __forceinline__ float4 load_frag(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-    // NB: bit-cast the whole vector — __builtin_bit_cast(float, v[i]) on a vector ELEMENT is miscompiled by this
-    // clang (every element reads lane 0 of the vector).
-    const f32x4 f = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0));
-    return make_float4(f.x, f.y, f.z, f.w);
-}
-
-// Register ring of weight fragments: k-blocks (even, odd) of the NBW column blocks a wave owns.
-template <int NBW>
-struct WRing {
-    float4 w0[NBW], w1[NBW];
-};
-
-// Prime a ring with k-blocks 0 and 1 of a phase.  Called EARLY (before the epilogue / barrier / LayerNorm /
-// attention that precedes the phase) so the L2 latency of a phase's first fragments is never exposed.
-template <int NBW>
-__device__ __forceinline__ void ring_prefetch(WRing<NBW>& g, __amdgpu_buffer_rsrc_t rsrc, int voff, int soff, int nstride_b) {
-#pragma unroll
-    for (int n = 0; n < NBW; ++n) {
-        g.w0[n] = load_frag(rsrc, voff, soff + n * nstride_b);
-        g.w1[n] = load_frag(rsrc, voff, soff + n * nstride_b + 1024);
-    }
-}
-
-// acc[r][n] += A[48 x 16*KB] (LDS, leading dim lda) * Wblock(n, kb)   for kb in [0, KB)
-//   soff: byte offset (wave-uniform) of the wave's first block at kb = 0; block n is + n*nstride_b; k-block kb is + kb*1024.
-//   The ring holds k-blocks 0,1 on entry.  The prefetch runs two k-blocks ahead and is unconditional (branch-free
-//   loop => counted vmcnt waits); for the LAST pair it is redirected to k-blocks 0,1 of the NEXT phase
-//   (nsoff / nnstride_b), so on exit the ring is already primed for a following phase of the same width.
-//   Callers without such a successor pass their own soff (a harmless in-bounds reload).
-template <int NBW, int KB, int SWAPN = 0, bool PIN = true>
-__device__ __forceinline__ void gemm_phase(f32x4 (&acc)[fz::RB][NBW], const float* As, int lda, __amdgpu_buffer_rsrc_t rsrc,
-                                           int voff, int soff, int nstride_b, WRing<NBW>& g, int nsoff, int nnstride_b) {
-    static_assert(KB % 2 == 0, "k-blocks are processed in pairs");
-    // A fragments are double-buffered too: the ds_read_b128 of k-block kb+1 is in flight while the MFMAs of kb issue.
-    // (Reads past the last k-block stay inside the LDS allocation and are never used.)
-    float4 a0[fz::RB], a1[fz::RB];
-#pragma unroll
-    for (int r = 0; r < fz::RB; ++r) a0[r] = *reinterpret_cast<const float4*>(As + r * 16 * lda);
-#pragma unroll 1
-    for (int kb = 0; kb < KB; kb += 2) {
-        const bool last = kb + 2 >= KB;                       // wave-uniform: scalar selects, no branch
-        const int o = last ? nsoff : soff + (kb + 2) * 1024;
-        const int st = last ? nnstride_b : nstride_b;
-#pragma unroll
-        for (int r = 0; r < fz::RB; ++r) a1[r] = *reinterpret_cast<const float4*>(As + r * 16 * lda + (kb + 1) * 16);
-        mfma_block<NBW, SWAPN>(acc, a0, g.w0);
-#pragma unroll
-        for (int n = 0; n < NBW; ++n) g.w0[n] = load_frag(rsrc, voff, o + n * st);
-        // PIN: keep the refill here (the scheduler may sink it towards its use).  Measured: helps the training forward and the
-        // backward kernels by ~1 %, costs the stash-free inference kernel 0.7 % — which therefore opts out
-        if (PIN) __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int r = 0; r < fz::RB; ++r) a0[r] = *reinterpret_cast<const float4*>(As + r * 16 * lda + (kb + 2) * 16);
-        mfma_block<NBW, SWAPN>(acc, a1, g.w1);
-#pragma unroll
-        for (int n = 0; n < NBW; ++n) g.w1[n] = load_frag(rsrc, voff, o + n * st + 1024);
-        if (PIN) __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-template <int NBW>
-__device__ __forceinline__ void zero_acc(f32x4 (&acc)[fz::RB][NBW]) {
-#pragma unroll
-    for (int r = 0; r < fz::RB; ++r)
-#pragma unroll
-        for (int n = 0; n < NBW; ++n) acc[r][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-}
-
-// LayerNorm of the residual stream: tip_layernorm.h (16 lanes per row, DPP reductions), all 48 rows here — the pad rows of the
-// padded kernels evolve like real ones and must stay finite.
-// The training forward's stash stores have per-thread row / column offsets that are loop invariant; hoisted out of the layer
-// loop they cost ~50 VGPRs for the whole kernel (hundreds of bytes of scratch per lane).  An opaque copy of the thread index at
-// each use keeps them where they are consumed: a dozen VALU instructions per store loop.
-__device__ __forceinline__ int opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
-
-// rows 0..T-1 of an LDS tile [rows][ld] (COLS floats wide) -> HBM rows of stride dst_ld, 16-byte streaming stores (the stash, 2 MB per
-// window, is read next by the backward; the weights it would push out of L2 in 0.1 us), with a FIXED number of stores per thread
-// (T <= 40: the hybrid kernel), rows >= T dropped by the buffer's range check instead of by a loop bound.  With a run-time trip count
-// the compiler cannot count the stores in flight, and the `s_waitcnt vmcnt(N)`
-// of the weight ring behind such a loop (vector memory retires in order, stores included) degenerates to "all but the last few":
-// every stash point waited for its own stores' acknowledgement before the next phase's first MFMA.
-template <int COLS>
-__device__ __forceinline__ void rows_to_hbm_fixed(const float* lds, int ld, float* dst, int dst_ld, int T, int tid) {
-    constexpr int C4 = COLS / 4, NP = (40 * C4 + fz::THREADS - 1) / fz::THREADS;
-    static_assert((NP * fz::THREADS + C4 - 1) / C4 <= fz::RP, "the passes stay inside the LDS tile's rows");
-    const __amdgpu_buffer_rsrc_t rs = tip_rows_buffer(dst, T * dst_ld * 4);
-#pragma unroll
-    for (int j = 0; j < NP; ++j) {
-        const int i = tid + j * fz::THREADS, r = i / C4, c4 = i - r * C4;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(lds + r * ld + c4 * 4);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ln_u32x4, v), rs, (r * dst_ld + c4 * 4) * 4, 0, kTipNT);
-    }
-}
-
-// The training forward's hidden chunk [T][256] (after ReLU and dropout): rows to HBM as rows_to_hbm_fixed does, plus the chunk's gates
-// (hidden > 0) as BITS for the fused FFN backward.  gb points at row 0 of the window in the gate-bit array [M][32 dwords]:
-//   dword (row, f*8 + 2*e + (c4 >> 5)), bit (c4 & 31)  =  hidden[row][f*256 + 4*c4 + e] > 0      (c4 = 0..63: column quad)
-// One wave iteration is one row (64 lanes = its 64 column quads): four ballots, 32 bytes stored by lane 0.  Round 5: ffn_bwd_kernel
-// read the gates as the saved fp32 hidden rows — 42 MB per layer that arrive cold from HBM in front of each chunk's weight ring
-// (vector memory returns in order: every chunk stalled ~4 000 cycles behind them); as bits they are 1.3 MB, staged into LDS once per window.
-// Five stores per thread whatever T <= 40 is (as rows_to_hbm_fixed); lanes other than 0 drop the bit stores.
-__device__ __forceinline__ void hidden_to_hbm(const float* lds, int ld, float* dst, int dst_ld, unsigned* gb, int f, int T, int tid) {
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    const int lane = tid & 63;
-    const __amdgpu_buffer_rsrc_t rs = tip_rows_buffer(dst, T * dst_ld * 4);
-    const __amdgpu_buffer_rsrc_t gs = tip_rows_buffer(reinterpret_cast<const float*>(gb), T * 128);
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const int r = (tid >> 6) + 8 * j;
-        const f32x4 v = *reinterpret_cast<const f32x4*>(lds + r * ld + lane * 4);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ln_u32x4, v), rs, (r * dst_ld + lane * 4) * 4, 0, kTipNT);
-        const unsigned long long b0 = __builtin_amdgcn_ballot_w64(v[0] > 0.f), b1 = __builtin_amdgcn_ballot_w64(v[1] > 0.f);
-        const unsigned long long b2 = __builtin_amdgcn_ballot_w64(v[2] > 0.f), b3 = __builtin_amdgcn_ballot_w64(v[3] > 0.f);
-        const int off = lane == 0 ? r * 128 + f * 32 : 0x7fffff00;      // one lane writes the row's 32 bytes; the others fall outside the buffer
-        const u32x4 lo = {(unsigned)b0, (unsigned)(b0 >> 32), (unsigned)b1, (unsigned)(b1 >> 32)};
-        const u32x4 hi = {(unsigned)b2, (unsigned)(b2 >> 32), (unsigned)b3, (unsigned)(b3 >> 32)};
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ln_u32x4, lo), gs, off, 0, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(ln_u32x4, hi), gs, off, 16, 0);
-    }
-}
 
 // TIP_PLAN_FUSED: the 48-row inference kernel.  (The training, live and traced forwards are fused_encoder_h_kernel's.)
 // The last argument is not read.  It holds the place of the hybrid kernel's FusedTrain in the kernel-argument block: the implicit
@@ -502,576 +309,18 @@ hipError_t launch_fused_encoder(const Dims& d, const float* fused_w, const float
     return hipGetLastError();
 }
 
-// =====================================================================================================================
-// "fusedh": the one-window kernel with a HYBRID row tiling — no matrix-core work on padded rows.
-//
-// T = 40 rows do not fill three 16-row MFMA blocks: in fused_encoder_kernel every weight fragment multiplies rows 0-15,
-// 16-31 and 32-47, and a third of that last block's cycles (17 % of all MFMA issue time) is spent on the eight zero rows
-// 40-47.  Here rows 0-31 keep v_mfma_f32_16x16x4_f32 (two row blocks), and rows 32-39 go through
-// v_mfma_f32_4x4x1_16b_f32 — sixteen independent 4x4x1 blocks per instruction, 512 FLOP in 2 passes (measured 8.4-9 cycles
-// per instruction against 32 for a 16x16x4: tools/probes/mfma4x4_probe.hip) — fed by THE SAME B-fragment registers:
-//   the 16x16x4 weight fragment has lane (l15, lg) = W[col 16 nb + l15][k = 16 kb + 4 lg + s] in component s.  Read as the
-//   B operand of a 4x4x1, lane 4 b + j is column j of block b: block b = 4 lg + (l15 >> 2), j = l15 & 3, i.e. block
-//   (lg, cb) multiplies columns 4 cb .. 4 cb + 3 at k = 16 kb + 4 lg + s.  Its A operand (lane 4 b + i = row i of block b)
-//   is X[row0 + i][16 kb + 4 lg + s]: one ds_read_b128 per (4-row block, k-block), lanes that differ only in cb reading the
-//   same address (LDS broadcast).  The accumulator of lane (lg, cb, j) then holds, in register i, the partial sum over the
-//   k == 4 lg .. 4 lg + 3 (mod 16) of output (row0 + i, column 16 nb + 4 cb + j): four k-partials per output, one per lg,
-//   combined once per phase by a two-step exchange (xor 32, xor 16) that leaves row row0 + lg in lane (lg, l15).
-// Per (16-column block, k-block): 8 big + 8 small MFMAs = 8 x 32 + 8 x 9 = 328 issue cycles instead of 12 x 32 = 384.
-// The QKV projection does the same; its rows 32..39 reach the attention's register fragments (attention_head_regs: Q^T / K^T
-// tiles with the row in the lane index) through a 1.3-KB per-wave LDS patch that transposes the tail's (row, channel) result.
-// Rows 40-47 of X are zeroed once and never written again (LayerNorm covers rows 0-39): finite pad keys/values for the attention.
-// Numerics: rows 0-31 are bit-identical to TIP_PLAN_FUSED (same instructions; causality keeps rows >= 32 out of them);
-// rows 32-39 differ in summation order only (four k-chains per output instead of one).
-// =====================================================================================================================
-namespace fzh {
-constexpr int RBM = 2;    // 16-row MFMA blocks (rows 0-31)
-constexpr int RBT = 2;    // 4-row blocks of the tail (rows 32-35, 36-39)
-constexpr int TAIL0 = 32;
-}  // namespace fzh
+// "fusedh": the one-window kernel with the hybrid row tiling (the design and the body: tip_fused_h.h)
+__device__ unsigned long long g_fh_trace[64];      // measurement only (TIP_FUSEDH_TRACE=1)
+__device__ unsigned long long g_fh_wg[2 * 1024];
 
-// (the first SWAPN column blocks of the 16-row part with swapped operands, as in mfma_block: transposed accumulators)
-template <int NBW, int SWAPN = 0>
-__device__ __forceinline__ void mfma_block_h(f32x4 (&acc)[fzh::RBM][NBW], f32x4 (&acct)[fzh::RBT][NBW], const float4 (&a)[fzh::RBM],
-                                             const float4 (&at)[fzh::RBT], const float4 (&w)[NBW]) {
-#define TIP_MFMA_STEP_H(c)                                                                                            \
-    _Pragma("unroll") for (int r = 0; r < fzh::RBM; ++r) _Pragma("unroll") for (int n = 0; n < NBW; ++n)               \
-        acc[r][n] = n < SWAPN ? __builtin_amdgcn_mfma_f32_16x16x4f32(w[n].c, a[r].c, acc[r][n], 0, 0, 0)              \
-                              : __builtin_amdgcn_mfma_f32_16x16x4f32(a[r].c, w[n].c, acc[r][n], 0, 0, 0);             \
-    _Pragma("unroll") for (int r = 0; r < fzh::RBT; ++r) _Pragma("unroll") for (int n = 0; n < NBW; ++n)               \
-        acct[r][n] = __builtin_amdgcn_mfma_f32_4x4x1f32(at[r].c, w[n].c, acct[r][n], 0, 0, 0);
-    TIP_MFMA_STEP_H(x)
-    TIP_MFMA_STEP_H(y)
-    TIP_MFMA_STEP_H(z)
-    TIP_MFMA_STEP_H(w)
-#undef TIP_MFMA_STEP_H
-}
-
-// acc  [r][n] += A[rows 16 r .. 16 r + 15] x Wblock(n, kb)      (r = 0, 1)
-// acct [r][n] += A[rows 32 + 4 r .. + 3]  x Wblock(n, kb), per-lg k-partials (see above)
-//   Am: this lane's LDS address for the 16-row blocks (base + l15 * lda + lg * 4);  At: for the tail (base + (32 + (lane & 3)) *
-//   lda + lg * 4).  Weight ring semantics exactly as gemm_phase.
-template <int NBW, int KB, int SWAPN = 0, bool PIN = false>
-__device__ __forceinline__ void gemm_phase_h(f32x4 (&acc)[fzh::RBM][NBW], f32x4 (&acct)[fzh::RBT][NBW], const float* Am, const float* At,
-                                             int lda, __amdgpu_buffer_rsrc_t rsrc, int voff, int soff, int nstride_b, WRing<NBW>& g,
-                                             int nsoff, int nnstride_b) {
-    static_assert(KB % 2 == 0, "k-blocks are processed in pairs");
-    float4 a0[fzh::RBM], a1[fzh::RBM], t0[fzh::RBT], t1[fzh::RBT];
-#pragma unroll
-    for (int r = 0; r < fzh::RBM; ++r) a0[r] = *reinterpret_cast<const float4*>(Am + r * 16 * lda);
-#pragma unroll
-    for (int r = 0; r < fzh::RBT; ++r) t0[r] = *reinterpret_cast<const float4*>(At + r * 4 * lda);
-#pragma unroll 1
-    for (int kb = 0; kb < KB; kb += 2) {
-        const bool last = kb + 2 >= KB;
-        const int o = last ? nsoff : soff + (kb + 2) * 1024;
-        const int st = last ? nnstride_b : nstride_b;
-#pragma unroll
-        for (int r = 0; r < fzh::RBM; ++r) a1[r] = *reinterpret_cast<const float4*>(Am + r * 16 * lda + (kb + 1) * 16);
-#pragma unroll
-        for (int r = 0; r < fzh::RBT; ++r) t1[r] = *reinterpret_cast<const float4*>(At + r * 4 * lda + (kb + 1) * 16);
-        mfma_block_h<NBW, SWAPN>(acc, acct, a0, t0, g.w0);
-#pragma unroll
-        for (int n = 0; n < NBW; ++n) g.w0[n] = load_frag(rsrc, voff, o + n * st);
-        if (PIN) __builtin_amdgcn_sched_barrier(0);   // (as in gemm_phase: keeps the refill ahead of the second half's MFMAs)
-#pragma unroll
-        for (int r = 0; r < fzh::RBM; ++r) a0[r] = *reinterpret_cast<const float4*>(Am + r * 16 * lda + (kb + 2) * 16);
-#pragma unroll
-        for (int r = 0; r < fzh::RBT; ++r) t0[r] = *reinterpret_cast<const float4*>(At + r * 4 * lda + (kb + 2) * 16);
-        // the NEXT pair's first A fragments are requested HERE, half an iteration ahead: left to itself the scheduler sinks these reads
-        // to the top of the next iteration, right in front of the MFMA that needs them, and both waves of a SIMD — in step behind every
-        // barrier — then sit out an LDS round trip per k-block pair with the matrix pipe idle
-        __builtin_amdgcn_sched_barrier(0);
-        mfma_block_h<NBW, SWAPN>(acc, acct, a1, t1, g.w1);
-#pragma unroll
-        for (int n = 0; n < NBW; ++n) g.w1[n] = load_frag(rsrc, voff, o + n * st + 1024);
-        if (PIN) __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-template <int NBW>
-__device__ __forceinline__ void zero_acc_h(f32x4 (&acc)[fzh::RBM][NBW], f32x4 (&acct)[fzh::RBT][NBW]) {
-#pragma unroll
-    for (int n = 0; n < NBW; ++n) {
-#pragma unroll
-        for (int r = 0; r < fzh::RBM; ++r) acc[r][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < fzh::RBT; ++r) acct[r][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-}
-
-// Combine the four k-partials of a tail accumulator (registers = rows row0 .. row0 + 3, one partial per lg): two exchange
-// steps, after which lane (lg, l15) holds the finished sum of row row0 + lg, column l15 of the block.  Every row is summed
-// as (p[lg] + p[lg ^ 2]) + (p[lg ^ 1] + p[lg ^ 3]) — the same pairing for all four rows.
-// Three permlane swaps (tip_layernorm.h), no LDS crossbar: swap32(v0, v2) leaves {v0.lo, v2.lo} and {v0.hi, v2.hi}, whose sum is
-// row 0 in lanes 0-31 and row 2 in lanes 32-63 — exactly what "keep one row, hand the other to lane ^ 32" produces.
-__device__ __forceinline__ float tail_reduce(const f32x4& v, int lg) {
-    (void)lg;
-    float a = v[0], b = v[2];
-    swap32(a, b);
-    float k0 = a + b;              // rows {0,1} live on with lg in {0,1}, rows {2,3} with lg in {2,3}
-    a = v[1], b = v[3];
-    swap32(a, b);
-    float k1 = a + b;
-    swap16(k0, k1);
-    return k0 + k1;                // row 2 * (lg >> 1) + (lg & 1) = lg
-}
-
-// The V tile of rows 32..47 in the plain accumulator layout (lane (l15, lg) = rows 32 + 4 lg + e, channel l15) from the two tail
-// accumulators (a0: rows 32..35, a1: rows 36..39; four k-partials each, one per lg): all four rows of block lg must end up in
-// ONE lane — an all-reduce over lg rather than tail_reduce's reduce-scatter.  swap16(a0, a1) pairs lg with lg ^ 1 and parks
-// block 0 in the even, block 1 in the odd lane groups; swap32 of the sums finishes both.  Lanes lg = 2, 3 (pad rows 40..47,
-// multiplied by P = 0 in the attention) get zeros.
-__device__ __forceinline__ f32x4 tail_gather_v(const f32x4& a0, const f32x4& a1, int lg) {
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        float x = a0[e], y = a1[e];
-        swap16(x, y);
-        float s = x + y, t = s;
-        swap32(s, t);
-        o[e] = s + t;
-    }
-    return lg < 2 ? o : (f32x4){0.f, 0.f, 0.f, 0.f};
-}
-
-// measurement only (TIP_FUSEDH_TRACE=1): s_memtime stamps of workgroup 0 / thread 0 at the phase boundaries of layer 1
-__device__ unsigned long long g_fh_trace[64];
-__device__ unsigned long long g_fh_wg[2 * 1024];   // TRACE: [workgroup][entry, exit] in s_memrealtime ticks (100 MHz, device-wide)
-#define FH_STAMP(slot) do { if (TRACE && blockIdx.x == 0 && tid == 0 && (layer == 1 || (slot) < 4 || (slot) >= 40)) g_fh_trace[slot] = __builtin_amdgcn_s_memtime(); } while (0)
-
-// TR: training forward (tip_train_forward) — the encoder's four dropout sites and the activation stash of the backward, exactly
-// as fused_encoder_kernel<8> writes them (same arrays, same per-element dropout keys: the masks do not depend on the tiling).
 template <bool TRACE, bool TR, bool LIVE = false>
 __global__ __launch_bounds__(fz::THREADS) void fused_encoder_h_kernel(
     const float* __restrict__ wts, const float* __restrict__ x_imu, const float* __restrict__ x_s,
     const float* __restrict__ keep_mask, float keep_scale, float* __restrict__ xout, float* __restrict__ ih_out,
     unsigned* __restrict__ hall_sentinel, int B, int T, int NI, int S, int L, int wbytes, int ih_off_b, FusedEncArgs<LIVE> tr) {
-    using namespace fz;
-    using namespace fzh;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* X = smem;
-    float* C = smem + X_FLOATS;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l15 = lane & 15, lg = lane >> 4;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(wts), 0, wbytes, 0x00020000);
-    const int voff = lane * 16;
-    // this lane's LDS offsets (floats) inside a [rows][ld] operand: 16-row blocks / tail blocks
-    auto am = [&](int ld) { return l15 * ld + lg * 4; };
-    auto at = [&](int ld) { return (TAIL0 + (lane & 3)) * ld + lg * 4; };
-    // LIVE: the deployed forward (tip_forward_live) — the TR instantiation's four dropout sites and the past-state keep mask drawn in the
-    // prologue, no stash; the inference instantiation's outputs.  Both seeds come from lv.seeds (device, {seed, state_seed}) when given:
-    // scalar loads, and every key below is computed from them once per site on the scalar unit.
-    constexpr bool DR = TR || LIVE;
-    const LiveArgs lv = live_args_of(tr);
-    unsigned long long dseed = tr.seed, sseed = 0;
-    if (LIVE) {
-        sseed = lv.state_seed;
-        if (lv.seeds) { dseed = lv.seeds[0]; sseed = lv.seeds[1]; }
-    }
-    const unsigned mkey = LIVE && lv.mthresh ? tip_drop_key_s(sseed, kStateMaskSite) : 0u;
-
-    // rows 40..47 of the residual stream: zero once, never written again (finite pad keys / values for the attention)
-    for (int i = tid; i < 8 * LDX; i += THREADS) X[TMAX * LDX + i] = 0.f;
-
-    for (int win = blockIdx.x; win < B; win += gridDim.x) {
-        WRing<3> g_qkv;
-        {
-        const int layer = -1;
-        FH_STAMP(0);
-        if (TRACE && tid == 0 && win == (int)blockIdx.x && blockIdx.x < 1024) g_fh_wg[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
-        const int in_soff = (int)(IN_W * 4) + (wave * 2) * (KIN / 16) * 1024;
-        WRing<2> g_in;
-        ring_prefetch<2>(g_in, rsrc, voff, in_soff, (KIN / 16) * 1024);
-        // ---- P0 prologue (:63-78) ------------------------------------------------------------------------------------
-        float* U = C;
-        for (int i = tid; i < RP * LDU / 4; i += THREADS) reinterpret_cast<float4*>(U)[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-        __syncthreads();
-        {
-            // Round 3: rows wave, wave + 8, ... (five per wave at T = 40), a lane per column: unit-stride loads without an index
-            // division, ALL of a wave's loads in flight before the first is used, unconditional (clamped addresses), and the LDS
-            // stores through one base + COMPILE-TIME offsets.  The element loop this replaces (i = tid, tid + 512, ...: 18 trips,
-            // each a dependent HBM round trip behind an integer division) took 17.2 k cycles per window; a first attempt at
-            // batching the loads (round 2) spilled its forty store addresses and was slower.
-            constexpr int NR = (TMAX + 7) / 8;
-            float vi[NR][2], vs[NR][3], vk[NR][3];
-            const float* kmb = keep_mask ? keep_mask : x_s;
-#pragma unroll
-            for (int j = 0; j < NR; ++j) {
-                const int r = wave + 8 * j;
-                const int rc = r < T ? r : T - 1;
-                const float* xi = x_imu + ((size_t)win * T + rc) * NI;
-                const float* xs = x_s + ((size_t)win * T + rc) * S;
-                const float* km = kmb + ((size_t)win * T + rc) * S;
-#pragma unroll
-                for (int q = 0; q < 2; ++q) vi[j][q] = xi[lane + 64 * q < NI ? lane + 64 * q : NI - 1];
-#pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    const int c = lane + 64 * q < S ? lane + 64 * q : S - 1;
-                    vs[j][q] = xs[c];
-                    vk[j][q] = km[c];
-                }
-            }
-            float* pu_i = U + wave * LDU + lane;
-            float* pu_s = pu_i + NI;
-#pragma unroll
-            for (int j = 0; j < NR; ++j) {
-                if (wave + 8 * j < T) {
-#pragma unroll
-                    for (int q = 0; q < 2; ++q)
-                        if (lane + 64 * q < NI) pu_i[8 * j * LDU + 64 * q] = vi[j][q];
-#pragma unroll
-                    for (int q = 0; q < 3; ++q)
-                        if (lane + 64 * q < S) {
-                            float v = vs[j][q];
-                            if (v != v) v = 0.f;                               // :65
-                            if (keep_mask) v = v * vk[j][q] * keep_scale;     // :77 with an explicit keep-mask
-                            else if (LIVE && lv.mthresh)                       // ... or drawn here: tip_draw_keep_mask's decision of this element of x_s
-                                v = v * (tip_drop_hash_k(mkey, ((unsigned)win * (unsigned)T + (unsigned)(wave + 8 * j)) * (unsigned)S + (unsigned)(lane + 64 * q)) >= lv.mthresh ? 1.f : 0.f) * keep_scale;
-                            pu_s[8 * j * LDU + 64 * q] = v;
-                        }
-                }
-            }
-        }
-        __syncthreads();
-        FH_STAMP(1);
-        // training forward: the staged input rows are dW_in's operand in the backward — stashed from here instead of by a launch of
-        // their own (tip_train.hip)
-        if (TR && tr.u) rows_to_hbm_fixed<KIN>(U, LDU, tr.sv + (size_t)tr.u * 64 + (size_t)win * T * KIN, KIN, T, opaque(tid));
-        // ---- P1 in_linear (:79) + channel shuffle (folded) -------------------------------------------------------------
-        {
-            f32x4 acc[RBM][2], acct[RBT][2];
-            zero_acc_h<2>(acc, acct);
-            gemm_phase_h<2, KIN / 16, 0, TR>(acc, acct, U + am(LDU), U + at(LDU), LDU, rsrc, voff, in_soff, (KIN / 16) * 1024, g_in, in_soff,
-                                      (KIN / 16) * 1024);
-            ring_prefetch<3>(g_qkv, rsrc, voff, (int)(LAYER0 * 4) + (int)(QKV_W * 4) + wave * 16 * 1024, 16 * 16 * 1024);
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const int col = (wave * 2 + n) * 16 + l15;
-                const float bv = wts[IN_B + col];
-#pragma unroll
-                for (int r = 0; r < RBM; ++r)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) X[(r * 16 + lg * 4 + e) * LDX + col] = acc[r][n][e] + bv;
-#pragma unroll
-                for (int r = 0; r < RBT; ++r) X[(TAIL0 + 4 * r + lg) * LDX + col] = tail_reduce(acct[r][n], lg) + bv;
-            }
-        }
-        __syncthreads();
-        FH_STAMP(2);
-        }
-        const size_t grow0 = (size_t)win * T;           // first global row (b*T + t) of this window
-        if (TR) rows_to_hbm_fixed<D>(X, LDX, tr.sv + (size_t)tr.x0 * 64 + grow0 * D, D, T, opaque(tid));
-#pragma unroll 1
-        for (int layer = 0; layer < L; ++layer) {
-            FH_STAMP(8);
-            const float* LW = wts + LAYER0 + (size_t)layer * LAYER_FLOATS;
-            const int lbase = (int)((LAYER0 + (size_t)layer * LAYER_FLOATS) * 4);
-            float* svl = TR ? tr.sv + (size_t)layer * tr.layer_stride * 64 : nullptr;   // this layer's stash
-            const unsigned dk1 = DR ? tip_drop_key_s(dseed, (unsigned)(layer * 4 + 1)) : 0u;
-            const unsigned dk2 = DR ? tip_drop_key_s(dseed, (unsigned)(layer * 4 + 2)) : 0u;
-            const unsigned dk3 = DR ? tip_drop_key_s(dseed, (unsigned)(layer * 4 + 3)) : 0u;
-            float bvo[2], bv2[2];   // out-projection / linear2 biases of this wave's columns: requested a phase (or eight) ahead of their use
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                bvo[n] = LW[WO_B + (wave * 2 + n) * 16 + l15];
-                bv2[n] = LW[W2_B + (wave * 2 + n) * 16 + l15];
-            }
-            WRing<2> g_o, g_f;
-            // ---- self-attention block.  Wave w owns heads w and 8 + w END TO END and runs them back to back with no workgroup
-            // barrier in between: projection -> attention -> projection -> attention.  The two waves that share a SIMD drift apart
-            // in this stretch, so one's softmax (VALU, LDS) runs under the other's projection MFMAs instead of both idling the
-            // matrix pipe at the same time in front of a barrier; then ONE out-projection over all 16 heads (K = 256).
-            float* Oc = C;   // attention output of all heads [48 rows][256 channels], leading dimension LDX: the out-projection's A operand
-#pragma unroll 1
-            for (int c = 0; c < 2; ++c) {
-                const int head = c * 8 + wave;
-                f32x4 acc[RBM][3], acct[RBT][3];
-                zero_acc_h<3>(acc, acct);
-                const int qsoff = lbase + (int)(QKV_W * 4) + head * 16 * 1024;
-                // rows 0..31: Q and K with swapped operands (their accumulators are the attention's transposed fragments), V plain;
-                // rows 32..39: all three through the 4x4x1 tail in the plain orientation.  The tail of head w's product primes
-                // the ring with head 8 + w's first fragments (they fly during head w's attention).
-                const int nxt = c == 0 ? qsoff + 8 * 16 * 1024 : qsoff;
-                gemm_phase_h<3, 16, 2, TR>(acc, acct, X + am(LDX), X + at(LDX), LDX, rsrc, voff, qsoff, 16 * 16 * 1024, g_qkv, nxt,
-                                       16 * 16 * 1024);
-                if (c == 1)   // out-projection fragments fly during the second attention and the barrier
-                    ring_prefetch<2>(g_o, rsrc, voff, lbase + (int)(WO_W * 4) + (wave * 2) * 16 * 1024, 16 * 1024);
-                const f32x4 bq = *reinterpret_cast<const f32x4*>(LW + QKV_B + head * 16 + lg * 4);
-                const f32x4 bk = *reinterpret_cast<const f32x4*>(LW + QKV_B + D + head * 16 + lg * 4);
-                const float bv = LW[QKV_B + 2 * D + head * 16 + l15];
-                f32x4 qt[RB], kt[RB], vv[RB];
-#pragma unroll
-                for (int r = 0; r < RBM; ++r) {
-                    qt[r] = acc[r][0] + bq;
-                    kt[r] = acc[r][1] + bk;
-                    vv[r] = acc[r][2] + bv;
-                }
-                // Third row block (rows 32..47, eight of them real).  V: gather the tail into the plain layout.  Q, K: the tail
-                // yields (row 4 rb + lg, channel l15) per lane; the attention wants (row l15, channels 4 lg ..): a 1.3-KB per-wave
-                // LDS patch behind the O plane does the transpose, no workgroup barrier — a wave's LDS operations complete in
-                // program order.
-                vv[2] = tail_gather_v(acct[0][2], acct[1][2], lg);
-                if (lg < 2) vv[2] += bv;
-                {
-                    constexpr int SLD = 20;                                   // 16 channels + 4: b128 reads of 8 rows conflict-free
-                    float* scr = C + RP * LDX + wave * (2 * 8 * SLD);
-                    const float bqp = LW[QKV_B + head * 16 + l15], bkp = LW[QKV_B + D + head * 16 + l15];
-#pragma unroll
-                    for (int rb = 0; rb < RBT; ++rb) {
-                        scr[(4 * rb + lg) * SLD + l15] = tail_reduce(acct[rb][0], lg) + bqp;
-                        scr[8 * SLD + (4 * rb + lg) * SLD + l15] = tail_reduce(acct[rb][1], lg) + bkp;
-                    }
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-                    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
-                    qt[2] = l15 < 8 ? *reinterpret_cast<const f32x4*>(scr + l15 * SLD + lg * 4) : z;
-                    kt[2] = l15 < 8 ? *reinterpret_cast<const f32x4*>(scr + 8 * SLD + l15 * SLD + lg * 4) : z;
-                    __builtin_amdgcn_wave_barrier();                          // (the patch is rewritten by this wave's next head)
-                }
-                FH_STAMP(9 + 4 * c);    // QKV projection issued and its results consumed
-                if (TR) {
-                    // raw q (the packed W_q carries the 1/sqrt(d_head) fold: undo it exactly), k, v -> [M, 3D]; the third block has
-                    // the same fragment layout as the padded kernel's (rows 32 + l15 / rows 32 + 4 lg + e), pad rows masked by T
-                    // (a buffer of this window's T rows: the pad rows' stores are dropped by the range check, not by a branch each)
-                    const __amdgpu_buffer_rsrc_t qp_rs = tip_rows_buffer(svl + (size_t)tr.qkv * 64 + grow0 * (3 * D), T * 3 * D * 4);
-                    const int lo = opaque(lane), l15o = lo & 15, lgo = lo >> 4;
-#pragma unroll
-                    for (int r = 0; r < RB; ++r) {
-                        const int qo = ((r * 16 + l15o) * (3 * D) + head * 16 + lgo * 4) * 4;
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, qt[r] * 4.0f), qp_rs, qo, 0, kTipNT);
-                        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, kt[r]), qp_rs, qo + D * 4, 0, kTipNT);
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(vv[r][e]), qp_rs,
-                                                                  ((r * 16 + lgo * 4 + e) * (3 * D) + 2 * D + head * 16 + l15o) * 4, 0, kTipNT);
-                    }
-                    attention_head_regs<LDX, true>(qt, kt, vv, Oc, head * 16, lo, TMAX, svl + (size_t)tr.ast * 64,
-                                                   (unsigned long long)win * H + head, T, tr.seed, (unsigned)(layer * 4 + 0), tr.thresh,
-                                                   tr.scale);
-                } else if (LIVE) {   // dropout on the probabilities as TR draws it, no statistics
-                    attention_head_regs<LDX, true, false>(qt, kt, vv, Oc, head * 16, opaque(lane), TMAX, nullptr, (unsigned long long)win * H + head, T,
-                                                          dseed, (unsigned)(layer * 4 + 0), tr.thresh, tr.scale);
-                } else {
-                    attention_head_regs<LDX>(qt, kt, vv, Oc, head * 16, lane, TMAX);   // rows 40..47 of the O plane are never read
-                }
-                FH_STAMP(10 + 4 * c);
-            }
-            __syncthreads();
-            FH_STAMP(15);
-            if (TR) rows_to_hbm_fixed<D>(Oc, LDX, svl + (size_t)tr.att * 64 + grow0 * D, D, T, opaque(tid));
-            ring_prefetch<2>(g_f, rsrc, voff, lbase + (int)(W1_W * 4) + (wave * 2) * 16 * 1024, 16 * 1024);
-            f32x4 acc_o[RBM][2], acc_ot[RBT][2];
-            zero_acc_h<2>(acc_o, acc_ot);
-            {
-                const int osoff = lbase + (int)(WO_W * 4) + (wave * 2) * 16 * 1024;
-                gemm_phase_h<2, 16, 0, TR>(acc_o, acc_ot, Oc + am(LDX), Oc + at(LDX), LDX, rsrc, voff, osoff, 16 * 1024, g_o, osoff, 16 * 1024);
-            }
-            __syncthreads();
-            FH_STAMP(16);
-            // residual + bias, then LayerNorm1.  The residual values of this lane's 20 elements are READ before the first is written
-            // back: `X[i] += v` per element compiles to a chain of ds_read -> wait -> ds_write round trips (2-3 k cycles per epilogue
-            // with the matrix pipe idle; the optimiser may not move a read across a write it cannot prove disjoint).
-            float xr[2][RBM][4], xt[2][RBT];
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {   // (the unroll pragma above binds to this loop)
-                const int col = (wave * 2 + n) * 16 + l15;
-#pragma unroll
-                for (int r = 0; r < RBM; ++r)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xr[n][r][e] = X[(r * 16 + lg * 4 + e) * LDX + col];
-#pragma unroll
-                for (int r = 0; r < RBT; ++r) xt[n][r] = X[(TAIL0 + 4 * r + lg) * LDX + col];
-            }
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const int col = (wave * 2 + n) * 16 + l15;
-                const float bv = bvo[n];
-                    const int hl = LIVE ? opaque(lane) : lane, hlg = LIVE ? hl >> 4 : lg, hcol = LIVE ? (wave * 2 + n) * 16 + (hl & 15) : col;   // (LIVE: the hash indices are formed here, not hoisted out of the layer loop and spilled)
-#pragma unroll
-                for (int r = 0; r < RBM; ++r)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = acc_o[r][n][e] + bv;
-                        if (DR && tr.thresh)
-                            v = tip_drop_hash_k(dk1, (grow0 + r * 16 + hlg * 4 + e) * D + hcol) >= tr.thresh ? v * tr.scale : 0.f;
-                        X[(r * 16 + lg * 4 + e) * LDX + col] = xr[n][r][e] + v;
-                    }
-#pragma unroll
-                for (int r = 0; r < RBT; ++r) {
-                    float v = tail_reduce(acc_ot[r][n], lg) + bv;
-                    if (DR && tr.thresh)
-                        v = tip_drop_hash_k(dk1, (grow0 + TAIL0 + 4 * r + hlg) * D + hcol) >= tr.thresh ? v * tr.scale : 0.f;
-                    X[(TAIL0 + 4 * r + lg) * LDX + col] = xt[n][r] + v;
-                }
-            }
-            __syncthreads();
-            FH_STAMP(17);
-            if (TR)
-                layernorm_rows16<fz::TMAX, fz::LDX, true>(X, LW + G1, LW + BE1, wave, opaque(lane), svl + (size_t)tr.z1 * 64 + grow0 * D,
-                                                          svl + (size_t)tr.st1 * 64 + grow0 * 2, svl + (size_t)tr.x1 * 64 + grow0 * D, T);
-            else
-                layernorm_rows16<fz::TMAX, fz::LDX>(X, LW + G1, LW + BE1, wave, lane);   // rows 40..47 stay zero
-            __syncthreads();
-            FH_STAMP(18);
-            // ---- feed-forward block: hidden in 4 chunks of 256, linear2 accumulates in registers -------------------------
-            float* Hc = C;
-            f32x4 acc_f[RBM][2], acc_ft[RBT][2];
-            zero_acc_h<2>(acc_f, acc_ft);
-#pragma unroll 1
-            for (int f = 0; f < 4; ++f) {
-                {
-                    f32x4 acc[RBM][2], acct[RBT][2];
-                    zero_acc_h<2>(acc, acct);
-                    const int nb0 = f * 16 + wave * 2;
-                    const int w1off = lbase + (int)(W1_W * 4) + nb0 * 16 * 1024;
-                    const int w2off = lbase + (int)(W2_W * 4) + ((wave * 2) * 64 + f * 16) * 1024;
-                    // (the epilogue's bias is requested BEFORE the product: after it, the L2 round trip would be exposed 16 times a layer)
-                    float bv1[2];
-#pragma unroll
-                    for (int n = 0; n < 2; ++n) bv1[n] = LW[W1_B + f * 256 + (wave * 2 + n) * 16 + l15];
-                    gemm_phase_h<2, 16, 0, TR>(acc, acct, X + am(LDX), X + at(LDX), LDX, rsrc, voff, w1off, 16 * 1024, g_f, w2off, 64 * 1024);
-#pragma unroll
-                    for (int n = 0; n < 2; ++n) {
-                        const int col = (wave * 2 + n) * 16 + l15;
-                        const float bv = bv1[n];
-                    const int hl = LIVE ? opaque(lane) : lane, hlg = LIVE ? hl >> 4 : lg, hcol = LIVE ? (wave * 2 + n) * 16 + (hl & 15) : col;   // (LIVE: the hash indices are formed here, not hoisted out of the layer loop and spilled)
-#pragma unroll
-                        for (int r = 0; r < RBM; ++r)
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) {
-                                float v = fmaxf(acc[r][n][e] + bv, 0.f);
-                                if (DR && tr.thresh)
-                                    v = tip_drop_hash_k(dk2, (grow0 + r * 16 + hlg * 4 + e) * F + f * 256 + hcol) >= tr.thresh ? v * tr.scale : 0.f;
-                                Hc[(r * 16 + lg * 4 + e) * LDX + col] = v;
-                            }
-#pragma unroll
-                        for (int r = 0; r < RBT; ++r) {
-                            float v = fmaxf(tail_reduce(acct[r][n], lg) + bv, 0.f);
-                            if (DR && tr.thresh)
-                                v = tip_drop_hash_k(dk2, (grow0 + TAIL0 + 4 * r + hlg) * F + f * 256 + hcol) >= tr.thresh ? v * tr.scale : 0.f;
-                            Hc[(TAIL0 + 4 * r + lg) * LDX + col] = v;
-                        }
-                    }
-                }
-                FH_STAMP(19 + 3 * f);
-                __syncthreads();
-                FH_STAMP(20 + 3 * f);
-                if (TR)   // (the gate bits sit behind the layer's [M][F] hidden rows: saved_layout, tip_train.hip)
-                    hidden_to_hbm(Hc, LDX, svl + (size_t)tr.hid * 64 + grow0 * F + f * 256, F,
-                                  reinterpret_cast<unsigned*>(svl + (size_t)tr.hid * 64 + (size_t)B * T * F) + grow0 * 32, f, T, opaque(tid));
-                {
-                    const int w2off = lbase + (int)(W2_W * 4) + ((wave * 2) * 64 + f * 16) * 1024;
-                    const int nxt = f < 3 ? lbase + (int)(W1_W * 4) + ((f + 1) * 16 + wave * 2) * 16 * 1024 : w2off;
-                    gemm_phase_h<2, 16, 0, TR>(acc_f, acc_ft, Hc + am(LDX), Hc + at(LDX), LDX, rsrc, voff, w2off, 64 * 1024, g_f, nxt,
-                                        f < 3 ? 16 * 1024 : 64 * 1024);
-                }
-                __syncthreads();
-                FH_STAMP(21 + 3 * f);
-            }
-            if (layer + 1 < L)
-                ring_prefetch<3>(g_qkv, rsrc, voff, lbase + (int)(LAYER_FLOATS * 4) + (int)(QKV_W * 4) + wave * 16 * 1024, 16 * 16 * 1024);
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {   // residual values first (as after the out-projection)
-                const int col = (wave * 2 + n) * 16 + l15;
-#pragma unroll
-                for (int r = 0; r < RBM; ++r)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) xr[n][r][e] = X[(r * 16 + lg * 4 + e) * LDX + col];
-#pragma unroll
-                for (int r = 0; r < RBT; ++r) xt[n][r] = X[(TAIL0 + 4 * r + lg) * LDX + col];
-            }
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const int col = (wave * 2 + n) * 16 + l15;
-                const float bv = bv2[n];
-                    const int hl = LIVE ? opaque(lane) : lane, hlg = LIVE ? hl >> 4 : lg, hcol = LIVE ? (wave * 2 + n) * 16 + (hl & 15) : col;   // (LIVE: the hash indices are formed here, not hoisted out of the layer loop and spilled)
-#pragma unroll
-                for (int r = 0; r < RBM; ++r)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = acc_f[r][n][e] + bv;
-                        if (DR && tr.thresh)
-                            v = tip_drop_hash_k(dk3, (grow0 + r * 16 + hlg * 4 + e) * D + hcol) >= tr.thresh ? v * tr.scale : 0.f;
-                        X[(r * 16 + lg * 4 + e) * LDX + col] = xr[n][r][e] + v;
-                    }
-#pragma unroll
-                for (int r = 0; r < RBT; ++r) {
-                    float v = tail_reduce(acc_ft[r][n], lg) + bv;
-                    if (DR && tr.thresh)
-                        v = tip_drop_hash_k(dk3, (grow0 + TAIL0 + 4 * r + hlg) * D + hcol) >= tr.thresh ? v * tr.scale : 0.f;
-                    X[(TAIL0 + 4 * r + lg) * LDX + col] = xt[n][r] + v;
-                }
-            }
-            __syncthreads();
-            FH_STAMP(31);
-            if (TR)
-                layernorm_rows16<fz::TMAX, fz::LDX, true>(X, LW + G2, LW + BE2, wave, opaque(lane), svl + (size_t)tr.z2 * 64 + grow0 * D,
-                                                          svl + (size_t)tr.st2 * 64 + grow0 * 2, svl + (size_t)tr.xo * 64 + grow0 * D, T);
-            else
-                layernorm_rows16<fz::TMAX, fz::LDX>(X, LW + G2, LW + BE2, wave, lane);
-            __syncthreads();
-            FH_STAMP(32);
-        }
-        { const int layer = -1; FH_STAMP(40); }
-        // ---- RNN input projection: IH = X W_ih^T + (b_ih + b_hh), rows 0..T-1 -> HBM -------------------------------------
-        if (ih_out) {
-            f32x4 acc[RBM][4], acct[RBT][4];
-            zero_acc_h<4>(acc, acct);
-            const int isoff = ih_off_b + (wave * 4) * 16 * 1024;
-            WRing<4> g_ih;
-            ring_prefetch<4>(g_ih, rsrc, voff, isoff, 16 * 1024);
-            // Round 3: the 16-row blocks with SWAPPED operands — transposed accumulators, (columns 16 n + 4 lg + e, row 16 r + l15): a
-            // lane stores four consecutive columns of one row with ONE 16-byte store instead of four scattered 4-byte ones (the
-            // store tail is issue-bound: 32 -> 8 store instructions per wave for rows 0-31).  Same products, same sums.
-            gemm_phase_h<4, 16, 4, TR>(acc, acct, X + am(LDX), X + at(LDX), LDX, rsrc, voff, isoff, 16 * 1024, g_ih, isoff, 16 * 1024);
-            // This window's IH rows as a buffer of T rows: the stores of the pad rows are dropped by the range check, not by a branch
-            // around each store.  The biases of all four column blocks are requested BEFORE the first store: loaded inside the loop, each
-            // block's bias load sat behind the previous block's stores (the optimiser may not hoist a load over a store it cannot prove
-            // disjoint) — four exposed L2 round trips at the end of every window.
-            const __amdgpu_buffer_rsrc_t io_rs = __builtin_amdgcn_make_buffer_rsrc(ih_out + (size_t)win * T * R, 0, T * R * 4, 0x00020000);
-            // (opaque lane index: the store offsets are formed here, not hoisted to the top of the kernel and carried in scratch)
-            const int lo = opaque(lane), l15o = lo & 15, lgo = lo >> 4;
-            float bvs[4];
-            f32x4 bv4s[4];
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                bvs[n] = wts[ih_off_b / 4 + R * D + (wave * 4 + n) * 16 + l15o];
-                bv4s[n] = *reinterpret_cast<const f32x4*>(wts + ih_off_b / 4 + R * D + (wave * 4 + n) * 16 + lgo * 4);
-            }
-#pragma unroll
-            for (int n = 0; n < 4; ++n) {
-                const int col = (wave * 4 + n) * 16 + l15o;
-#pragma unroll
-                for (int r = 0; r < RBM; ++r) {
-                    const int row = r * 16 + l15o;
-                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, acc[r][n] + bv4s[n]), io_rs, (row * R + (wave * 4 + n) * 16 + lgo * 4) * 4, 0, 0);
-                }
-#pragma unroll
-                for (int r = 0; r < RBT; ++r) {
-                    const float v = tail_reduce(acct[r][n], lg) + bvs[n];
-                    const int row = TAIL0 + 4 * r + lgo;
-                    __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), io_rs, (row * R + col) * 4, 0, 0);
-                }
-            }
-        }
-        if (hall_sentinel) {
-            uint4* hp = reinterpret_cast<uint4*>(hall_sentinel + (size_t)win * T * R);
-            for (int i = opaque(tid); i < T * (R / 4); i += THREADS) hp[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
-        }
-        if (xout) {
-            float* out = xout + (size_t)win * T * D;
-            for (int i = tid; i < T * (D / 4); i += THREADS) {
-                const int r = i / (D / 4), c4 = i - r * (D / 4);
-                *reinterpret_cast<float4*>(out + (size_t)r * D + c4 * 4) = *reinterpret_cast<const float4*>(X + r * LDX + c4 * 4);
-            }
-        }
-        __syncthreads();
-        { const int layer = -1; FH_STAMP(41); }
-        if (TRACE && tid == 0 && blockIdx.x < 1024) g_fh_wg[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-    }
+    using Ctl = FhGridStride;
+    const Ctl ctl{};
+#include "tip_fused_h_body.inc"
 }
 #undef FH_STAMP
 
@@ -1132,7 +381,9 @@ hipError_t launch_fused_live_h(const Dims& d, const float* fused_w, const float*
 
 }  // namespace tip
 extern "C" int tip_debug_read_fh_wg(unsigned long long* out, int n) {
-    if (!out || n < 0 || n > 2048) return -1;
+    if (!out || n < 0 || n > 2048 + 5 * 1024) return -1;
+    if (n > 2048 && tip::read_round_wg(out + 2048, n - 2048) != hipSuccess) return -5;   // the one-launch round's table behind this one
+    if (n > 2048) n = 2048;
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(tip::g_fh_wg), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -5;
 }
 extern "C" int tip_debug_read_fh_trace(unsigned long long* out, int n) {

@@ -239,6 +239,9 @@ struct MeasureSwitches {
 const MeasureSwitches& measure_switches();   // tip_schedule.hip
 
 // ---- the forward's schedule (tip_schedule.hip): which plan(s) a batch takes.  Pure host arithmetic, no HIP call ----
+// TIP_OPT_NO_ROUND_LAUNCH of a new handle: 0 — the one-launch round (tip_round.hip) is taken where the schedule allows it: its slowest
+// of five benchmark runs beat the three launches' fastest in one lease (profiles/round/ab.txt)
+constexpr int kNoRoundLaunchDefault = 0;
 struct ScheduleIn {
     const Dims& d;
     int B, T;
@@ -247,6 +250,7 @@ struct ScheduleIn {
     bool demoted;                       // TIP_OPT_DEMOTED
     bool reuse_full;                    // tip_forward_reuse on full windows: ONE sequence on the two-window encoder's ring-reading form
     size_t workspace_bytes;             // the caller's buffer: a part that would not fit its own carve-up is not split off
+    bool no_round_launch = kNoRoundLaunchDefault != 0;   // TIP_OPT_NO_ROUND_LAUNCH
 };
 struct SchedPart {
     int first, count;   // windows [first, first + count) of the batch
@@ -259,6 +263,8 @@ struct Schedule {
     SchedPart part[2];
     bool shared_tail;   // 2 parts in ONE launch sequence: two encoders, then one recurrence + one output projection over all B windows;
                         // clear: every part is a launch sequence of its own over the same workspace
+    bool round_launch;  // the whole batch is ONE round on the hybrid encoder and runs as ONE launch (forward_round_kernel, tip_round.hip):
+                        // encoder, recurrence and (T = 40) projection as phases of the same workgroups
 };
 Schedule schedule_forward(const ScheduleIn& in);
 
@@ -411,6 +417,7 @@ struct tip_handle {
     unsigned long long flow_epoch = 0;   // launches of lat_flow_kernel so far (+ a per-handle base): stamps the completion flags of a launch
     int demoted = 0;                // TIP_OPT_DEMOTED: set by tip_demote after a lost hand-off: AUTO then avoids every cooperating kernel
     int no_flow = 0;                // TIP_OPT_NO_FLOW: the few-stream plan never takes its one-launch form (launch chain for every B)
+    int no_round_launch = tip::kNoRoundLaunchDefault;   // TIP_OPT_NO_ROUND_LAUNCH: one round on the hybrid encoder stays three launches
     tip::Guard guard() const { return tip::Guard{err_dev, fault_inject}; }
 };
 
@@ -601,6 +608,17 @@ hipError_t launch_latency_head(const float* A, long long lda, const float* wfrag
 hipError_t read_spin_timeouts_general(unsigned* out);
 hipError_t read_spin_timeouts_latency(unsigned* out);
 hipError_t read_spin_timeouts_fused2(unsigned* out);
+hipError_t read_spin_timeouts_round(unsigned* out);
+hipError_t read_round_wg(unsigned long long* out, int n);   // measurement: forward_round_kernel's per-workgroup stamps (n <= 5120)
+
+// ---- one round as ONE launch (tip_round.hip): encoder, recurrence and projection as phases of the same workgroups ----
+// the shapes the form serves (pure arithmetic: the schedule asks it too)
+bool round_launch_shape(const Dims& d, int B, int T, int num_cus);
+// head: 0 = the caller launches the projection, 1 = full output, 2 = last rows (1 and 2: T = 40 only).  hipErrorInvalidValue: not such a
+// shape; hipErrorCooperativeLaunchTooLarge: the grid would not be co-resident — the caller launches the three kernels in both cases.
+hipError_t launch_forward_round(const Dims& d, const float* fused_w, const float* x_imu, const float* x_s, const float* keep_mask,
+                                float keep_scale, float* ih, float* hall, unsigned* flags, const float* whh_frag, const float* out_frag,
+                                const float* out_bias, float* y, int B, int T, int head, int num_cus, const Guard& gd, hipStream_t s);
 
 // ---- two-window fused encoder (tip_fused2.hip): 80 rows = 5 MFMA row blocks, no padding; for >= 2 windows per CU ----
 bool fused2_supported(const Dims& d, int T);

@@ -33,6 +33,9 @@ namespace cost {
 constexpr long long kHybridRound = 527;       // one-window hybrid encoder, one round of #CUs windows
 constexpr long long kTwoWindowRound = 1049;   // two-window encoder, one round of 2 x #CUs windows
 constexpr long long kTailRound = 96;          // recurrence + output projection per round of #CUs windows
+constexpr long long kRoundStep = 615;         // ONE round (B = #CUs) as one launch (tip_round.hip; profiles/round/ab.txt: 0.613-0.616 ms against
+                                              // 0.621-0.623 for the three launches), against kHybridRound + kTailRound
+static_assert(kRoundStep <= kHybridRound + kTailRound, "the one-launch round is never taken where it is slower than the three launches");
 // profiles/r05/f1s_parts.txt (whole forward / its encoder stage; the staircase as a whole: profiles/pool/auto_sweep.txt):
 constexpr long long kSplitQuad = 305, kSplitQuadEncoder = 232;   // window-split plan, one window on four CUs (up to #CUs / 4 windows)
 constexpr long long kSplitPair = 452, kSplitPairEncoder = 375;   // ... on two CUs (up to #CUs / 2)
@@ -162,6 +165,11 @@ Schedule schedule_forward(const ScheduleIn& in) {
     }
     sc.nparts = 1;
     part(0, 0, B, resolve_rnn_cluster(in, B));
+    // ONE round on the hybrid encoder as ONE launch (tip_round.hip): the whole batch is at most one window per CU of the whole device,
+    // the recurrence is the four-row one, the handle is not demoted (every workgroup of that launch waits for others) and
+    // TIP_OPT_NO_ROUND_LAUNCH is clear.  Measured (profiles/round/ab.txt, B = 256, T = 40): cost::kRoundStep.
+    sc.round_launch = sc.status == TIP_OK && !in.no_round_launch && !in.demoted && !in.reuse_full && sc.part[0].plan == TIP_PLAN_FUSEDH &&
+                      sc.part[0].rnn_cluster == kRnnRows4 && cus == in.num_cus && round_launch_shape(d, B, T, cus);
     return sc;
 }
 
@@ -170,7 +178,8 @@ Schedule schedule_forward(const ScheduleIn& in) {
 extern "C" int tip_debug_schedule(const tip_handle* h, int B, int T, int cus, int reuse_full, size_t workspace_bytes, int* out, int cap) {
     if (!h || B < 1 || T < 1 || !out || cap < 9) return TIP_ERR_INVALID_ARG;
     const tip::Schedule sc = tip::schedule_forward(tip::ScheduleIn{h->d, B, T, cus > 0 ? cus : h->num_cus, h->num_cus, h->plan, h->rnn_cluster,
-                                                                   h->f1s_parts, h->demoted != 0, reuse_full != 0, workspace_bytes});
+                                                                   h->f1s_parts, h->demoted != 0, reuse_full != 0, workspace_bytes,
+                                                                   h->no_round_launch != 0});
     int* o = out;
     *o++ = sc.nparts;
     *o++ = sc.shared_tail ? 1 : 0;
@@ -178,5 +187,6 @@ extern "C" int tip_debug_schedule(const tip_handle* h, int B, int T, int cus, in
     for (const tip::SchedPart& p : sc.part) {
         *o++ = p.first; *o++ = p.count; *o++ = p.plan;
     }
+    if (cap >= 10) *o++ = sc.round_launch ? 1 : 0;
     return sc.status;
 }

@@ -29,6 +29,7 @@ TIP_SAVED_QKV, TIP_SAVED_ATT, TIP_SAVED_X1, TIP_SAVED_HID, TIP_SAVED_XOUT, TIP_S
 TIP_STREAM_FRAME_AUTO = -1   # tip_stream_ingest / tip_stream_consume: continue from the counter in the state buffer (HIP graphs)
 TIP_OPT_PLAN, TIP_OPT_PROFILE, TIP_OPT_RNN_CLUSTER, TIP_OPT_FAULT_INJECT, TIP_OPT_FUSE_HEAD = 1, 2, 3, 4, 5
 TIP_OPT_AUTO_DEMOTE, TIP_OPT_DEMOTED, TIP_OPT_F1S_PARTS = 7, 8, 9   # 6: retired
+TIP_OPT_NO_ROUND_LAUNCH = 12   # 1: one round on the hybrid encoder stays three launches; 0: encoder, recurrence and projection as ONE launch
 TIP_OPT_NO_FLOW, TIP_OPT_HANDOFF_KIND = 10, 11   # few-stream plan without its one-launch form; (read only) 0 none / 1 a wait gave up / 2 one-launch placement only
 TIP_ABI_VERSION = 5
 TIP_RNN_CLUSTER_ROWS4 = 0x44   # TIP_OPT_RNN_CLUSTER value: 4-window tiles on 4-workgroup clusters (AUTO's choice for rnn_hidden 512)
@@ -369,6 +370,13 @@ class Handle:
         self._check(self.lib.tip_debug_schedule(self._h, B, T, cus, 1 if reuse_full else 0, wsb, out, 9))
         return {"nparts": out[0], "shared_tail": bool(out[1]), "rnn_cluster": out[2],
                 "parts": [tuple(out[3 + 3 * i: 6 + 3 * i]) for i in range(out[0])]}
+
+    def round_launch(self, B: int, T: int, cus: int = 0) -> bool:
+        """tip_debug_schedule's tenth word: would forward() run these B windows as the one-launch round (encoder, recurrence and projection
+        as phases of one kernel; TIP_OPT_NO_ROUND_LAUNCH = 0, one window per CU at most on the hybrid encoder)?"""
+        out = (ctypes.c_int * 10)()
+        self._check(self.lib.tip_debug_schedule(self._h, B, T, cus, 0, self.workspace_bytes(B, T), out, 10))
+        return bool(out[9])
 
     def max_batch(self, T: int, fp64: bool = False) -> int:
         """Largest batch one forward / forward_f64 call serves at window length T (the host chunks beyond it)."""
