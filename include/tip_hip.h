@@ -661,6 +661,86 @@ TIP_API int tip_resample_rows(const float* packets /* [n_in,42] */, const double
                       const long long* out_offsets /* [n_seq+1] */, long long n_out, int n_seq, double delay, double max_hold, int mode,
                       int depth, float* packets_out /* [n_out,42] */, unsigned char* flags /* [n_out] */, tip_stream_t stream);
 
+/* ---- clock sync and predicted ticks: in front of the resampler above, for hubs that stamp packets with a clock of their own (it starts
+ *      at power-on and drifts by tens of ppm) while the server knows only arrival times, which carry the network's jitter; and a third
+ *      emit rule that gives a packet AT the tick with delay 0, so that neither a sensor period of delay (SLERP) nor a packet of
+ *      varying age (HOLD with delay 0) has to be chosen.  The reference keeps no stamps (live_demo_new.py:82-115).  Every time and every
+ *      decision is fp64, the library is built with -ffp-contract=off, and the statements below give the same bits in numpy.
+ *      CLOCK.  `state` is a caller-owned device buffer of tip_clock_state_bytes() (8-byte aligned), 32 bytes per slot, separate from the
+ *      resampler's: double theta; double s_prev; int count; int rejected; 8 bytes reserved.  A reset block is all zero bits.
+ *      The model: arrival a = s + theta + d, s the sensor's stamp, d >= 0 the network's delay, theta an offset that drifts by at most
+ *      `leak` seconds per second.  The estimate is a lower envelope of a - s that may rise only as fast as a clock can drift and fall
+ *      only as fast as keeps mapped times strictly increasing.  One slot, its arrivals (s, a) in array order, leak >= 0, 0 <= slew < 1:
+ *          if s or a is not finite, or (count > 0 and s <= s_prev):   rejected += 1; mapped = NaN
+ *          else:
+ *              o = a - s
+ *              if count == 0:   theta = o
+ *              else:
+ *                  d  = s - s_prev
+ *                  up = theta + leak * d
+ *                  dn = theta - slew * d
+ *                  th = o if o < up else up
+ *                  theta = th if th > dn else dn
+ *              s_prev = s; count += 1; mapped = s + theta
+ *      (TIP_CLOCK_LEAK, 200 ppm, is above any crystal; with TIP_CLOCK_SLEW 0.5 two mapped times are at least half as far apart as
+ *      their stamps.)  A NaN mapped time is what tip_resample_push drops and counts.
+ *      tip_clock_reset: the blocks of the listed slots, or of all n when slots is null (required once), to zero.
+ *      tip_clock_get: theta_out[count] (device fp64) and counts_out[count, 2] (device int) = count | rejected of the listed slots; a
+ *        slot outside [0, n) leaves its entries as they were.
+ *      tip_clock_map: m arrivals, slots[m], stamps[m], arrivals[m] -> times_out[m] (device arrays).  One wave per slot scans the list 64
+ *        entries at a time, as tip_resample_push does (and at the same n_slots x m reads of slots[]); times_out[j] of an arrival whose
+ *        slot is outside [0, n) is not written.
+ *      tip_clock_push: tip_clock_map and tip_resample_push in ONE launch: the same scan maps the stamp and inserts the packet at the
+ *        mapped time.  Ring, counters and clock blocks are bit for bit what the two launches leave.  times_out may be null.
+ *      tip_clock_rows: n_seq ragged recorded sequences in one launch, sequence j rows offsets[j] .. offsets[j + 1] - 1 of stamps[n_in]
+ *        and arrivals[n_in] (offsets clamped to [0, n_in] and to ascending order), each from a reset block: bit for bit what the live
+ *        rule gives when fed the sequence in any chunking.  The rule is a sequential scan: one wave per sequence loads 64 pairs at a
+ *        time and steps them out of registers, so a launch takes as many dependent steps as its longest sequence has rows.
+ *      PREDICTED TICKS.  tip_resample_emit and tip_resample_rows keep their two modes; prediction has entries of its own, with
+ *      tip_resample_emit's and tip_resample_rows' arguments, max_predict (seconds, finite, >= 0) in the place of mode.  With
+ *      tau = t - delay, the ring's stamps s_0 < ... < s_last and s_prev the one before s_last:
+ *          fewer than 2 packets, or not (tau > s_last)                             the SLERP rule above: rows, flags and bits unchanged
+ *          tau > s_last: h = tau - s_last, b = s_last - s_prev;
+ *            h <= max_predict and h <= TIP_PREDICT_SPAN * b and (max_hold < 0 or b <= max_hold)
+ *                                                                                  predicted at u = (tau - s_prev) / b > 1, fp64    5
+ *            otherwise                                                             the SLERP rule above (the newest packet held, or stale)
+ *        max_predict = 0 predicts no row: every row is then bit for bit SLERP's.
+ *      A predicted sensor, a the packet at s_prev and b the one at s_last: the quaternion statements of the interpolation above with this
+ *        u — the shorter arc, w0 = sin((1 - u) th) / sin(th) (negative), w1 = sin(u th) / sin(th), q = w0 qa + w1 qb normalised —
+ *        which is the geodesic through the two packets continued past the newer one: a constant angular rate.  One statement
+ *        differs: above d = 1 - 1e-6, where acos cannot tell arcs apart, th = 2 asin(|qb - qa| / 2) (fp64, the chord's four squares
+ *        summed left to right) and the same two sines, not the linear weights, whose error of u (u^2 - 1) th^3 / 6 is a rate error
+ *        once u is past 1; the weights are 1 - u and u only below th = 1e-5.  The result is unit, and its sign is the earlier packet's while u th < pi / 2 (q . qa = cos(u th)).
+ *        The acceleration is HELD in the global frame, never extrapolated (that would amplify the sensor's noise): gb_r = Rb[r,0] b4 +
+ *        Rb[r,1] b5 + Rb[r,2] b6, out[4 + c] = Rq[0,c] gb_0 + Rq[1,c] gb_1 + Rq[2,c] gb_2.  Only the newer packet's acceleration is
+ *        read: a NaN in the older one's does not reach the row.  A zero or non-finite quaternion in either packet, or a q without a
+ *        rotation, gives the sensor's seven columns NaN; a NaN in the newer packet's acceleration gives its three columns NaN.
+ *      Null buffers, misaligned state, negative counts, a depth outside 2 .. 64, a leak, delay or max_predict that is negative or not
+ *      finite, a slew outside [0, 1), a NaN max_hold return TIP_ERR_INVALID_ARG before any launch; n_slots = 0, m = 0, count = 0,
+ *      n_in = 0, n_out = 0 launch nothing. */
+#define TIP_CLOCK_LEAK    2e-4
+#define TIP_CLOCK_SLEW    0.5
+#define TIP_PREDICT_SPAN  2.0
+#define TIP_RESAMPLE_PREDICTED 5
+TIP_API int tip_clock_state_bytes(int n_slots, size_t* bytes);
+TIP_API int tip_clock_reset(void* state, int n_slots, const int* slots /* or null: all */, int count, tip_stream_t stream);
+TIP_API int tip_clock_get(const void* state, int n_slots, const int* slots, int count, double* theta_out /* [count] */,
+                  int* counts_out /* [count,2] */, tip_stream_t stream);
+TIP_API int tip_clock_map(void* state, int n_slots, const int* slots /* [m] */, const double* stamps /* [m] */,
+                  const double* arrivals /* [m] */, int m, double leak, double slew, double* times_out /* [m] */, tip_stream_t stream);
+TIP_API int tip_clock_push(void* resample_state, void* clock_state, int n_slots, int depth, const float* packets /* [m,42] */,
+                   const int* slots /* [m] */, const double* stamps /* [m] */, const double* arrivals /* [m] */, int m, double leak,
+                   double slew, double* times_out /* [m] or null */, tip_stream_t stream);
+TIP_API int tip_clock_rows(const double* stamps /* [n_in] */, const double* arrivals /* [n_in] */, const long long* offsets /* [n_seq+1] */,
+                   long long n_in, int n_seq, double leak, double slew, double* times_out /* [n_in] */, tip_stream_t stream);
+TIP_API int tip_predict_emit(void* state, int n_slots, int depth, const double* t /* device [n] */, double delay, double max_hold,
+                     double max_predict, float* packets_out /* [n,42] */, unsigned char* flags /* [n] */, tip_stream_t stream);
+TIP_API int tip_predict_rows(const float* packets /* [n_in,42] */, const double* stamps /* [n_in] */,
+                     const long long* in_offsets /* [n_seq+1] */, long long n_in, const double* t_out /* [n_out] */,
+                     const long long* out_offsets /* [n_seq+1] */, long long n_out, int n_seq, double delay, double max_hold,
+                     double max_predict, int depth, float* packets_out /* [n_out,42] */, unsigned char* flags /* [n_out] */,
+                     tip_stream_t stream);
+
 /* ---- kinematics: forward kinematics of the character, the root track with its SBP correction, and the evaluation script's seven
  *      metrics — what the reference does through PyBullet behind RTRunnerMin.step (real_time_runner_minimal.py:159-194;
  *      data_utils.py:262-306, 397-412, 473-548) and in offline_testing_simple.py --compare_gt (:422-453; data_utils.py:314-391).

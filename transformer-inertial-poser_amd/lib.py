@@ -39,6 +39,8 @@ TIP_ERR_UNSUPPORTED_CONFIG = -2
 TIP_LOSS_Q, TIP_LOSS_C, TIP_LOSS_J, TIP_LOSS_STATS = 1, 2, 4, 16
 TIP_SENSOR_HEADING, TIP_SENSOR_TPOSE = 1, 2   # tip_sensor_begin: which hold starts
 TIP_RESAMPLE_HOLD, TIP_RESAMPLE_SLERP = 0, 1   # tip_resample_emit / tip_resample_rows: mode
+TIP_RESAMPLE_PREDICTED = 5                     # tip_predict_emit / tip_predict_rows: the flag of a predicted row
+TIP_CLOCK_LEAK, TIP_CLOCK_SLEW, TIP_PREDICT_SPAN = 2e-4, 0.5, 2.0
 
 # every symbol include/tip_hip.h declares (tests check that the .so exports exactly these + the hooks of tip_hip_debug.h)
 EXPORTS = (
@@ -59,6 +61,8 @@ EXPORTS = (
     "tip_fill_real", "tip_fill_rows", "tip_fill_state_bytes", "tip_fill_reset", "tip_fill_live", "tip_fill_get", "tip_fill_packets",
     "tip_resample_tile", "tip_resample_state_bytes", "tip_resample_reset", "tip_resample_push", "tip_resample_emit", "tip_resample_get",
     "tip_resample_rows",
+    "tip_clock_state_bytes", "tip_clock_reset", "tip_clock_get", "tip_clock_map", "tip_clock_push", "tip_clock_rows",
+    "tip_predict_emit", "tip_predict_rows",
     "tip_kin_skel_bytes", "tip_kin_carry_bytes", "tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_kin_metrics",
     "tip_terrain_state_bytes", "tip_terrain_reset", "tip_terrain_track",
     "tip_kin_fk_scaled", "tip_kin_track_reset_scaled", "tip_kin_track_scaled", "tip_terrain_reset_scaled", "tip_terrain_track_scaled",
@@ -222,6 +226,15 @@ def load() -> ctypes.CDLL:
     lib.tip_resample_emit.argtypes = [vp, i32, i32, vp, f64, f64, i32, vp, vp, vp]
     lib.tip_resample_get.argtypes = [vp, i32, i32, vp, i32, vp, vp]
     lib.tip_resample_rows.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.c_longlong, i32, f64, f64, i32, i32, vp, vp, vp]
+    # clock sync and predicted ticks (csrc/tip_clock.hip): leak, slew and max_predict are fp64; max_predict stands where mode stood
+    lib.tip_clock_state_bytes.argtypes = [i32, ctypes.POINTER(sz)]
+    lib.tip_clock_reset.argtypes = [vp, i32, vp, i32, vp]
+    lib.tip_clock_get.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    lib.tip_clock_map.argtypes = [vp, i32, vp, vp, vp, i32, f64, f64, vp, vp]
+    lib.tip_clock_push.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32, f64, f64, vp, vp]
+    lib.tip_clock_rows.argtypes = [vp, vp, vp, ctypes.c_longlong, i32, f64, f64, vp, vp]
+    lib.tip_predict_emit.argtypes = [vp, i32, i32, vp, f64, f64, f64, vp, vp, vp]
+    lib.tip_predict_rows.argtypes = [vp, vp, vp, ctypes.c_longlong, vp, vp, ctypes.c_longlong, i32, f64, f64, f64, i32, vp, vp, vp]
     # kinematics (csrc/tip_kin.hip): the skeleton table, then what the header lists, then the stream
     lib.tip_kin_skel_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_kin_carry_bytes.argtypes = [i32, ctypes.POINTER(sz)]

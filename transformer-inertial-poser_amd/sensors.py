@@ -34,6 +34,17 @@ is the [n, 42] every method above and every engine's step_packets take; resample
     rs = PacketResampler(n, "cuda", mode="slerp", delay=1 / 100, max_hold=0.1)      # 100 Hz sensors: one period of delay
     rs.push(packets, slots, times)                                                  # whatever arrived since the last tick
     out = engine.step_packets(front, rs.emit(t))                                    # t: the tick, a number or [n]; rs.flags says how
+
+Clock sync and predicted ticks (csrc/tip_clock.hip; include/tip_hip.h, "clock sync and predicted ticks"): a hub stamps its packets
+with a clock of its own, and the server knows only when they arrive.  ClockSync keeps per slot the offset between the two as a lower
+envelope of arrival - stamp; push(..., arrivals=, sync=) maps and inserts in one launch; mode "predict" continues the orientation past
+the newest packet at the rate of the newest two, so that delay 0 gives a packet AT the tick; sync_sequences and
+resample_sequences(mode="predict") are the same for recorded sessions.
+
+    clk = ClockSync(n, "cuda")
+    rs = PacketResampler(n, "cuda", mode="predict", delay=0.0, max_hold=0.1)        # max_predict: 25 ms unless given
+    rs.push(packets, slots, sensor_stamps, arrivals=arrival_times, sync=clk)        # stamps on each hub's clock, arrivals on the server's
+    out = engine.step_packets(front, rs.emit(t))
 """
 from __future__ import annotations
 
@@ -452,23 +463,26 @@ def transform_sequences(packets_list, tables, fill=False, max_acc=10.0, max_gap=
 
 
 # ---- timestamped packets: every wearer resampled to the tick grid ----------------------------------------------------------------------
-MODES = {"hold": _lib.TIP_RESAMPLE_HOLD, "slerp": _lib.TIP_RESAMPLE_SLERP}
+MODES = {"hold": _lib.TIP_RESAMPLE_HOLD, "slerp": _lib.TIP_RESAMPLE_SLERP, "predict": 2}
 # what emit says about a slot's row: interpolated; a packet held (copied bit for bit); NaN because the packet to hold is older than
-# max_hold; NaN because the ring is empty; NaN because t - delay is before the ring's oldest packet
+# max_hold; NaN because the ring is empty; NaN because t - delay is before the ring's oldest packet; continued past the newest packet
+# at the rate of the newest two (mode "predict" only)
 INTERPOLATED, HELD, STALE, EMPTY, EARLY = range(5)
+PREDICTED = _lib.TIP_RESAMPLE_PREDICTED
+MAX_PREDICT = 0.025                                              # mode "predict" without a max_predict: a tick and a half
 
 
 def _resample_rule(mode, delay, max_hold, depth, who):
     """(mode, delay, max_hold, depth) as the C ABI takes them; anything else is a ValueError in `who`'s name."""
-    if mode not in MODES:
-        raise ValueError(f"tip_amd.sensors.{who}: mode is \"slerp\" or \"hold\"; got {mode!r}")
+    if not isinstance(mode, str) or mode not in MODES:
+        raise ValueError(f"tip_amd.sensors.{who}: mode is \"slerp\", \"hold\" or \"predict\"; got {mode!r}")
     try:
         delay = float(delay)
     except (TypeError, ValueError):
         delay = float("nan")
     if not (delay >= 0.0 and np.isfinite(delay)):
-        raise ValueError(f"tip_amd.sensors.{who}: delay is the age of the emitted packet in seconds, a finite number >= 0 (nothing is "
-                         f"extrapolated past the newest packet); got {delay!r}")
+        raise ValueError(f"tip_amd.sensors.{who}: delay is the age of the emitted packet in seconds, a finite number >= 0 (a row past "
+                         f"the newest packet is mode \"predict\"'s with max_predict, never a negative delay); got {delay!r}")
     if max_hold is None:
         hold = -1.0
     else:
@@ -482,6 +496,40 @@ def _resample_rule(mode, delay, max_hold, depth, who):
     if isinstance(depth, bool) or not isinstance(depth, (int, np.integer)) or not 2 <= depth <= 64:
         raise ValueError(f"tip_amd.sensors.{who}: depth is the number of packets a slot keeps, an int in 2 .. 64; got {depth!r}")
     return MODES[mode], delay, hold, int(depth)
+
+
+def _predict_rule(mode, max_predict, who):
+    """max_predict as the C ABI takes it: MAX_PREDICT when mode "predict" names none; a ValueError with any other mode."""
+    if mode != "predict":
+        if max_predict is not None:
+            raise ValueError(f"tip_amd.sensors.{who}: max_predict is mode \"predict\"'s; mode {mode!r} predicts nothing")
+        return 0.0
+    if max_predict is None:
+        return MAX_PREDICT
+    try:
+        far = float(max_predict)
+    except (TypeError, ValueError):
+        far = float("nan")
+    if not (far >= 0.0 and np.isfinite(far)):
+        raise ValueError(f"tip_amd.sensors.{who}: max_predict is how far past the newest packet a row may be predicted, a finite "
+                         f"number of seconds >= 0; got {max_predict!r}")
+    return far
+
+
+def _clock_rule(leak, slew, who):
+    """(leak, slew) of the clock rule as floats; anything else is a ValueError in `who`'s name."""
+    def number(v):
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            return float("nan")
+    lk, sl = number(leak), number(slew)
+    if not (lk >= 0.0 and np.isfinite(lk)):
+        raise ValueError(f"tip_amd.sensors.{who}: leak is the fastest drift the offset may follow upwards, a finite number of seconds "
+                         f"per second >= 0; got {leak!r}")
+    if not 0.0 <= sl < 1.0:
+        raise ValueError(f"tip_amd.sensors.{who}: slew is the share of a stamp interval the offset may fall by, in [0, 1); got {slew!r}")
+    return lk, sl
 
 
 def tick_times(t0, count, rate_hz=60.0):
@@ -525,21 +573,125 @@ def _tick_rule(rate_hz, delay, who):
     return rate, delay
 
 
+def _pinned_image(parts, device):
+    """Host tensors [(tensor, dtype)], each flat -> their device copies, sent up as ONE pinned image in ONE non-blocking copy.  The
+    parts are laid out in the order given: put the widest type first and every part stays aligned to its type."""
+    sizes = [int(t.numel()) * torch.empty((), dtype=d).element_size() for t, d in parts]
+    image = torch.empty(sum(sizes), dtype=torch.uint8).pin_memory()
+    at = 0
+    for (t, d), nb in zip(parts, sizes):
+        image[at: at + nb].view(d).copy_(t.reshape(-1))
+        at += nb
+    dev, out, at = image.to(device, non_blocking=True), [], 0
+    for (t, d), nb in zip(parts, sizes):
+        out.append(dev[at: at + nb].view(d))
+        at += nb
+    return out
+
+
+class ClockSync:
+    """n clock blocks on `device` (csrc/tip_clock.hip; include/tip_hip.h, "clock sync and predicted ticks"): per slot the offset
+    between a hub's own clock, which stamps the packets, and the server's, which only sees them arrive.  The estimate is a lower
+    envelope of arrival - stamp: it rises by at most `leak` seconds per second of stamps (a crystal's drift) and falls by at most `slew`
+    of a stamp interval, so that mapped times are strictly increasing.  map() gives the stamps on the server's clock, which is what
+    PacketResampler.push takes as times; push(..., arrivals=, sync=) does both in one launch.  No call synchronises."""
+
+    def __init__(self, n: int, device, *, leak: float = _lib.TIP_CLOCK_LEAK, slew: float = _lib.TIP_CLOCK_SLEW):
+        who = "ClockSync"
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+            raise ValueError(f"tip_amd.sensors.{who}: n is the number of slots, at least 1; got {n!r}")
+        self.n = int(n)
+        self.leak, self.slew = _clock_rule(leak, slew, who)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("tip_amd.sensors.ClockSync runs on an MI355X: give it the engine's device")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.lib = _lib.load()
+        nbytes = ctypes.c_size_t()
+        _lib.check(self.lib.tip_clock_state_bytes(self.n, ctypes.byref(nbytes)))
+        self.state = torch.empty(nbytes.value, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.tip_clock_reset(self.state.data_ptr(), self.n, None, 0, self._stream()))
+
+    def _stream(self):
+        return _lib.current_stream(self.device)
+
+    def _slots(self, slots, who):
+        return list(range(self.n)) if slots is None else slot_list(slots, self.n, f"sensors.ClockSync.{who}")
+
+    def map(self, slots, stamps, arrivals):
+        """m arrivals: slots [m], stamps [m] (the sensor's clock) and arrivals [m] (the server's), float64 seconds read as
+        PacketResampler.push reads its times -> the stamps on the server's clock, a CUDA float64 [m].  The arrivals of one slot are
+        taken in array order; one whose stamp or arrival time is not finite, or whose stamp is not above the slot's last, is counted
+        as rejected and maps to NaN, as does an arrival for a slot outside [0, n).  Host inputs go up in ONE non-blocking copy."""
+        who = "tip_amd.sensors.ClockSync.map"
+        sl, st, ar = torch.as_tensor(slots), _times_f64(stamps, f"{who}: stamps"), _times_f64(arrivals, f"{who}: arrivals")
+        m = int(sl.numel())
+        if sl.dim() != 1 or tuple(st.shape) != (m,) or tuple(ar.shape) != (m,):
+            raise ValueError(f"{who}: slots, stamps and arrivals are [m]; got {tuple(sl.shape)}, {tuple(st.shape)}, {tuple(ar.shape)}")
+        if m and (sl.dtype.is_floating_point or sl.dtype == torch.bool):
+            raise ValueError(f"{who}: slots are integers; got {sl.dtype}")
+        out = torch.full((m,), float("nan"), dtype=torch.float64, device=self.device)
+        if m == 0:
+            return out
+        with torch.cuda.device(self.device):
+            if not (sl.is_cuda or st.is_cuda or ar.is_cuda):
+                s, a, l = _pinned_image([(st, torch.float64), (ar, torch.float64), (sl.to(torch.int32), torch.int32)], self.device)
+            else:
+                l, s, a = (_to(t.to(d), self.device).contiguous() for t, d in zip((sl, st, ar), (torch.int32, torch.float64, torch.float64)))
+            _lib.check(self.lib.tip_clock_map(self.state.data_ptr(), self.n, l.data_ptr(), s.data_ptr(), a.data_ptr(), m, self.leak,
+                                               self.slew, out.data_ptr(), self._stream()))
+        return out
+
+    def reset(self, slots=None):
+        """Forget the offsets of the listed slots (None: all): a slot whose hub restarted, or that takes a new wearer."""
+        idx = self._slots(slots, "reset")
+        if not idx:
+            return
+        with torch.cuda.device(self.device):
+            sl = _to(torch.tensor(idx, dtype=torch.int32), self.device)
+            _lib.check(self.lib.tip_clock_reset(self.state.data_ptr(), self.n, sl.data_ptr(), len(idx), self._stream()))
+
+    def _get(self, slots, who):
+        idx = self._slots(slots, who)
+        theta = torch.zeros(len(idx), dtype=torch.float64, device=self.device)
+        counts = torch.zeros((len(idx), 2), dtype=torch.int32, device=self.device)
+        if idx:
+            with torch.cuda.device(self.device):
+                sl = _to(torch.tensor(idx, dtype=torch.int32), self.device)
+                _lib.check(self.lib.tip_clock_get(self.state.data_ptr(), self.n, sl.data_ptr(), len(idx), theta.data_ptr(),
+                                                   counts.data_ptr(), self._stream()))
+        return theta, counts
+
+    def offsets(self, slots=None):
+        """The offset estimates (server's clock minus sensor's, seconds) of the listed slots (None: all): a CUDA float64 tensor."""
+        return self._get(slots, "offsets")[0]
+
+    def counts(self, slots=None):
+        """(count, rejected) of the listed slots (None: all), two CUDA int32 tensors: arrivals taken, arrivals refused."""
+        c = self._get(slots, "counts")[1]
+        return c[:, 0], c[:, 1]
+
+
 class PacketResampler:
     """n rings of the last `depth` packets with their fp64 stamps on `device`, and the per-tick launch that gives every slot its
     packet at the tick (csrc/tip_resample.hip).  mode "hold": the newest packet not after t - delay, the demo's rule at delay 0;
     "slerp": interpolated between the two packets around t - delay (quaternions on the shorter arc, accelerations linearly in the
-    global frame), which needs a delay of about one sensor period to have a later packet.  max_hold (seconds; None: no limit): a packet
-    older than that is not held and nothing is interpolated across a longer gap — the slot gets a NaN row, which fill=True of the front
-    end fills or the engines' NaN contract takes.  No call synchronises; everything runs on the current stream."""
+    global frame), which needs a delay of about one sensor period to have a later packet; "predict" (csrc/tip_clock.hip): "slerp"
+    wherever t - delay has a later packet, and past the newest packet — delay 0 — the orientation continued at the angular rate of the
+    newest two packets, by at most max_predict seconds and twice their spacing, the newest acceleration held in the global frame.
+    max_hold (seconds; None: no limit): a packet older than that is not held and nothing is interpolated or predicted across a
+    longer gap — the slot gets a NaN row, which fill=True of the front end fills or the engines' NaN contract takes.  No call synchronises; everything runs on the current stream."""
 
-    def __init__(self, n: int, device, *, mode: str = "slerp", delay: float = 0.0, max_hold=None, depth: int = 8):
+    def __init__(self, n: int, device, *, mode: str = "slerp", delay: float = 0.0, max_hold=None, depth: int = 8, max_predict=None):
         who = "PacketResampler"
         if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
             raise ValueError(f"tip_amd.sensors.{who}: n is the number of slots, at least 1; got {n!r}")
         self.n = int(n)
         self.mode_name = mode
         self.mode, self.delay, self.max_hold, self.depth = _resample_rule(mode, delay, max_hold, depth, who)
+        self.max_predict = _predict_rule(mode, max_predict, who)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("tip_amd.sensors.PacketResampler runs on an MI355X: give it the engine's device")
@@ -560,22 +712,46 @@ class PacketResampler:
     def _slots(self, slots, who):
         return list(range(self.n)) if slots is None else slot_list(slots, self.n, f"sensors.PacketResampler.{who}")
 
-    def push(self, packets, slots, times):
+    def push(self, packets, slots, times, *, arrivals=None, sync=None):
         """m arrivals: packets [m, 42] float32, slots [m] (an arrival for a slot outside [0, n) is skipped), times [m] float64 seconds.
         The arrivals of one slot are taken in array order; one whose stamp is not finite or not above the slot's newest is dropped and
         counted.  Host inputs go up in ONE non-blocking copy from pinned memory; CUDA tensors are used where they lie.  times that are
         no tensor (lists, numpy arrays) are read as float64 whatever they hold; a tensor of a narrower float type is refused: at an
-        epoch-sized stamp float32 has already lost the packet's time."""
+        epoch-sized stamp float32 has already lost the packet's time.
+        arrivals [m] and sync (a ClockSync of this pool's n, on this device), both or neither: times are then the SENSOR's stamps,
+        arrivals the server's arrival times, and one launch maps every stamp through sync and inserts the packet at the mapped time —
+        what sync.map followed by push leaves, bit for bit; an arrival that sync rejects is dropped and counted here too."""
         who = "tip_amd.sensors.PacketResampler.push"
+        if (arrivals is None) != (sync is None):
+            raise ValueError(f"{who}: arrivals and sync come together (sensor stamps, arrival times and the ClockSync that maps them) "
+                             "or not at all")
         args = [torch.as_tensor(packets), torch.as_tensor(slots), _times_f64(times, f"{who}: times")]
         m = int(args[1].numel())
         if args[0].dim() != 2 or tuple(args[0].shape) != (m, PACKET) or args[1].dim() != 1 or tuple(args[2].shape) != (m,):
             raise ValueError(f"{who}: packets is [m, {PACKET}], slots [m] and times [m]; got {tuple(args[0].shape)}, "
                              f"{tuple(args[1].shape)}, {tuple(args[2].shape)}")
+        if sync is not None:
+            if not isinstance(sync, ClockSync) or sync.n != self.n or sync.device != self.device:
+                raise ValueError(f"{who}: sync is a ClockSync of {self.n} slots on {self.device}")
+            args.append(_times_f64(arrivals, f"{who}: arrivals"))
+            if tuple(args[3].shape) != (m,):
+                raise ValueError(f"{who}: arrivals is [m], one arrival time per packet; got {tuple(args[3].shape)} for m = {m}")
         if m == 0:
             return
         if args[1].dtype.is_floating_point or args[1].dtype == torch.bool:
             raise ValueError(f"{who}: slots are integers; got {args[1].dtype}")
+        if sync is not None:
+            with torch.cuda.device(self.device):
+                if not any(a.is_cuda for a in args):
+                    # times | arrivals | packets | slots in one pinned image: (8 + 8 + 168 + 4) m bytes, every part aligned to its type
+                    t, a, p, s = _pinned_image([(args[2], torch.float64), (args[3], torch.float64), (args[0].to(torch.float32), torch.float32),
+                                                (args[1].to(torch.int32), torch.int32)], self.device)
+                else:
+                    p, s, t, a = (_to(x.to(d), self.device).contiguous()
+                                  for x, d in zip(args, (torch.float32, torch.int32, torch.float64, torch.float64)))
+                _lib.check(self.lib.tip_clock_push(self.state.data_ptr(), sync.state.data_ptr(), self.n, self.depth, p.data_ptr(),
+                                                    s.data_ptr(), t.data_ptr(), a.data_ptr(), m, sync.leak, sync.slew, None, self._stream()))
+            return
         dtypes = (torch.float32, torch.int32, torch.float64)
         with torch.cuda.device(self.device):
             if not any(a.is_cuda for a in args):
@@ -593,7 +769,7 @@ class PacketResampler:
 
     def emit(self, t, out=None):
         """Every slot's packet at tick t -> a CUDA float32 [n, 42] (`out`, or a new tensor); `flags` [n] uint8 says how each row came
-        about (INTERPOLATED, HELD, STALE, EMPTY, EARLY; the last three are NaN rows).  t: a number or anything 0-d (one tick for the
+        about (INTERPOLATED, HELD, STALE, EMPTY, EARLY, of which the last three are NaN rows, and in mode "predict" PREDICTED).  t: a number or anything 0-d (one tick for the
         pool), or [n]; lists and numpy arrays are read as float64, a tensor of a narrower float type is refused.  A CUDA float64 [n]
         tensor is read WHERE IT LIES, which is what a captured frame needs: it must be contiguous and on this device, else it is
         refused rather than copied behind the caller's back.  Everything else goes through the resampler's own buffer `t`."""
@@ -619,8 +795,12 @@ class PacketResampler:
             else:                                                 # (a 0-d value is broadcast)
                 tq.copy_(h if h.is_cuda else h.contiguous().pin_memory(), non_blocking=True)
         with torch.cuda.device(self.device):
-            _lib.check(self.lib.tip_resample_emit(self.state.data_ptr(), self.n, self.depth, tq.data_ptr(), self.delay, self.max_hold,
-                                                         self.mode, out.data_ptr(), self.flags.data_ptr(), self._stream()))
+            if self.mode == MODES["predict"]:
+                _lib.check(self.lib.tip_predict_emit(self.state.data_ptr(), self.n, self.depth, tq.data_ptr(), self.delay, self.max_hold,
+                                                      self.max_predict, out.data_ptr(), self.flags.data_ptr(), self._stream()))
+            else:
+                _lib.check(self.lib.tip_resample_emit(self.state.data_ptr(), self.n, self.depth, tq.data_ptr(), self.delay, self.max_hold,
+                                                             self.mode, out.data_ptr(), self.flags.data_ptr(), self._stream()))
         return out
 
     def reset(self, slots=None):
@@ -687,16 +867,52 @@ def sequence_ticks(times, rate_hz=60.0, delay=0.0, t_start=None):
     return ticks[ticks - delay <= times[-1]]
 
 
+def sync_sequences(stamps_list, arrivals_list, leak=_lib.TIP_CLOCK_LEAK, slew=_lib.TIP_CLOCK_SLEW, device=None):
+    """Recorded sessions whose packets carry the SENSOR's stamps beside the server's arrival times -> the stamps on the server's clock:
+    stamps_list[i] and arrivals_list[i] are [L_i] float64 seconds, and the result is a list of host float64 arrays [L_i], what
+    resample_sequences takes as times_list (a rejected row — a stamp or an arrival time that is not finite, a stamp not above the one
+    before it — is NaN there, which resample_sequences refuses by its row).  Every sequence starts from a reset clock and gets, bit for
+    bit, what a ClockSync(leak=, slew=) gives when it is fed the sequence in any chunking; all sequences in one launch."""
+    who = "sync_sequences"
+    leak, slew = _clock_rule(leak, slew, who)
+    if not len(stamps_list):
+        raise ValueError(f"tip_amd.sensors.{who}: no sequences")
+    if len(stamps_list) != len(arrivals_list):
+        raise ValueError(f"tip_amd.sensors.{who}: {len(stamps_list)} stamp arrays for {len(arrivals_list)} arrival arrays")
+    st, ar, lens = [], [], []
+    for i, (s, a) in enumerate(zip(stamps_list, arrivals_list)):
+        s, a = _times_f64(s, f"tip_amd.sensors.{who}: stamps_list[{i}]"), _times_f64(a, f"tip_amd.sensors.{who}: arrivals_list[{i}]")
+        if s.dim() != 1 or tuple(a.shape) != tuple(s.shape):
+            raise ValueError(f"tip_amd.sensors.{who}: stamps_list[{i}] and arrivals_list[{i}] are [L], one arrival time per stamp; got "
+                             f"{tuple(s.shape)} and {tuple(a.shape)}")
+        st.append(s.detach().cpu())
+        ar.append(a.detach().cpu())
+        lens.append(int(s.shape[0]))
+    dev = _device_of([], device)
+    N = int(sum(lens))
+    if N == 0:
+        return [np.empty(0, dtype=np.float64) for _ in lens]
+    with torch.cuda.device(dev):
+        s, a, off = _pinned_image([(torch.cat(st), torch.float64), (torch.cat(ar), torch.float64),
+                                   (torch.tensor(np.concatenate(([0], np.cumsum(lens))), dtype=torch.int64), torch.int64)], dev)
+        out = torch.empty(N, dtype=torch.float64, device=dev)
+        _lib.check(_lib.load().tip_clock_rows(s.data_ptr(), a.data_ptr(), off.data_ptr(), N, len(lens), leak, slew, out.data_ptr(),
+                                               _lib.current_stream(dev)))
+        host = out.cpu().numpy()
+    return [h.copy() for h in _split(host, lens)]
+
+
 def resample_sequences(packets_list, times_list, rate_hz=60.0, *, mode="slerp", delay=0.0, max_hold=None, depth=8, t_start=None,
-                       device=None, host=False):
+                       device=None, host=False, max_predict=None):
     """Recorded packet sessions whose stamps are not on the grid -> sessions that are: packets_list[i] is [L_i, 42] float32 and
     times_list[i] its stamps [L_i] (host float64; finite and strictly increasing, else a ValueError naming the sequence and the row).
     Sequence i is taken at sequence_ticks(times_list[i], rate_hz, delay, t_start) — t_start None, a number, or one number per sequence —
     and every output row is what a PacketResampler(mode, delay, max_hold, depth) that was pushed everything stamped up to the row's
-    tick emits there, bit for bit, all sequences in one launch.  Returns (packets, flags): lists of CUDA float32 [K_i, 42] and uint8
-    [K_i] (host=True: numpy arrays).  The packets are what transform_sequences takes."""
+    tick emits there, bit for bit, all sequences in one launch (mode "predict" with its max_predict included).  Returns (packets,
+    flags): lists of CUDA float32 [K_i, 42] and uint8 [K_i] (host=True: numpy arrays).  The packets are what transform_sequences takes."""
     who = "resample_sequences"
     mode_c, delay, hold, depth = _resample_rule(mode, delay, max_hold, depth, who)
+    far = _predict_rule(mode, max_predict, who)
     rate = float(rate_hz)
     if not (rate > 0.0 and np.isfinite(rate)):
         raise ValueError(f"tip_amd.sensors.{who}: rate_hz is the tick rate, a finite number > 0; got {rate_hz!r}")
@@ -727,7 +943,12 @@ def resample_sequences(packets_list, times_list, rate_hz=60.0, *, mode="slerp", 
         K = int(sum(out_lens))
         out = torch.empty((K, PACKET), dtype=torch.float32, device=dev)
         flags = torch.empty(K, dtype=torch.uint8, device=dev)
-        _lib.check(lib.tip_resample_rows(packets.data_ptr(), stamps.data_ptr(), in_off.data_ptr(), int(packets.shape[0]), t_out.data_ptr(),
-                                           out_off.data_ptr(), K, len(lens), delay, hold, mode_c, depth, out.data_ptr(), flags.data_ptr(),
-                                           _lib.current_stream(dev)))
+        if mode_c == MODES["predict"]:
+            _lib.check(lib.tip_predict_rows(packets.data_ptr(), stamps.data_ptr(), in_off.data_ptr(), int(packets.shape[0]), t_out.data_ptr(),
+                                             out_off.data_ptr(), K, len(lens), delay, hold, far, depth, out.data_ptr(), flags.data_ptr(),
+                                             _lib.current_stream(dev)))
+        else:
+            _lib.check(lib.tip_resample_rows(packets.data_ptr(), stamps.data_ptr(), in_off.data_ptr(), int(packets.shape[0]), t_out.data_ptr(),
+                                               out_off.data_ptr(), K, len(lens), delay, hold, mode_c, depth, out.data_ptr(), flags.data_ptr(),
+                                               _lib.current_stream(dev)))
     return _recordings(out, flags, out_lens, host, True)
