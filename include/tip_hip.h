@@ -883,6 +883,35 @@ tip_terrain_track_scaled(const void* skel, void* state, int n_slots, int grid_nu
                          float* viz_out /* [n_rows,5,3] */, float* q_hist_out /* [n_rows,54] */, int* fire_out /* [n_rows] */,
                          const float* scale /* [n_slots], by block */, tip_stream_t stream);
 
+/* ---- hand-over: a live wearer's state moved between pools (tip_amd.handover).  Every per-wearer state above is a block of
+ *      *_state_bytes(1, ...) bytes at slot * that in its buffer — tip_stream_state_bytes_w, tip_sensor_state_bytes, tip_fill_state_bytes,
+ *      tip_resample_state_bytes, tip_clock_state_bytes, tip_kin_carry_bytes, tip_terrain_state_bytes — so a wearer leaves one pool and
+ *      enters another (of another n, on another device through the host, after a restart) as those bytes, and continues bit for bit.
+ *      All lists are DEVICE arrays; every call is asynchronous on `stream`; nothing is read by the host.
+ *      tip_handover_export: for each j < count, block slots[j] of `state` (n_slots blocks of block_bytes) -> out + j * out_stride.
+ *      tip_handover_import: the other way.  An entry outside [0, n_slots) is skipped and its row (export) or block (import) left
+ *        untouched — tip_stream_history_override's convention.  A slot listed twice in an import is the caller's error (either row may win).
+ *      tip_handover_stream_import: tip_handover_import for stream blocks (40-row and any-length layout, window 1 .. 128 as the _w family).
+ *        Words of a block that belong to the BUFFER, not to the wearer — the complete list, over all seven states: the stream block's
+ *        shape word (float index 10474 at window 40, word 2 otherwise: model shape, and the window tag in bits 16-30).  It is not copied,
+ *        and it is compared first: a block whose stored shape word differs from the destination block's (or, any-length layout, a
+ *        destination whose block 0 does not confirm `window`) is skipped, the slot untouched.  refused (nullable, [count] device ints):
+ *        entry j <- slots[j] where the block was skipped for that reason, -1 otherwise.  The frame counter and the attached flag travel
+ *        with the block.  No other block stores its slot index or anything derived from n: the terrain block's grid_num and max_regions
+ *        words are the wearer's map's, and the host refuses a destination that was built with others; per-slot arrays BESIDE the
+ *        blocks (the trackers' scale [n], fire [n], whose entries are slot indices) are the host's to carry and rewrite.
+ *      Refused with TIP_ERR_INVALID_ARG before any launch: null state / out / in, a null list with count > 0, negative counts,
+ *        block_bytes 0 or not a multiple of 4, a stride below block_bytes or not a multiple of 4, a base or list that is not 4-byte
+ *        aligned, a window outside [1, 128].  count = 0 returns TIP_OK without a launch.
+ *      One workgroup per (entry, 16-KiB chunk); 16-byte loads and stores when block_bytes, the stride and both bases are multiples of
+ *        16, 4-byte ones otherwise (chosen per launch); no LDS; nothing waits on another workgroup. */
+TIP_API int tip_handover_export(const void* state, int n_slots, size_t block_bytes, const int* slots /* [count] */, int count,
+                                void* out, size_t out_stride, tip_stream_t stream);
+TIP_API int tip_handover_import(void* state, int n_slots, size_t block_bytes, const int* slots /* [count] */, int count,
+                                const void* in, size_t in_stride, tip_stream_t stream);
+TIP_API int tip_handover_stream_import(void* state, int n_streams, const int* slots /* [count] */, int count, const void* in,
+                                       size_t in_stride, int window, int* refused /* [count] or null */, tip_stream_t stream);
+
 /* ---- synthetic data: IMU readings and stationary-body-point (SBP) labels from pose sequences — the reference's offline generator
  *      (data-gen-and-viz-bullet-new.py:44-218 over data_utils.py:27-100 get_rot_center_sample_based; bullet_agent.py for the scale),
  *      for `count` ragged sequences held back to back: sequence j is rows offsets[j] .. offsets[j + 1] - 1 of every array, offsets

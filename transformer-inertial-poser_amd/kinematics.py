@@ -493,6 +493,7 @@ class _Tracker:
             self.scale = torch.ones(self.n, dtype=torch.float32, device=self.device)      # the slots' body scales; 1 until a reset gives one
         self._outs = (self.root, self.viz_locs)
         self._lists = {}
+        self._scale_host = np.ones(self.n, dtype=np.float32)      # the scales as the resets gave them (host): what a hand-over checks
 
     def _slot_tensors(self, slots, who):
         import torch
@@ -525,6 +526,7 @@ class _Tracker:
         if self._s.scale is not None:
             self._s.scale = None
             self.scale.fill_(1.0)
+            self._scale_host[:] = 1.0
 
     def reset(self, slots, s_init_rows, scales=None):
         import torch
@@ -551,6 +553,7 @@ class _Tracker:
                     self.scale[rows] = _scales_dev(scales, self.device)
                 elif self._s.scale is not None:
                     self.scale[rows] = 1.0
+                self._scale_host[slice(None) if sl is None else list(idx)] = 1.0 if scales is None else scales
                 self._s.reset(sl, count, s0)
                 self.root[rows] = s0[:, :3]
                 self.viz_locs[rows] = 100.0
@@ -574,6 +577,22 @@ class _Tracker:
             if idx:
                 self._s.track(sl, be[0].data_ptr(), be[1].data_ptr(), len(idx), s, c, v, *self._outs)
         return self.root, self.viz_locs
+
+    # ---- wearer hand-over (tip_amd.handover) ---------------------------------------------------------------------------------------------
+    def export_slots(self, slots):
+        """The listed slots' wearers as they stand (tip_amd.handover): their state block, body scale and output rows as device tensors,
+        plus plain metadata (block size, the skeleton table, the scales as the host gave them).  Nothing is reset or detached; one
+        launch and a few gathers on the current stream, no synchronisation."""
+        from . import handover
+        return handover.export_tracker(self, slots)
+
+    def import_slots(self, slots, exported):
+        """Put exported wearers into the listed slots: from the next step on each continues bit for bit where it was.  The skeleton table
+        and block layout (a terrain tracker: grid_num, max_regions, multi_sbp) must be the exporter's, and a tracker that has never been
+        given scales refuses a wearer whose scale is not 1 (ValueError, before anything is launched); one that has takes any.  The
+        entries of `fire` that travel are rewritten to the new slot indices."""
+        from . import handover
+        handover.import_tracker(self, slots, exported)
 
 
 class RootTracker(_Tracker):

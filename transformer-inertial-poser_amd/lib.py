@@ -66,6 +66,7 @@ EXPORTS = (
     "tip_kin_skel_bytes", "tip_kin_carry_bytes", "tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_kin_metrics",
     "tip_terrain_state_bytes", "tip_terrain_reset", "tip_terrain_track",
     "tip_kin_fk_scaled", "tip_kin_track_reset_scaled", "tip_kin_track_scaled", "tip_terrain_reset_scaled", "tip_terrain_track_scaled",
+    "tip_handover_export", "tip_handover_import", "tip_handover_stream_import",
     "tip_syn_skel_bytes", "tip_syn_grid_bytes", "tip_syn_poses", "tip_syn_imu", "tip_syn_sbp",
     "tip_motion_tile", "tip_motion_qdq",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
@@ -252,6 +253,10 @@ def load() -> ctypes.CDLL:
         at = getattr(lib, name).argtypes
         getattr(lib, name + "_scaled").argtypes = at[:-1] + [vp, vp]
     # synthetic data (csrc/tip_syn.hip): device buffers, counts, then the stream
+    # hand-over (include/tip_hip.h, "hand-over"; tip_amd.handover)
+    lib.tip_handover_export.argtypes = [vp, i32, sz, vp, i32, vp, sz, vp]
+    lib.tip_handover_import.argtypes = [vp, i32, sz, vp, i32, vp, sz, vp]
+    lib.tip_handover_stream_import.argtypes = [vp, i32, vp, i32, vp, sz, i32, vp, vp]
     lib.tip_syn_skel_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_syn_grid_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_syn_poses.argtypes = [vp, vp, i32, vp, i32, vp, ctypes.c_longlong, vp, vp]

@@ -302,6 +302,20 @@ class SensorFrontEnd:
         """bool [len(slots)] (numpy; None: all n): the slot's calibration is finished or loaded — transform gives it finite rows."""
         return self.mirror.live(None if slots is None else self._slots(slots, "live"))
 
+    # ---- wearer hand-over (tip_amd.handover) -----------------------------------------------------------------------------------------
+    def export_slots(self, slots):
+        """The listed slots' calibrations as they stand — a hold in progress included: its fp64 sums, count and phase are in the block —
+        with their PhaseMirror entries and, with fill=True, their fill rings: a dict of device tensors plus `meta` (tip_amd.handover).
+        One launch per buffer on the current stream, no synchronisation."""
+        from . import handover
+        return handover.export_front(self, slots)
+
+    def import_slots(self, slots, exported):
+        """Put exported calibrations into the listed slots, whatever those held; both front ends must agree on `fill` (ValueError
+        otherwise, before anything is launched).  A hold in progress goes on where it was: accumulate() and finish() on this object."""
+        from . import handover
+        handover.import_front(self, slots, exported)
+
     # ---- the per-frame launch --------------------------------------------------------------------------------------------------------
     def transform(self, packets, out=None):
         """packets [n, 42] -> the calibrated frame [n, 72] the engines' step() takes (54 rotation columns, 18 acceleration columns), into
@@ -664,6 +678,17 @@ class ClockSync:
                                                    counts.data_ptr(), self._stream()))
         return theta, counts
 
+    def export_slots(self, slots):
+        """The listed slots' envelopes (32 bytes each) for import_slots of another ClockSync (tip_amd.handover); leak and slew belong to
+        the object, not the wearer.  One launch, no synchronisation."""
+        from . import handover
+        return handover.export_simple(self, slots, "clock")
+
+    def import_slots(self, slots, exported):
+        """Put exported envelopes into the listed slots, whatever those held (a block of another size: ValueError, nothing launched)."""
+        from . import handover
+        handover.import_simple(self, slots, exported, "clock")
+
     def offsets(self, slots=None):
         """The offset estimates (server's clock minus sensor's, seconds) of the listed slots (None: all): a CUDA float64 tensor."""
         return self._get(slots, "offsets")[0]
@@ -802,6 +827,17 @@ class PacketResampler:
                 _lib.check(self.lib.tip_resample_emit(self.state.data_ptr(), self.n, self.depth, tq.data_ptr(), self.delay, self.max_hold,
                                                              self.mode, out.data_ptr(), self.flags.data_ptr(), self._stream()))
         return out
+
+    def export_slots(self, slots):
+        """The listed slots' packet rings for import_slots of another PacketResampler of the same `depth` (tip_amd.handover); mode, delay
+        and limits belong to the object, not the wearer.  One launch, no synchronisation."""
+        from . import handover
+        return handover.export_simple(self, slots, "resampler")
+
+    def import_slots(self, slots, exported):
+        """Put exported rings into the listed slots, whatever those held; another `depth` is a ValueError before anything is launched."""
+        from . import handover
+        handover.import_simple(self, slots, exported, "resampler")
 
     def reset(self, slots=None):
         """Empty the rings and zero the counters of the listed slots (None: all): a slot that takes a new wearer."""

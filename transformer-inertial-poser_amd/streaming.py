@@ -60,6 +60,10 @@ IK on the device and hands its pose back without the host reading anything.
 step_packets(front, packets), both engines: the frame from RAW sensor packets [n, 42] instead of the calibrated frame — `front` is a
 tip_amd.sensors.SensorFrontEnd (the live demo's calibration and per-frame transform, live_demo_new.py:161-175, on the device), whose
 one launch fills the engine's `raw`; everything behind "raw is filled" is step()'s (_step_filled), bit for bit.
+
+export_slots(slots) / import_slots(slots, exported), StaggeredStreamingEngine: a live slot's whole state — its block, its rows, the
+s_init it was attached with, its age — into a slot of another staggered engine of any n (plain or compact), where it continues bit for
+bit instead of starting at its frame 0 (tip_amd.handover: the whole chain around the engine, files, other devices).
 """
 from __future__ import annotations
 
@@ -530,6 +534,16 @@ class StreamingEngine(_StreamBase):
         self._packets_to_raw(front, packets, range(self.n))
         return self._step_filled(self.raw)
 
+    def export_slots(self, slots):
+        """Not served: one frame counter serves all streams of a lock-step engine, so a single stream has no state of its own to take
+        along.  Wearers that come and go live in a StaggeredStreamingEngine."""
+        raise RuntimeError("tip_amd.StreamingEngine.export_slots: a lock-step engine keeps one frame counter for all its streams; "
+                           "wearer hand-over is StaggeredStreamingEngine.export_slots / import_slots")
+
+    def import_slots(self, slots, exported):
+        raise RuntimeError("tip_amd.StreamingEngine.import_slots: a lock-step engine keeps one frame counter for all its streams; "
+                           "wearer hand-over is StaggeredStreamingEngine.export_slots / import_slots")
+
     def _step_filled(self, raw) -> Optional[dict]:
         """The frame behind "raw is filled" (raw: [n, 72] on the device; self.raw when the frame replays)."""
         f = self.frame
@@ -616,6 +630,7 @@ class StaggeredStreamingEngine(_StreamBase):
             self.y_slot = torch.full((self.n, self.model.size_s), float("nan"), dtype=torch.float32, device=self.device)
             self.rows_slot = torch.full((self.n,), -1, dtype=torch.int32, device=self.device)
             self._fed, self.fed_frames = None, 0          # device-fed frames (_step_fed): the feeder's two launches, frames launched
+            self._s_arriving = []     # import_slots: (event, slots, pinned rows) of s_init rows still on their way to s_host (_s_host_settle)
 
     def _attach_dev(self, idx):
         if not idx:
@@ -656,6 +671,7 @@ class StaggeredStreamingEngine(_StreamBase):
         for i in idx:
             self._attach_frame[i] = self.frame
         if self.compact:            # host only: the device work goes with the next step's single upload (_flush)
+            self._s_host_settle()
             self.s_host[idx] = rows
             for i in idx:
                 self._attached[i] = True
@@ -683,6 +699,38 @@ class StaggeredStreamingEngine(_StreamBase):
         with torch.cuda.device(self.device):
             sl = self._to_dev(torch.tensor(idx, dtype=torch.int32))
             self._call("detach", self.state.data_ptr(), self.n, sl.data_ptr(), len(idx))
+
+    # ---- wearer hand-over (tip_amd.handover) ---------------------------------------------------------------------------------------------
+    def _s_host_settle(self):
+        """compact=True: the s_init rows an import_slots took from a DEVICE export reach s_host by a non-blocking copy into pinned
+        memory; whoever reads or writes s_host next (an attach, a re-prime's flush) waits for that copy's event here — long past, as a
+        rule — and stores the rows.  Nothing to do otherwise."""
+        for ev, idx, rows in self._s_arriving:
+            ev.synchronize()
+            self.s_host[idx] = rows
+        self._s_arriving = []
+
+    def export_slots(self, slots):
+        """The listed ATTACHED slots' wearers as they stand, for import_slots of another StaggeredStreamingEngine (tip_amd.handover; plain
+        or compact, any n, the same window and model shape): a dict of device tensors — `block` [count, block bytes] (rings, pose
+        average, frame counter, attached flag), the slots' rows of s_rest, c_t, y_last and T - 1, the s_init rows they were last attached
+        with — and `meta`, plain numbers: window, widths, block size and each slot's age in frames (what override_history asks for).
+        Exporting does not detach: that is the caller's next call.  A compact pool flushes its pending attach / detach first; then one
+        launch and a few gathers on the current stream, after the last frame, no synchronisation.
+        live_dropout=True: the blocks move exactly, but the dropout seeds are the ENGINE's, not the wearer's: after an import the wearer
+        draws the destination's masks, so its rows differ from an uninterrupted run's (both are draws of the same model)."""
+        from . import handover
+        return handover.export_engine(self, slots)
+
+    def import_slots(self, slots, exported):
+        """Put exported wearers into the listed DETACHED slots (RuntimeError for an attached one; ValueError for another window, model
+        shape or block size — all before anything is launched).  The slots become attached at the age they had: from the next step()
+        on each continues bit for bit where it was on a plan whose per-window result does not depend on the batch (set_plan("fused"),
+        compact=True's rule).  A compact pool gives each a window position as attach does (SlotPositions.attach) and uploads the map with
+        the next frame's flush.  Runs on the current stream behind the previous frame, between two replays with use_graph=True: no
+        pointer changes, nothing is re-captured.  No synchronisation."""
+        from . import handover
+        handover.import_engine(self, slots, exported)
 
     def _override_ready(self, idx):
         for i in idx:
@@ -743,6 +791,8 @@ class StaggeredStreamingEngine(_StreamBase):
         if not (self._map_dirty or self._pending_attach or self._pending_detach):
             return
         att, det = list(self._pending_attach), list(self._pending_detach)
+        if att:
+            self._s_host_settle()
         h, (o_att, o_det, o_rows) = stage_image(self.n, self._positions.slot_at, att, det, self.s_host[att].numpy())
         self._stage[: h.size].copy_(torch.from_numpy(h).pin_memory(), non_blocking=True)
         base = self._stage.data_ptr()
