@@ -912,6 +912,72 @@ TIP_API int tip_handover_import(void* state, int n_slots, size_t block_bytes, co
 TIP_API int tip_handover_stream_import(void* state, int n_streams, const int* slots /* [count] */, int count, const void* in,
                                        size_t in_stride, int window, int* refused /* [count] or null */, tip_stream_t stream);
 
+/* ---- session recorder: the rows a live pool's wearers were served, logged on the device and handed to the host a page at a time
+ *      (tip_amd.record.SessionRecorder) — the reference's is_recording buffer (live_demo_new.py:276-278, 312-323), for n wearers and
+ *      without a host copy per frame.  A consumer BESIDE the frame, as tip_kin_track and tip_terrain_track are: one launch behind the
+ *      engine's frame on the same stream, reading the engine's static buffers; no engine, front-end, tracker, replay or hand-over kernel
+ *      is involved.  Every call is asynchronous on `stream`, all lists are DEVICE arrays, nothing is read by the host, and NOTHING
+ *      WAITS: no kernel here polls a word another workgroup writes.  The calls on one state buffer are ordered by the stream they share.
+ *      State: ONE buffer of tip_record_state_bytes(n, P, R, W) bytes, 16-byte aligned (n slots, P pages of R rows of W floats), int32
+ *      words unless said otherwise:
+ *          byte 0         header, 64 bytes: 0 magic, 1 n, 2 P, 3 R, 4 W, 5 free-ring head, 6 free-ring tail, 7 full-queue head,
+ *                         8 full-queue tail (all four counters run on, taken modulo P as indices), 9 the drain's arrival count
+ *          64             slot heads, 32 bytes per slot: 0 open flag, 1 session id, 2 rows written, 3 current page (-1: none),
+ *                         4 rows in the current page, 5 rows dropped, 6 pages dropped (runs of dropped rows: page requests that were
+ *                         refused behind a row that was stored), 7 rows dropped since the last stored row
+ *          64 + 32 n      page records, 32 bytes per page: 0 slot, 1 session id, 2 sequence number within the session, 3 rows used,
+ *                         4 rows dropped directly in front of this page's first row (> 0: the page FOLLOWS A GAP), 5-7 unused
+ *          + 32 P         free ring int32[P] (padded to 16 bytes), then the full queue int32[P] (padded likewise): pages ready for the host
+ *          + ...          the pages, P * R * W floats
+ *      A page of a session is pushed onto the full queue the moment it fills, so every page of a session but its last is full and a
+ *      page's first row is row seq * R of the session's stored rows.
+ *      tip_record_reset: header, heads, records and rings for the stated shape; every page free, every slot closed.
+ *      tip_record_open: for each j < count, slot slots[j] starts session sessions[j] with every counter at 0.  An entry outside
+ *        [0, n_slots) is skipped (the hand-over's convention), an open slot is left as it is; a slot listed twice is the caller's error.
+ *      tip_record_close: the listed slots stop: a partly filled page goes onto the full queue with its row count, the slot becomes closed
+ *        (its head keeps the session's counters until the next open).  Closing a slot that is not open does nothing; a slot listed
+ *        twice in one close is the caller's error (its page may be queued twice).
+ *      tip_record_append: THE PER-FRAME LAUNCH.  srcs is a HOST table of n_srcs <= TIP_RECORD_MAX_SOURCES sources, passed to the kernel
+ *        by value (the launch reads no table from memory, and the host can choose the copy's vector from it): a slot's row is row `slot`
+ *        of every source, one behind the other, and the columns must add up to W (the kernel checks it against the buffer's header and
+ *        writes nothing otherwise; likewise for another n_slots).  valid (nullable, device int32[n_slots]): a slot appends only where
+ *        valid[slot] >= valid_min — valid_min = 1 for an array of window lengths T (a priming or detached slot has T = 0 and writes
+ *        nothing), 0 for the engines' static arrays of T - 1; with valid null every open slot appends.  No argument changes from frame to
+ *        frame, so the launch can sit inside a captured frame.  One wave per slot.  An open slot without a page pops one from the free
+ *        ring: ONE device-scope atomic add on the ring's head, checked against its tail (and taken back when nothing was free); a page
+ *        that fills is stamped and pushed onto the full queue with one atomic add on that queue's tail.  When no page is free the row is
+ *        DROPPED AND COUNTED (head words 5-7) and written nowhere; the slot's next stored row starts a new page whose record word 4
+ *        holds the rows dropped in front of it.  When FEWER pages are free than slots ask for one in the same frame, exactly as many
+ *        slots get one as pages are free (successful claims take distinct ring entries; once a claim has failed none after it in the
+ *        launch succeeds; the head ends where it belongs) and every other asking slot counts its row as dropped; only WHICH of them
+ *        get one is not defined.  Rows are copied as 16-byte
+ *        vectors when every source's columns and stride are multiples of 4 floats and every base is 16-byte aligned, 4 bytes at a
+ *        time otherwise (chosen per launch).
+ *      tip_record_drain: the first min(pages on the full queue, max_pages) pages of the queue -> staging, those pages back onto the free
+ *        ring, the queue advanced.  staging (tip_record_staging_bytes(max_pages, R, W) bytes, 16-byte aligned): 16 int32 words — 0 pages
+ *        gathered, 1 pages still queued, 2 pages in use after the drain (with slots or queued), 3 n, 4 P, 5 R, 6 W, 7 max_pages — then
+ *        max_pages page records, then max_pages pages of R * W floats; entries from the gathered count on are left as they were.
+ *        out_count (nullable, device int): <- word 0.  It runs in stream order behind an append and in front of the next: no pop is
+ *        ever concurrent with a push onto the free ring.
+ *      Refused with TIP_ERR_INVALID_ARG before any launch: a null or misaligned state / staging / bytes, a null list with count > 0,
+ *        negative counts, pages < 1, page_rows < 1, width < 1 (W = 0), a null source table, n_srcs outside [1, 8], a source with a null
+ *        or misaligned base, columns < 1 or a stride below its columns, max_pages < 1.  count = 0 and n_slots = 0 launch nothing. */
+#define TIP_RECORD_MAX_SOURCES 8
+typedef struct tip_record_source {
+    const float* data; /* device, [n_slots] rows */
+    int cols;          /* floats taken from each row */
+    int stride;        /* floats from one row to the next (>= cols) */
+} tip_record_source;
+TIP_API int tip_record_state_bytes(int n_slots, int pages, int page_rows, int width, size_t* bytes);
+TIP_API int tip_record_staging_bytes(int max_pages, int page_rows, int width, size_t* bytes);
+TIP_API int tip_record_reset(void* state, int n_slots, int pages, int page_rows, int width, tip_stream_t stream);
+TIP_API int tip_record_open(void* state, int n_slots, const int* slots /* [count] */, const int* sessions /* [count] */, int count,
+                            tip_stream_t stream);
+TIP_API int tip_record_close(void* state, int n_slots, const int* slots /* [count] */, int count, tip_stream_t stream);
+TIP_API int tip_record_append(void* state, int n_slots, const tip_record_source* srcs /* HOST, [n_srcs] */, int n_srcs,
+                              const int* valid /* [n_slots] or null */, int valid_min, tip_stream_t stream);
+TIP_API int tip_record_drain(void* state, void* staging, int max_pages, int* out_count /* or null */, tip_stream_t stream);
+
 /* ---- synthetic data: IMU readings and stationary-body-point (SBP) labels from pose sequences — the reference's offline generator
  *      (data-gen-and-viz-bullet-new.py:44-218 over data_utils.py:27-100 get_rot_center_sample_based; bullet_agent.py for the scale),
  *      for `count` ragged sequences held back to back: sequence j is rows offsets[j] .. offsets[j + 1] - 1 of every array, offsets

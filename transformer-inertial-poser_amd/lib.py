@@ -67,6 +67,8 @@ EXPORTS = (
     "tip_terrain_state_bytes", "tip_terrain_reset", "tip_terrain_track",
     "tip_kin_fk_scaled", "tip_kin_track_reset_scaled", "tip_kin_track_scaled", "tip_terrain_reset_scaled", "tip_terrain_track_scaled",
     "tip_handover_export", "tip_handover_import", "tip_handover_stream_import",
+    "tip_record_state_bytes", "tip_record_staging_bytes", "tip_record_reset", "tip_record_open", "tip_record_close", "tip_record_append",
+    "tip_record_drain",
     "tip_syn_skel_bytes", "tip_syn_grid_bytes", "tip_syn_poses", "tip_syn_imu", "tip_syn_sbp",
     "tip_motion_tile", "tip_motion_qdq",
     "tip_train_bytes", "tip_train_saved_view", "tip_train_forward", "tip_train_backward", "tip_train_input_grads",
@@ -95,6 +97,14 @@ class TipConfig(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "input_size_imu", "size_s", "rnn_hid_size", "tf_hid_size", "tf_in_dim", "n_heads", "tf_layers",
         "with_rnn", "with_acc_sum", "t_max")]
+
+
+TIP_RECORD_MAX_SOURCES = 8
+
+
+class RecordSource(ctypes.Structure):
+    """tip_record_source: one source of tip_record_append — a device base, the floats taken from each row, the floats between rows."""
+    _fields_ = [("data", ctypes.c_void_p), ("cols", ctypes.c_int32), ("stride", ctypes.c_int32)]
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
@@ -257,6 +267,14 @@ def load() -> ctypes.CDLL:
     lib.tip_handover_export.argtypes = [vp, i32, sz, vp, i32, vp, sz, vp]
     lib.tip_handover_import.argtypes = [vp, i32, sz, vp, i32, vp, sz, vp]
     lib.tip_handover_stream_import.argtypes = [vp, i32, vp, i32, vp, sz, i32, vp, vp]
+    # session recorder (include/tip_hip.h, "session recorder"; tip_amd.record): the source table is a HOST array of RecordSource
+    lib.tip_record_state_bytes.argtypes = [i32, i32, i32, i32, ctypes.POINTER(sz)]
+    lib.tip_record_staging_bytes.argtypes = [i32, i32, i32, ctypes.POINTER(sz)]
+    lib.tip_record_reset.argtypes = [vp, i32, i32, i32, i32, vp]
+    lib.tip_record_open.argtypes = [vp, i32, vp, vp, i32, vp]
+    lib.tip_record_close.argtypes = [vp, i32, vp, i32, vp]
+    lib.tip_record_append.argtypes = [vp, i32, ctypes.POINTER(RecordSource), i32, vp, i32, vp]
+    lib.tip_record_drain.argtypes = [vp, vp, i32, vp, vp]
     lib.tip_syn_skel_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_syn_grid_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_syn_poses.argtypes = [vp, vp, i32, vp, i32, vp, ctypes.c_longlong, vp, vp]

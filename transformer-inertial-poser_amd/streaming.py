@@ -69,6 +69,7 @@ from __future__ import annotations
 
 import bisect
 import ctypes
+import gc
 from typing import Optional
 
 import numpy as np
@@ -398,8 +399,18 @@ class _StreamBase:
         torch.cuda.current_stream(self.device).synchronize()
         self._poll_handoff()
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._y_last = self._captured_frame(key)
+        # no cycle collection inside the capture: a dead cycle may hold another engine's captured graphs, pinned buffers or a library
+        # handle (a dropped pool is one: its feeder closures point back at its engine), and their finalizers make HIP calls that a
+        # capturing thread must not make.  torch.cuda.graph no longer collects on entry, so the collector could fire on any allocation
+        # of the frame's host code.  What is dead now is collected as usual once the capture has ended.
+        collecting = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self._y_last = self._captured_frame(key)
+        finally:
+            if collecting:
+                gc.enable()
         self._graphs[key] = (g, self._graph_ws, self.model._packed_dev, self._graph_y)
         self.captures += 1
         return g
