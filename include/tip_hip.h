@@ -885,14 +885,15 @@ tip_terrain_track_scaled(const void* skel, void* state, int n_slots, int grid_nu
 
 /* ---- hand-over: a live wearer's state moved between pools (tip_amd.handover).  Every per-wearer state above is a block of
  *      *_state_bytes(1, ...) bytes at slot * that in its buffer — tip_stream_state_bytes_w, tip_sensor_state_bytes, tip_fill_state_bytes,
- *      tip_resample_state_bytes, tip_clock_state_bytes, tip_kin_carry_bytes, tip_terrain_state_bytes — so a wearer leaves one pool and
+ *      tip_resample_state_bytes, tip_clock_state_bytes, tip_kin_carry_bytes, tip_terrain_state_bytes, and tip_pose_state_bytes of the
+ *      display-time poses below — so a wearer leaves one pool and
  *      enters another (of another n, on another device through the host, after a restart) as those bytes, and continues bit for bit.
  *      All lists are DEVICE arrays; every call is asynchronous on `stream`; nothing is read by the host.
  *      tip_handover_export: for each j < count, block slots[j] of `state` (n_slots blocks of block_bytes) -> out + j * out_stride.
  *      tip_handover_import: the other way.  An entry outside [0, n_slots) is skipped and its row (export) or block (import) left
  *        untouched — tip_stream_history_override's convention.  A slot listed twice in an import is the caller's error (either row may win).
  *      tip_handover_stream_import: tip_handover_import for stream blocks (40-row and any-length layout, window 1 .. 128 as the _w family).
- *        Words of a block that belong to the BUFFER, not to the wearer — the complete list, over all seven states: the stream block's
+ *        Words of a block that belong to the BUFFER, not to the wearer — the complete list, over all eight states: the stream block's
  *        shape word (float index 10474 at window 40, word 2 otherwise: model shape, and the window tag in bits 16-30).  It is not copied,
  *        and it is compared first: a block whose stored shape word differs from the destination block's (or, any-length layout, a
  *        destination whose block 0 does not confirm `window`) is skipped, the slot untouched.  refused (nullable, [count] device ints):
@@ -977,6 +978,89 @@ TIP_API int tip_record_close(void* state, int n_slots, const int* slots /* [coun
 TIP_API int tip_record_append(void* state, int n_slots, const tip_record_source* srcs /* HOST, [n_srcs] */, int n_srcs,
                               const int* valid /* [n_slots] or null */, int valid_min, tip_stream_t stream);
 TIP_API int tip_record_drain(void* state, void* staging, int max_pages, int* out_count /* or null */, tip_stream_t stream);
+
+/* ---- display-time poses: the pool's OUTPUT at the viewer's time (tip_amd.display.PoseResampler; csrc/tip_display.hip).  The input side
+ *      of a pool is free of the 60 Hz grid (timestamped packets, clock sync and predicted ticks, above); its output is not, and it is late
+ *      by construction: the pose a frame produces belongs to IMU_n_smooth = 5 frames before the packet that produced it (the centred
+ *      11-tap acceleration average, real_time_runner.py:279-296, :391-393), and the reference shows it once per clock.tick(FREQ)
+ *      (live_demo_new.py:281-307).  Here a slot keeps a ring of its last poses with their fp64 stamps, and one launch gives every slot
+ *      its pose AT a time of the viewer's choosing — a headset at 72, 90 or 120 Hz, a renderer's next vsync, an export at 30 or 100 fps —
+ *      held, interpolated, or predicted past the newest entry.  A consumer BESIDE the frame, as tip_kin_track and tip_record_append are:
+ *      it reads the tracker's root [n,3] and the engine's s_rest [n,ld] (root axis-angle and 17 joint axis-angles in its first 54
+ *      columns) where they lie; no engine, tracker, replay, hand-over or recorder kernel is involved.  Every call is asynchronous on
+ *      `stream`, all arrays are DEVICE arrays, nothing waits on another workgroup and there are no atomics.
+ *      `state` is a caller-owned device buffer of tip_pose_state_bytes() (8-byte aligned), one block of bytes / n_slots per slot: the
+ *      packet ring's 16-byte header (the ring index of the oldest entry, have, total, dropped: 4-byte ints), depth fp64 stamps, depth
+ *      rows [57] fp32 (root xyz, then 18 axis-angles: the q of tip_kin_fk), padded to a multiple of 8 bytes.  depth is 2 .. 64.  A row is
+ *      stored exactly as pushed and quaternions are not stored: emit converts the two rows it reads, so a row that is given back is a
+ *      bit-for-bit copy.  A block stores nothing derived from its slot index or from n: tip_handover_export / _import carry it unchanged.
+ *      tip_pose_reset: the blocks of the listed slots, or of all n when slots is null (required once), to zero: an empty ring.
+ *      tip_pose_get: counts_out[count, 3] (device int) = have | dropped | total of the listed slots, with tip_resample_get's conventions.
+ *      tip_pose_push: for each listed slot (slots[count], or all n when slots is null) whose valid[slot] is set (valid null: every one),
+ *        append (t[slot], root[slot, 0:3], s_rest[slot, 0:54]).  A stamp that is not finite, or (have > 0) not above the slot's newest
+ *        stamp, is refused: dropped += 1, nothing else changes.  A slot outside [0, n) is skipped; a slot listed twice is the caller's
+ *        error.  A full ring loses its oldest entry; total += 1.  Every argument is static, so a captured frame can hold the call.  One
+ *        wave per listed slot.
+ *      tip_pose_emit: the per-display-frame launch.  t[n] is a DEVICE array.  Per slot, with tau = t[slot] - delay (fp64) and the ring's
+ *        stamps s_0 < ... < s_last, the decision in modes TIP_POSE_HOLD and TIP_POSE_SLERP is tip_resample_emit's table (timestamped
+ *        packets, above: the kernel calls the same function), and flags[slot] keeps its numbering: 3 empty, 4 early, 1 held, 2 stale,
+ *        0 interpolated.  TIP_POSE_PREDICT is SLERP except where have >= 2 and tau > s_last.  There, with b = min(baseline, have - 1),
+ *        s_a the stamp b entries back from the newest and h = tau - s_last:
+ *          h <= max_predict and (max_hold < 0 or s_last - s_a <= b * max_hold)      predicted at u = (tau - s_a) / (s_last - s_a) > 1, fp64    5
+ *          otherwise                                                                the SLERP rule (the newest entry held, or stale)
+ *        THERE IS NO SPAN RULE: the packet side's TIP_PREDICT_SPAN (at most two brackets past the newest packet) would refuse exactly
+ *        the 5 .. 9 frames this entry exists for; max_predict alone bounds the horizon.  max_predict = 0 predicts no row: every row is
+ *        then bit for bit SLERP's.  baseline > 1 takes the rate over a longer chord: less noise, more lag on a curved track.
+ *        A held row is copied bit for bit; an empty, early or stale row is 57 NaN.  quat_out (nullable, [n,18,4]): the 18 rotations as
+ *        quaternions x y z w — of a held row its conversion below, of an interpolated or predicted row the unit quaternion the
+ *        axis-angle came from, its sign the earlier row's; NaN where the row's columns are.
+ *      The arithmetic, per (slot, part), 18 rotation parts and the root, a the earlier row and b the later one.  fp32 unless said, every
+ *        sum left to right, nothing contracted:
+ *          Axis-angle a -> quaternion: t2 = a0 a0 + a1 a1 + a2 a2, t = sqrt(t2); s = 1/2 - t2 / 48 below t = 1e-3, else
+ *            s = sin(t / 2) / t (fp64, rounded once); q = (s a0, s a1, s a2, cos(t / 2) (fp64, rounded once)).  t = 0 is the identity.
+ *            A non-finite component makes that joint's three output columns (and its four quaternion columns) NaN and touches nothing else.
+ *          dot = qa0 qb0 + qa1 qb1 + qa2 qb2 + qa3 qb3; not (|dot| > TIP_POSE_ANTIPODAL): the two rotations are pi apart, there is no
+ *            shorter arc, and the joint is NaN (its neighbours are untouched).
+ *          Between the rows (flag 0): the quaternion statements of the packet interpolation above — normalise, the shorter arc, fp64
+ *            weights rounded once, q normalised; the kernel calls that function with a zero acceleration.  Past the newer row (flag 5):
+ *            the predicted sensor's statements of "clock sync and predicted ticks" — the chord's asin above d = 1 - 1e-6, linear weights
+ *            only below th = 1e-5 — likewise called.
+ *          Quaternion q -> axis-angle: w < 0: q = -q.  v2 = x x + y y + z z, v = sqrt(v2); k = 2 + v2 / 3 below v = 1e-3, else
+ *            k = 2 atan2(v, w) / v (fp64, rounded once); out = (k x, k y, k z): the angle is in [0, pi], so an axis-angle above pi comes
+ *            back as its equivalent.
+ *          Root position: uf = (float) u, vf = 1 - uf, p_c = vf pa_c + uf pb_c.  The same statement covers u in [0, 1) and u > 1: the
+ *            root moves on at the finite-difference velocity of the two entries.  A non-finite component in either row makes the three
+ *            root columns NaN.
+ *        One thread per (slot, part), tip_pose_tile slots per workgroup; part 0 of a slot decides and the others read the decision from LDS.
+ *      tip_pose_rows: tip_resample_rows for poses.  Sequence j is rows in_offsets[j] .. in_offsets[j + 1] - 1 of stamps[n_in] (strictly
+ *        increasing within a sequence: the host checks), root[n_in,3] and rows[n_in,ld] (its first 54 columns), and its output rows
+ *        out_offsets[j] .. out_offsets[j + 1] - 1 of q_out[n_out,57], quat_out (nullable, [n_out,18,4]) and flags[n_out], taken at
+ *        t_out[n_out].  An output row sees what a live ring would hold at its time — the entries of its sequence with a stamp <=
+ *        t_out[row], of these the last `depth`, found by searches — and then the rule of tip_pose_emit, bit for bit.  A row no sequence
+ *        owns is NaN with flag 3; offsets are clamped and trusted as tip_resample_rows states.
+ *      Null buffers, misaligned state or times, negative counts, a depth outside 2 .. 64, ld < 54, a baseline outside 1 .. depth - 1, a
+ *      delay or max_predict that is negative or not finite, a NaN max_hold and an unknown mode return TIP_ERR_INVALID_ARG before any
+ *      launch; n_slots = 0, count = 0 with a list, n_out = 0 launch nothing. */
+#define TIP_POSE_HOLD      0
+#define TIP_POSE_SLERP     1
+#define TIP_POSE_PREDICT   2
+#define TIP_POSE_ANTIPODAL 1e-6f
+TIP_API int tip_pose_tile(int* slots);
+TIP_API int tip_pose_state_bytes(int n_slots, int depth, size_t* bytes);
+TIP_API int tip_pose_reset(void* state, int n_slots, int depth, const int* slots /* or null: all */, int count, tip_stream_t stream);
+TIP_API int tip_pose_get(const void* state, int n_slots, int depth, const int* slots, int count, int* counts_out /* [count,3] */,
+                 tip_stream_t stream);
+TIP_API int tip_pose_push(void* state, int n_slots, int depth, const int* slots /* [count] or null: all */, int count,
+                  const float* root /* [n,3] */, const float* s_rest /* [n,ld] */, int ld, const unsigned char* valid /* [n] or null */,
+                  const double* t /* device [n] */, tip_stream_t stream);
+TIP_API int tip_pose_emit(void* state, int n_slots, int depth, const double* t /* device [n] */, double delay, double max_hold,
+                  double max_predict, int baseline, int mode, float* q_out /* [n,57] */, float* quat_out /* [n,18,4] or null */,
+                  unsigned char* flags /* [n] */, tip_stream_t stream);
+TIP_API int tip_pose_rows(const double* stamps /* [n_in] */, const float* root /* [n_in,3] */, const float* rows /* [n_in,ld] */, int ld,
+                  const long long* in_offsets /* [n_seq+1] */, long long n_in, const double* t_out /* [n_out] */,
+                  const long long* out_offsets /* [n_seq+1] */, long long n_out, int n_seq, double delay, double max_hold,
+                  double max_predict, int baseline, int mode, int depth, float* q_out /* [n_out,57] */,
+                  float* quat_out /* [n_out,18,4] or null */, unsigned char* flags /* [n_out] */, tip_stream_t stream);
 
 /* ---- synthetic data: IMU readings and stationary-body-point (SBP) labels from pose sequences — the reference's offline generator
  *      (data-gen-and-viz-bullet-new.py:44-218 over data_utils.py:27-100 get_rot_center_sample_based; bullet_agent.py for the scale),

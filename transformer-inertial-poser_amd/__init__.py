@@ -18,7 +18,7 @@ def __getattr__(name):
     if name == "TF_RNN_Past_State":
         from .simple_transformer_with_state import TF_RNN_Past_State
         return TF_RNN_Past_State
-    if name in ("lib", "dist", "simple_transformer_with_state", "streaming", "replay", "sensors", "kinematics", "terrain", "handover", "record", "syndata", "motion", "data", "learning_utils"):
+    if name in ("lib", "dist", "simple_transformer_with_state", "streaming", "replay", "sensors", "kinematics", "terrain", "handover", "record", "display", "syndata", "motion", "data", "learning_utils"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

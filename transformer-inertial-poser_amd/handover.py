@@ -2,7 +2,7 @@
 
 Everything around the model lives per wearer in HBM as "n fixed blocks in one buffer", n fixed when the object is built: the streaming
 engine's block, the front end's calibration and fill blocks, the resampler's packet ring, the clock's envelope, a tracker's carry or
-terrain block.  A wearer could enter a pool only through attach(), at its frame 0.  Here it moves as it stands, and continues bit for bit:
+terrain block, the display side's ring of recent poses (display.PoseResampler, poses=).  A wearer could enter a pool only through attach(), at its frame 0.  Here it moves as it stands, and continues bit for bit:
 
     w = export_wearers([3, 7], engine=small, front=front_a, resampler=rs_a, clock=ck_a, tracker=tt_a)     # nothing is detached ...
     small.detach([3, 7])                                                                                  # ... that is the next call
@@ -32,7 +32,7 @@ import torch
 from . import lib as _lib
 from .streaming import slot_list
 
-COMPONENTS = ("engine", "front", "resampler", "clock", "tracker")
+COMPONENTS = ("engine", "front", "resampler", "clock", "tracker", "poses")
 _TRACKER_KINDS = {"RootTracker": 0, "TerrainTracker": 1}
 
 
@@ -299,10 +299,13 @@ def import_front(front, slots, exported):
 def simple_meta(obj, kind) -> dict:
     if kind == "resampler":
         return {"kind": kind, "depth": int(obj.depth), "block_bytes": _state_bytes("tip_resample_state_bytes", 1, int(obj.depth))}
+    if kind == "poses":         # (display.block_bytes is tip_pose_state_bytes(1, depth) on the host: a refusal needs no library)
+        from .display import block_bytes
+        return {"kind": kind, "depth": int(obj.depth), "block_bytes": block_bytes(obj.depth)}
     return {"kind": kind, "block_bytes": _state_bytes("tip_clock_state_bytes", 1)}
 
 
-_SIMPLE_NAME = {"resampler": "sensors.PacketResampler", "clock": "sensors.ClockSync"}
+_SIMPLE_NAME = {"resampler": "sensors.PacketResampler", "clock": "sensors.ClockSync", "poses": "display.PoseResampler"}
 
 
 @torch.no_grad()
@@ -388,6 +391,8 @@ def expected_block_bytes(meta: dict) -> dict:
         return {"block_bytes": _state_bytes("tip_resample_state_bytes", 1, int(meta["depth"]))}
     if kind == "clock":
         return {"block_bytes": _state_bytes("tip_clock_state_bytes", 1)}
+    if kind == "poses":
+        return {"block_bytes": _state_bytes("tip_pose_state_bytes", 1, int(meta["depth"]))}
     if kind == "tracker":
         if int(meta["tracker"]) == 1:
             return {"block_bytes": _state_bytes("tip_terrain_state_bytes", 1, int(meta["grid_num"]), int(meta["max_regions"]))}
@@ -524,27 +529,28 @@ class Wearers:
         return cls(count, parts, abi)
 
 
-def _chain(who, engine, front, resampler, clock, tracker):
-    given = {k: v for k, v in zip(COMPONENTS, (engine, front, resampler, clock, tracker)) if v is not None}
+def _chain(who, engine, front, resampler, clock, tracker, poses=None):
+    given = {k: v for k, v in zip(COMPONENTS, (engine, front, resampler, clock, tracker, poses)) if v is not None}
     if not given:
-        raise ValueError(f"tip_amd.handover.{who}: give at least one of engine=, front=, resampler=, clock=, tracker=")
+        raise ValueError(f"tip_amd.handover.{who}: give at least one of engine=, front=, resampler=, clock=, tracker=, poses=")
     return given
 
 
-def export_wearers(slots, engine=None, front=None, resampler=None, clock=None, tracker=None) -> Wearers:
-    """The wearers in `slots` of every object given — one chain serving the same slots — as they stand.  Nothing is detached or reset."""
-    given = _chain("export_wearers", engine, front, resampler, clock, tracker)
+def export_wearers(slots, engine=None, front=None, resampler=None, clock=None, tracker=None, poses=None) -> Wearers:
+    """The wearers in `slots` of every object given — one chain serving the same slots — as they stand.  Nothing is detached or reset.
+    poses: the chain's display.PoseResampler, whose rings of recent poses travel with the wearers."""
+    given = _chain("export_wearers", engine, front, resampler, clock, tracker, poses)
     idx = [int(i) for i in slots]
     return Wearers(len(idx), {name: obj.export_slots(idx) for name, obj in given.items()})
 
 
-def import_wearers(wearers: Wearers, slots, engine=None, front=None, resampler=None, clock=None, tracker=None):
+def import_wearers(wearers: Wearers, slots, engine=None, front=None, resampler=None, clock=None, tracker=None, poses=None):
     """Put `wearers` into `slots` of the objects given: wearer j goes to slots[j] of each.  Every component the wearers hold must be
     given, and the reverse (ValueError); every object checks its part on the host before ANY of them launches."""
     who = "import_wearers"
     if not isinstance(wearers, Wearers):
         raise ValueError(f"tip_amd.handover.{who}: wearers is a handover.Wearers")
-    given = _chain(who, engine, front, resampler, clock, tracker)
+    given = _chain(who, engine, front, resampler, clock, tracker, poses)
     if set(given) != set(wearers.parts):
         raise ValueError(f"tip_amd.handover.{who}: the wearers hold {sorted(wearers.parts)}, the call gives {sorted(given)} — every component "
                          "of one must be in the other")

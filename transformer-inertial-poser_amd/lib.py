@@ -41,6 +41,8 @@ TIP_SENSOR_HEADING, TIP_SENSOR_TPOSE = 1, 2   # tip_sensor_begin: which hold sta
 TIP_RESAMPLE_HOLD, TIP_RESAMPLE_SLERP = 0, 1   # tip_resample_emit / tip_resample_rows: mode
 TIP_RESAMPLE_PREDICTED = 5                     # tip_predict_emit / tip_predict_rows: the flag of a predicted row
 TIP_CLOCK_LEAK, TIP_CLOCK_SLEW, TIP_PREDICT_SPAN = 2e-4, 0.5, 2.0
+TIP_POSE_HOLD, TIP_POSE_SLERP, TIP_POSE_PREDICT = 0, 1, 2   # tip_pose_emit / tip_pose_rows: mode
+TIP_POSE_ANTIPODAL = 1e-6                      # |qa . qb| at or below this: two rotations pi apart, the joint is NaN
 
 # every symbol include/tip_hip.h declares (tests check that the .so exports exactly these + the hooks of tip_hip_debug.h)
 EXPORTS = (
@@ -63,6 +65,7 @@ EXPORTS = (
     "tip_resample_rows",
     "tip_clock_state_bytes", "tip_clock_reset", "tip_clock_get", "tip_clock_map", "tip_clock_push", "tip_clock_rows",
     "tip_predict_emit", "tip_predict_rows",
+    "tip_pose_tile", "tip_pose_state_bytes", "tip_pose_reset", "tip_pose_get", "tip_pose_push", "tip_pose_emit", "tip_pose_rows",
     "tip_kin_skel_bytes", "tip_kin_carry_bytes", "tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_kin_metrics",
     "tip_terrain_state_bytes", "tip_terrain_reset", "tip_terrain_track",
     "tip_kin_fk_scaled", "tip_kin_track_reset_scaled", "tip_kin_track_scaled", "tip_terrain_reset_scaled", "tip_terrain_track_scaled",
@@ -262,7 +265,15 @@ def load() -> ctypes.CDLL:
     for name in ("tip_kin_fk", "tip_kin_track_reset", "tip_kin_track", "tip_terrain_reset", "tip_terrain_track"):
         at = getattr(lib, name).argtypes
         getattr(lib, name + "_scaled").argtypes = at[:-1] + [vp, vp]
-    # synthetic data (csrc/tip_syn.hip): device buffers, counts, then the stream
+    # display-time poses (csrc/tip_display.hip): state, n, depth first; stamps, query times, delay, max_hold and max_predict are fp64
+    ll = ctypes.c_longlong
+    lib.tip_pose_tile.argtypes = [ctypes.POINTER(i32)]
+    lib.tip_pose_state_bytes.argtypes = [i32, i32, ctypes.POINTER(sz)]
+    lib.tip_pose_reset.argtypes = [vp, i32, i32, vp, i32, vp]
+    lib.tip_pose_get.argtypes = [vp, i32, i32, vp, i32, vp, vp]
+    lib.tip_pose_push.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, vp, vp]
+    lib.tip_pose_emit.argtypes = [vp, i32, i32, vp, f64, f64, f64, i32, i32, vp, vp, vp, vp]
+    lib.tip_pose_rows.argtypes = [vp, vp, vp, i32, vp, ll, vp, vp, ll, i32, f64, f64, f64, i32, i32, i32, vp, vp, vp, vp]
     # hand-over (include/tip_hip.h, "hand-over"; tip_amd.handover)
     lib.tip_handover_export.argtypes = [vp, i32, sz, vp, i32, vp, sz, vp]
     lib.tip_handover_import.argtypes = [vp, i32, sz, vp, i32, vp, sz, vp]
@@ -275,6 +286,7 @@ def load() -> ctypes.CDLL:
     lib.tip_record_close.argtypes = [vp, i32, vp, i32, vp]
     lib.tip_record_append.argtypes = [vp, i32, ctypes.POINTER(RecordSource), i32, vp, i32, vp]
     lib.tip_record_drain.argtypes = [vp, vp, i32, vp, vp]
+    # synthetic data (csrc/tip_syn.hip): device buffers, counts, then the stream
     lib.tip_syn_skel_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_syn_grid_bytes.argtypes = [ctypes.POINTER(sz)]
     lib.tip_syn_poses.argtypes = [vp, vp, i32, vp, i32, vp, ctypes.c_longlong, vp, vp]
